@@ -14,6 +14,17 @@ strong scaling, and c2 tiled once per rank, labelled non-BASELINE), each with it
 (and bound evidence), c2 / c3 / c4 / c5 with a stored-sweep sub-line, c2 / c3 with the drop-in's
 whole BASELINE run timed end to end through mcmc_draw_parameters (run_mcmc_abe.py:60-77).
 
+A plain run does only what `value` needs: it builds the primary workload's sampler, settles the
+clocks, warms up, times exactly --steps sweeps and prints the line — with the roofline of the timed
+launch where the persistent kernel ran it (its events are part of the timed path), without it on
+launch-per-sweep paths.  --dump-outputs DIR then also writes what the timed sweeps left, as a caller
+of the timed path reads it back (HipSampler.get_state): DIR/lambda.npy and DIR/mu.npy [chain][customer],
+DIR/beta.npy [chain][K][D], DIR/sigma.npy [chain][D][D], float64; seed 42 and the committed / seeded
+data make them identical from run to run.  Everything else is behind --full: the `configs` legs, the
+stored-sweep sub-lines, `cold`, `host_us`, the probe kernel's clock reading, the event-timed roofline
+pass of launch-per-sweep paths (also run where --timing-steps is given), the drop-in's whole runs
+and the CPU baselines.
+
 Prints ONE JSON line (rank 0).  value = chains * customers * steps / wall time of the timed region
 (max over ranks).  roofline: the dominant kernel's algorithmic bytes (SURVEY §8d per (chain,
 customer) sweep) per launch / its launch duration measured with HIP events on the sampler's stream
@@ -181,6 +192,28 @@ def load_workload(name: str, world: int = 1):
         if world > 1:
             df = pd.concat([df] * world, ignore_index=True)
     return df, D, covs, chains, burnin, mcmc, thin, sink
+
+
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000  # --dump-outputs writes at most this much
+DUMP_SAMPLE_SEED = 20250720
+
+
+def dump_outputs(path: str, sampler) -> None:
+    """--dump-outputs: the chains' state after the last timed sweep as HipSampler.get_state returns it
+    (at N > 1: rank 0's shard of lambda and mu) — `path`/lambda.npy, mu.npy, beta.npy, sigma.npy,
+    float64.  Where lambda and mu would pass DUMP_LIMIT_BYTES, a fixed seeded sample of the customers
+    (the same for both, ascending; their indices in customers.npy) is written instead."""
+    import numpy as np
+    lam, mu, beta, sigma = sampler.get_state()
+    arrays = {"lambda": lam, "mu": mu, "beta": beta, "sigma": sigma}
+    C, n = lam.shape
+    keep = (DUMP_LIMIT_BYTES - beta.nbytes - sigma.nbytes) // (8 * (2 * C + 1))
+    if n > keep:
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, size=int(keep), replace=False))
+        arrays.update({"lambda": lam[:, idx], "mu": mu[:, idx], "customers": idx})
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def stored_fraction(burnin: int, thin: int, first: int, last: int) -> float:
@@ -382,7 +415,8 @@ def whole_run_e2e(name: str, reps: int = 2) -> dict:
 def run_leg(name: str, world: int, rank: int, local_rank: int, dist, steps: int, warmup: int, *,
             graph_chunk: int = 32, exchange: str = "rccl", settle_ms: float = 0.0, stored_phase: bool = True,
             timing_steps: int = 3000, force_sharded: bool = False, phase: str = "burnin", blocks_per_unit: int = 0,
-            one_call_warmup: bool = False, cold: bool = False, host_split: bool = False) -> dict:
+            one_call_warmup: bool = False, cold: bool = False, host_split: bool = False,
+            roofline_pass: bool = True, probe_clock: bool = True, dump_dir: str | None = None) -> dict:
     """One BASELINE configuration at this world size: `warmup` untimed sweeps, then exactly `steps`
     timed sweeps bracketed by barrier + synchronize (wall time, max over ranks).  The roofline
     comes from HIP events on the sampler's stream: the timed launch itself (persistent kernel) or a
@@ -390,7 +424,11 @@ def run_leg(name: str, world: int, rank: int, local_rank: int, dist, steps: int,
     burn-in longer than the window) the same chains continue 100 sweeps past the burn-in and
     `steps` stored sweeps are timed as well (bi:402-428: the draws or the running sums);
     `whole_run` combines both phases' per-sweep times over the BASELINE run's burn-in + mcmc
-    (c4 / c5; c2 / c3 measure the drop-in end to end instead, see whole_run_e2e)."""
+    (c4 / c5; c2 / c3 measure the drop-in end to end instead, see whole_run_e2e).
+    A plain run's leg (main, without --full) switches off what takes launches of its own:
+    `roofline_pass` (the launch-per-sweep roofline's further sweeps; the persistent kernel's roofline
+    is the timed launch's) and `probe_clock` (the probe kernel, where the kernel's own record
+    exists).  `dump_dir`: dump_outputs right after the timed sweeps."""
     import torch
     from mcmc_clv_model_amd.sampler import HipSampler, build_problem
     df, D, covs, chains, burnin, mcmc, thin, sink = load_workload(name, world)
@@ -459,7 +497,7 @@ def run_leg(name: str, world: int, rank: int, local_rank: int, dist, steps: int,
         keeps no record).  Returns (clock, source, probe); at world size > 1 the clock is the ranks'
         min and max.  Boxes of one pool run the same kernels at clocks ~13% apart."""
         rec = kern.clock_ghz()
-        probe = kern.clock_probe(50.0)
+        probe = kern.clock_probe(50.0) if (probe_clock or rec <= 0) else 0.0
         v = rec if rec > 0 else probe
         src = "clv_clock_ghz (in-kernel record)" if rec > 0 else ("clv_clock_probe (50 us probe kernel behind "
                                                                   "the timed launches)" if v > 0 else None)
@@ -474,6 +512,8 @@ def run_leg(name: str, world: int, rank: int, local_rank: int, dist, steps: int,
         """Roofline of n_t sweeps starting at sweep `first` (persistent: kt of the timed launch);
         traffic and counters from the committed profile of phase `ph` (profile_name)."""
         if kt is None:  # launch-per-sweep: event-timed pass over further sweeps of the same chains
+            if not roofline_pass:
+                return None
             kern.set_timing(True)
             run(n_t)
             sync()
@@ -514,12 +554,14 @@ def run_leg(name: str, world: int, rank: int, local_rank: int, dist, steps: int,
     sync()
     dt, kt = timed(steps, persistent)
     clk, clk_src, clk_probe = run_clock()  # the timed launches' shader clock (outside the timed region)
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, kern.s if sharded else kern)
     host_us = kern.host_times() if (host_split and persistent and not sharded) else None
     value = chains * n_total * steps / dt
     roof = launch_roofline(warmup + 1, steps if persistent else min(steps, timing_steps), kt,
                            "the timed region's launch" if persistent else
                            f"a pass of {min(steps, timing_steps)} further sweeps, one event pair per launch", ph=phase)
-    done = warmup + steps + (0 if persistent else min(steps, timing_steps))
+    done = warmup + steps + (0 if persistent or not roofline_pass else min(steps, timing_steps))
     res = dict(workload=f"{name}: {'bivariate' if D == 2 else 'trivariate'}, K={K}, " +
                         ("synthetic (mcmc_clv_model_amd.data.synthetic_cbs)" if WORKLOADS[name][1].startswith("synthetic:")
                          else f"CDNOW {WORKLOADS[name][1]} CBS"),
@@ -622,8 +664,19 @@ def main():
     ap.add_argument("--warmup", type=int, default=1000)
     ap.add_argument("--workload", default=None, choices=sorted(WORKLOADS),
                     help="primary workload (default: c2 at N = 1, c5 at N > 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline figure: the `configs` legs, the stored-sweep "
+                         "sub-lines, `cold`, `host_us`, the probe kernel's clock, the launch-per-sweep roofline pass, "
+                         "the drop-in's whole runs and the CPU baselines (the --no-* options and --scaling-* then "
+                         "choose among them; a plain run does none of it)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write the chains' state they left (HipSampler.get_state: lambda, mu, "
+                         "beta, sigma) as DIR/<name>.npy, float64 (at most 64 MB: a fixed seeded sample of the "
+                         "customers of a larger state)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--timing-steps", type=int, default=3000, help="sweeps in the event-timed roofline pass")
+    ap.add_argument("--timing-steps", type=int, default=None,
+                    help="sweeps in the event-timed roofline pass of launch-per-sweep paths (default 3000; the pass "
+                         "runs under --full, or where this option is given)")
     ap.add_argument("--graph-chunk", type=int, default=32,
                     help="sharded RCCL path: sweeps (incl. the all-gather) per captured torch.cuda graph; 0 = eager")
     ap.add_argument("--force-sharded", action="store_true",
@@ -662,6 +715,9 @@ def main():
     a = ap.parse_args()
     global SETTLE_WORK
     SETTLE_WORK = a.settle_work
+    roofline_pass = a.full or a.timing_steps is not None
+    if a.timing_steps is None:
+        a.timing_steps = 3000
     if a.cpu_baseline_child:
         cpu_baseline_child(a.workload or "c2", a.cpu_warm, a.cpu_timed)
         return
@@ -695,16 +751,19 @@ def main():
     name = a.workload or primary_workload(world)
     exch = a.exchange if world > 1 else "rccl"
     prim = run_leg(name, world, rank, local_rank, dist, a.steps, a.warmup, graph_chunk=a.graph_chunk, exchange=exch,
-                   settle_ms=a.clock_settle_ms, stored_phase=a.stored_phase, timing_steps=a.timing_steps,
+                   settle_ms=a.clock_settle_ms, stored_phase=a.full and a.stored_phase, timing_steps=a.timing_steps,
                    force_sharded=a.force_sharded, phase=a.phase, blocks_per_unit=a.blocks_per_unit,
-                   one_call_warmup=True, cold=True, host_split=True)
+                   one_call_warmup=True, cold=a.full, host_split=a.full, roofline_pass=roofline_pass,
+                   probe_clock=a.full, dump_dir=a.dump_outputs)
     D, data, covs, chains, burnin, mcmc, thin, sink = WORKLOADS[name]
     if a.phase == "stored":
         mcmc, burnin = mcmc + burnin, 0
-    if world == 1 and not a.force_sharded and a.whole_run and name in ("c2", "c3") and a.phase == "burnin":
+    if a.full and world == 1 and not a.force_sharded and a.whole_run and name in ("c2", "c3") and a.phase == "burnin":
         prim["whole_run"] = whole_run_e2e(name)
 
     legs = config_legs(world, name) if a.scaling_configs is None else [c for c in a.scaling_configs.split(",") if c]
+    if not a.full:
+        legs = []
     extra = {}
     for leg in legs:
         if leg == name:
@@ -723,7 +782,7 @@ def main():
                                   "(a rehearsal of the CDNOW-size exchange at N GPUs)")
         if world == 1 and a.whole_run and leg == "c3":
             extra[leg]["whole_run"] = whole_run_e2e("c3")
-    if world == 1 and not a.force_sharded and a.c1_leg and "c1" not in (name,) and a.scaling_configs is None:
+    if a.full and world == 1 and not a.force_sharded and a.c1_leg and "c1" not in (name,) and a.scaling_configs is None:
         # BASELINE configs[0] ("Bivariate M1, Abe 1/10 CDNOW subset, 4000 iters on CPU numpy reference
         # path"): the same 4-chain c1 sampler on the GPU (2,000 sweeps after 80), next to its 1-core
         # CPU leg in cpu_baseline["c1"]
@@ -732,7 +791,7 @@ def main():
 
     if rank == 0:
         cpu = None
-        if world == 1 and not a.no_cpu_baseline and not a.force_sharded:
+        if a.full and world == 1 and not a.no_cpu_baseline and not a.force_sharded:
             cpu = cpu_baseline(name)
             for leg in ("c1", "c3"):
                 if leg in extra and leg != name:
@@ -749,11 +808,12 @@ def main():
         line = dict(
             metric="MCMC sweeps/sec x N_customers (customer-sweeps/s)", value=prim["value"], unit="customer-sweeps/s",
             n_gpus=world, steps=a.steps, warmup=a.warmup, ms_per_step=prim["ms_per_step"], higher_is_better=True,
+            full=a.full,
             scaling="weak", vs_baseline=None, dtype="f64",
             proposal_dtype="f32",  # t3 proposal noise and accept log-uniforms; state, posterior f64
             ms_per_step_kind=("steady state: the GPU's clocks settled by clock_settle_ms of sweeps on a scratch sampler "
                               "(clock_settle_work; the timed chains untouched) before the warm-up; the timed call leaves its last level-2 draw pending (drawn at the start of the "
-                              "next call) — `cold` times the same steps from an idle GPU with that draw included")
+                              "next call) — `cold` (--full) times the same steps from an idle GPU with that draw included")
             if prim.get("_persistent") and not sharded else "wall time of the timed steps",
             data=(f"synthetic CBS ({n_total} customers, mcmc_clv_model_amd.data.synthetic_cbs" +
                   (f", {n_total // world:,} per GPU)" if world > 1 else ")")

@@ -702,3 +702,99 @@ def test_bench_primary_is_a_baseline_configuration():
         bench.survey_bytes(3, 3, 0.1, "full") == pytest.approx(96.0)
     assert bench.survey_bytes(2, 5, 1.0, "summary") == 84.0 and bench.survey_bytes(3, 9, 1.0, "summary") == 140.0
     assert bench.survey_bytes(2, 1, 1.0, "full") == 84.0
+
+
+def test_bench_plain_run_times_only_the_primary_and_dumps_its_state(monkeypatch, tmp_path, capsys):
+    """A plain bench.py run (no --full) builds the primary workload's sampler (and the clock settle's
+    scratch one), runs the warm-up calls and exactly --steps timed sweeps, nothing else — no configs
+    legs, stored phase, cold window, probe kernel, whole run or CPU leg — and --dump-outputs writes
+    get_state()'s arrays after the timed sweeps as float64 .npy files; a state above the size limit
+    is written as a fixed seeded sample of the customers.  Stub sampler, no GPU."""
+    import json
+    import sys
+
+    import torch
+
+    import bench
+    from mcmc_clv_model_amd import _lib
+    from mcmc_clv_model_amd import sampler as S
+
+    made = []
+    rng = np.random.default_rng(5)
+
+    class Fake:
+        n = 300
+
+        def __init__(self, p, **kw):
+            self.kw, self.log, self.probes = kw, [], 0
+            made.append(self)
+
+        def run(self, n):
+            self.log.append(n)
+
+        def synchronize(self):
+            pass
+
+        def launch_info(self):
+            return dict(persistent=True)
+
+        def set_timing(self, on):
+            pass
+
+        def kernel_time(self):
+            return dict(sweep_ms=0.2, sweep_launches=20, hyper_ms=0.0, hyper_launches=0)
+
+        def clock_ghz(self):
+            return 2.38
+
+        def clock_probe(self, us):
+            self.probes += 1
+            return 2.4
+
+        def get_state(self):
+            C = self.kw["chains"]
+            if not hasattr(self, "state"):
+                self.state_after = list(self.log)
+                self.state = tuple(rng.random(s) for s in ((C, self.n), (C, self.n), (C, 2, 2), (C, 2, 2)))
+            return self.state
+
+        def close(self):
+            pass
+
+    monkeypatch.setattr(S, "HipSampler", Fake)
+    monkeypatch.setattr(S, "build_problem", lambda df, covs, D: None)
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda *a, **k: None)
+    monkeypatch.setattr(_lib, "lib", lambda: None)
+    monkeypatch.setattr(bench, "cpu_baseline", lambda *a, **k: pytest.fail("a plain run has no CPU leg"))
+    monkeypatch.setattr(bench, "whole_run_e2e", lambda *a, **k: pytest.fail("a plain run has no whole run"))
+    out = tmp_path / "dump"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--clock-settle-ms", "1",
+                                      "--dump-outputs", str(out)])
+    bench.main()
+    lines = capsys.readouterr().out.strip().splitlines()
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    timed, scratch = made  # the primary (c2) and its clock-settle sampler: no other leg was built
+    assert timed.kw["seed"] == 42 and timed.log == [1] * 5 + [20] and timed.probes == 0
+    assert timed.state_after == [1] * 5 + [20]  # the state was read right after the timed sweeps
+    assert line["steps"] == 20 and line["warmup"] == 5 and line["full"] is False
+    assert line["metric"].startswith("MCMC sweeps/sec") and line["unit"] == "customer-sweeps/s" and line["dtype"] == "f64"
+    assert line["higher_is_better"] is True and line["ms_per_step"] > 0
+    assert line["value"] == pytest.approx(4 * 23570 * 1e3 / line["ms_per_step"])
+    assert line["roofline"]["events"] == "the timed region's launch"  # (the timed launch's own events)
+    for k in ("configs", "cpu_baseline", "cold", "stored", "whole_run", "host_us", "gpu_clock_probe_ghz"):
+        assert line[k] is None, k
+    for name, want in zip(("lambda", "mu", "beta", "sigma"), timed.state):
+        got = np.load(out / f"{name}.npy")
+        assert got.dtype == np.float64 and np.array_equal(got, want)
+    assert sorted(os.listdir(out)) == ["beta.npy", "lambda.npy", "mu.npy", "sigma.npy"]
+    # above the limit: the same seeded customers of lambda and mu, every time
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 2 * 4 * (2 * 2 * 8) + 100 * 8 * (2 * 4 + 1))
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), timed)
+    idx = np.load(tmp_path / "s1" / "customers.npy").astype(int)
+    assert len(idx) == 100 and np.all(np.diff(idx) > 0) and idx.max() < 300
+    assert np.array_equal(idx, np.load(tmp_path / "s2" / "customers.npy"))
+    assert np.array_equal(np.load(tmp_path / "s1" / "lambda.npy"), timed.state[0][:, idx])
+    assert np.array_equal(np.load(tmp_path / "s1" / "mu.npy"), timed.state[1][:, idx])
+    assert sum(os.path.getsize(tmp_path / "s1" / f) for f in os.listdir(tmp_path / "s1")) <= 4 * 64 + 100 * 72 + 5 * 128

@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}; cd $R; mkdir -p gpurun_out
 for rep in $(seq ${REPS:-2}); do
   for E in "$@"; do
     for W in ${WL:-c2}; do
-      env $E timeout -k 10 120 python bench.py --workload $W --steps ${STEPS:-5000} --warmup 200 --no-cpu-baseline \
+      env $E timeout -k 10 120 python bench.py --full --workload $W --steps ${STEPS:-5000} --warmup 200 --no-cpu-baseline \
         --scaling-configs= --no-c1-leg --no-stored-phase --no-whole-run > gpurun_out/ab.log 2>&1 || { tail -5 gpurun_out/ab.log; exit 1; }
       python - "$W" "$E" <<'PY'
 import json, sys

@@ -17,7 +17,7 @@ for W in "$@"; do
     c4_shard8) TR="--steps 9000 --warmup 5"; PS=10000 ;;  # (persistent since round 6: its 10,000-sweep run)
     *)        TR="--steps 2000 --warmup 200 --timing-steps 500"; PS=100 ;;
   esac
-  B="python3 $R/bench.py --workload $WL --phase $PH --no-cpu-baseline --scaling-configs= --no-c1-leg --no-stored-phase --no-whole-run"
+  B="python3 $R/bench.py --full --workload $WL --phase $PH --no-cpu-baseline --scaling-configs= --no-c1-leg --no-stored-phase --no-whole-run"
   timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $D/trace -o run --output-format csv -- $B $TR > $D/prof_trace.log 2>&1; rc=$?
   echo ${W}_trace_rc=$rc; tail -1 $D/prof_trace.log | cut -c1-200
   [ $rc -eq 0 ] || exit $rc

@@ -27,7 +27,10 @@ for step in "$@"; do
       echo driver_rc=$rc; tail -c 600 gpurun_out/bench_driver.log
       [ $rc -eq 0 ] || exit $rc ;;
     default)
+      # (the CPU legs and configs of the default line are behind bench.py --full)
+      PLAIN_ARGS=${BENCH_ARGS}; BENCH_ARGS="--full ${BENCH_ARGS}"
       timeout -k 10 900 python bench.py ${BENCH_ARGS} > gpurun_out/bench_default.log 2>&1; rc=$?
+      BENCH_ARGS=${PLAIN_ARGS}
       echo default_rc=$rc; tail -c 600 gpurun_out/bench_default.log
       [ $rc -eq 0 ] || exit $rc ;;
     e2e)
@@ -36,7 +39,7 @@ for step in "$@"; do
       [ $rc -eq 0 ] || exit $rc ;;
     rehearse)
       timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-        --master-port 29517 bench.py --gpus 2 --steps ${STEPS:-20} --warmup 5 --one-gpu-rehearsal ${BENCH_ARGS} \
+        --master-port 29517 bench.py --full --gpus 2 --steps ${STEPS:-20} --warmup 5 --one-gpu-rehearsal ${BENCH_ARGS} \
         > gpurun_out/rehearse_n2.log 2>&1; rc=$?
       echo rehearse_rc=$rc; grep -v Warning gpurun_out/rehearse_n2.log | tail -c 2500
       [ $rc -eq 0 ] || exit $rc ;;
