@@ -386,6 +386,39 @@ int clv_chain_total_loglik(int32_t device, const double* level1, int64_t n_draws
                            const int32_t* x, const double* T_cal, double* mean_total);
 int clv_chain_total_loglik_sampler(clv_sampler* s, double* mean_total);
 
+/* ---- Convergence diagnostics on device (csrc/diag.hip) ----
+ * The reference checks convergence with ArviZ on its level-2 draws (bivariate/analysis_abe.py:
+ * 651-706: az.summary, az.plot_autocorr).  Here a series is m chains x n draws (n >= 8) of one
+ * quantity, optionally logged first, and its statistics are six doubles: mean and sd (ddof 1) over
+ * all m n values; the split-chain R-hat and the mean effective sample size of BDA3 / Stan / ArviZ
+ * WITHOUT rank normalisation (each chain split into its first and last n / 2 draws, biased
+ * autocovariances averaged over the 2 m split chains, Geyer's initial positive sequence truncated
+ * at lag T and made monotone, tau floored at 1 / log10(2 m (n / 2))); mcse = sd / sqrt(ess); and
+ * the truncation lag T (-1 when no pair was accepted).  All six are NaN for a series with a
+ * non-finite value (after the log) or zero within-chain variance — a customer whose z never
+ * changes.  az.summary reports the rank-normalised variants (bulk / tail ESS, rank R-hat): those,
+ * and R-hat of quantiles, are out of scope; this estimator is meant for the scales the sampler
+ * works on — log lambda, log mu and the level-2 parameters.
+ *   series: [chain][draw][n_series] — level-2 draws [chain][draw][P] as they are, level-1 draws
+ *           [chain][draw][n][D+2] with n_series = n (D+2);  out: [n_series][CLV_N_DIAG_STATS].
+ *   Series s is logged when bit s % period of log_mask is set (period 1..32; level 1: D+2).
+ * clv_diagnostics_sampler works on the draws a sampler holds in HBM after its run, without a host
+ * copy: level1_out [n (D+2)][6] (CLV_SINK_FULL only, log_mask over the D+2 columns; CLV_ESTATE as
+ * the other *_sampler entry points), level2_out [D K + D(D+1)/2][6] (never logged); either may be
+ * NULL.  Same kernels and summation order as clv_diagnostics: the same bits.
+ * clv_autocorr: acf_c(t) = A_c(t) / A_c(0) of every unsplit chain, A_c(t) = (1/n) sum_i c[i] c[i+t]
+ * centred at the chain mean, t = 0..max_lag (< n_draws); out [chain][n_series][max_lag + 1].
+ * CLV_EINVAL before any device call: null pointer, n_chains < 1, n_draws < 8, n_series < 1,
+ * period outside 1..32, max_lag outside 0..n_draws-1. */
+enum {
+  CLV_DIAG_MEAN = 0, CLV_DIAG_SD, CLV_DIAG_MCSE, CLV_DIAG_ESS, CLV_DIAG_RHAT, CLV_DIAG_LAG, CLV_N_DIAG_STATS
+};
+int clv_diagnostics(int32_t device, const double* series, int32_t n_chains, int64_t n_draws, int64_t n_series,
+                    int32_t period, uint32_t log_mask, double* out);
+int clv_diagnostics_sampler(clv_sampler* s, uint32_t log_mask, double* level1_out, double* level2_out);
+int clv_autocorr(int32_t device, const double* series, int32_t n_chains, int64_t n_draws, int64_t n_series,
+                 int32_t max_lag, double* out);
+
 /* ---- Data preparation on device ----
  * Event log -> CBS (utils/elog2cbs2param.py:33-94): events (cust, date in ns since the epoch,
  * sales or NULL = 1) -> one row per customer with calibration events, sorted by cust.  Output

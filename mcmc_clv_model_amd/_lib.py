@@ -143,6 +143,9 @@ def lib() -> ctypes.CDLL:
         "clv_level1_summary_sampler": (c_int32, [sp, c_double, dp]),
         "clv_chain_total_loglik": (c_int32, [c_int32, dp, c_int64, c_int64, c_int32, POINTER(c_int32), dp, dp]),
         "clv_chain_total_loglik_sampler": (c_int32, [sp, dp]),
+        "clv_diagnostics": (c_int32, [c_int32, dp, c_int32, c_int64, c_int64, c_int32, c_uint32, dp]),
+        "clv_diagnostics_sampler": (c_int32, [sp, c_uint32, dp, dp]),
+        "clv_autocorr": (c_int32, [c_int32, dp, c_int32, c_int64, c_int64, c_int32, dp]),
         "clv_elog2cbs": (c_int32, [c_int32, c_int64, POINTER(c_int64), POINTER(c_int64), dp, c_int64, c_int64, c_int64,
                                    POINTER(c_int64), POINTER(c_int64), POINTER(c_int64), dp, dp, dp, dp,
                                    POINTER(c_int64), dp, dp, POINTER(c_int64), dp]),
@@ -166,6 +169,9 @@ def lib() -> ctypes.CDLL:
 # Columns of clv_level1_summary() (include/clvmcmc.h CLV_L1_*).
 L1_STATS = ("mean_lambda", "lambda_p025", "lambda_p975", "mean_mu", "mean_mu_capped", "mu_p025", "mu_p975",
             "mean_z", "mean_tau", "mean_eta")
+
+# Columns of clv_diagnostics() (include/clvmcmc.h CLV_DIAG_*).
+DIAG_STATS = ("mean", "sd", "mcse", "ess", "rhat", "lag")
 
 
 def exported_symbols():

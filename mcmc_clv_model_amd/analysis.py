@@ -10,6 +10,12 @@ Reference functions mirrored (same names, arguments, defaults and return layout)
 * ``posterior_weekly_tracking`` — the posterior-predictive weekly repeat-transaction curve of
   ``src/models/bivariate/analysis_abe.py:444-464`` (inline script code in the reference).
 
+* ``summarize_level2``, ``extract_correlation`` — ``analysis_bi_helpers.py:6-13, 39-48`` (host only).
+* ``level2_diagnostics``, ``level2_autocorr`` — what ``bivariate/analysis_abe.py:651-706`` asks of
+  ArviZ (``az.summary``, ``az.plot_autocorr``) on the level-2 draws, and ``level1_diagnostics``, the
+  same convergence check for every customer's parameters (``csrc/diag.hip``: split R-hat and mean
+  ESS without rank normalisation, see :func:`level1_diagnostics`).
+
 The per-customer / per-draw work runs in ``csrc/analysis.hip`` through the C ABI (``clv_predict``,
 ``clv_track``, ``clv_level1_summary``, ``clv_chain_total_loglik``); the host only reshapes and
 formats (pandas).  Random draws come from Philox streams keyed by ``seed`` (the reference uses
@@ -29,7 +35,9 @@ from ._lib import check, dptr
 from .sampler import resolve_seed
 
 __all__ = ["draw_future_transactions", "draw_future_transactions_rfm_m", "post_mean_lambdas", "post_mean_mus",
-           "chain_total_loglik", "compute_table4", "level1_summary", "posterior_weekly_tracking"]
+           "chain_total_loglik", "compute_table4", "level1_summary", "posterior_weekly_tracking",
+           "level1_diagnostics", "level2_diagnostics", "level2_autocorr", "summarize_level2", "extract_correlation",
+           "summary_rhat"]
 
 
 def _stacked_level1(level1_chains) -> np.ndarray:
@@ -190,3 +198,153 @@ def posterior_weekly_tracking(draws, birth_week, times, seed: Optional[int] = 0,
     out = np.empty(t.shape[0], np.float64)
     check(L.clv_track(int(device), dptr(a), nd, n, w, dptr(b), dptr(t), t.shape[0], resolve_seed(seed), dptr(out)))
     return out
+
+
+# ---- convergence diagnostics (csrc/diag.hip) -------------------------------------------------
+LEVEL1_PARAMS = ("lambda", "mu", "tau", "z", "eta")
+
+
+def level1_log_mask(log_columns, width: int) -> int:
+    """Bit i set = level-1 column i (lambda, mu, tau, z[, eta]) is logged before the statistics."""
+    names = LEVEL1_PARAMS[:width]
+    mask = 0
+    for c in log_columns or ():
+        if c not in names:
+            raise ValueError(f"log_columns entries must be among {names} (got {c!r})")
+        mask |= 1 << names.index(c)
+    return mask
+
+
+def level1_diagnostics_frame(stats: np.ndarray, n: int, width: int, log_mask: int) -> pd.DataFrame:
+    """[n * width][6] statistics -> one row per customer, columns f"{stat}_{param}"."""
+    a = np.asarray(stats).reshape(n, width, len(_lib.DIAG_STATS))
+    cols = {}
+    for j, nm in enumerate(LEVEL1_PARAMS[:width]):
+        pname = f"log_{nm}" if (log_mask >> j) & 1 else nm
+        for k, st in enumerate(_lib.DIAG_STATS):
+            cols[f"{st}_{pname}"] = a[:, j, k]
+    return pd.DataFrame(cols)
+
+
+def level2_diagnostics_frame(stats: np.ndarray, param_names=None) -> pd.DataFrame:
+    a = np.asarray(stats)
+    names = list(param_names) if param_names is not None else [f"level_2[{i}]" for i in range(a.shape[0])]
+    if len(names) != a.shape[0]:
+        raise ValueError(f"param_names has {len(names)} entries for {a.shape[0]} level-2 parameters")
+    return pd.DataFrame(a, columns=list(_lib.DIAG_STATS), index=names)
+
+
+def _chains_array(chains_list) -> np.ndarray:
+    """A draws list (one array per chain, equal shapes) as one C-contiguous [chain][draw][...] array."""
+    if chains_list is None:
+        raise ValueError("level-1 draws are needed (run the sampler with draw_sink='full')")
+    return np.ascontiguousarray(np.stack([np.asarray(c, dtype=np.float64) for c in chains_list], axis=0))
+
+
+def _diagnostics(a: np.ndarray, n_series: int, period: int, log_mask: int, device: int) -> np.ndarray:
+    L = _L()
+    out = np.empty((n_series, len(_lib.DIAG_STATS)), np.float64)
+    check(L.clv_diagnostics(int(device), dptr(a), a.shape[0], a.shape[1], n_series, period, log_mask, dptr(out)))
+    return out
+
+
+def level1_diagnostics(draws: Dict[str, Any], *, log_columns=("lambda", "mu"), device: int = -1) -> pd.DataFrame:
+    """Per-customer convergence diagnostics of the level-1 draws, on the GPU (``csrc/diag.hip``).
+
+    One row per customer; columns ``f"{stat}_{param}"`` with stat in mean, sd, mcse, ess, rhat, lag
+    and param in log_lambda, log_mu, tau, z (and eta for the trivariate model) — a column that is
+    not in ``log_columns`` keeps its plain name (``lambda``, ``mu``).
+
+    The estimator is the split-chain R-hat and the mean effective sample size of BDA3 / Stan /
+    ArviZ WITHOUT rank normalisation: every chain is split in halves, the biased autocovariances of
+    the split chains are averaged, Geyer's initial positive sequence is cut at ``lag`` and made
+    monotone, ``ess = M h / tau``, ``mcse = sd / sqrt(ess)``.  ``az.summary`` reports the
+    rank-normalised variants; rank-normalised bulk ESS, tail ESS and R-hat of quantiles are out of
+    scope.  The estimator is meant for the scales the sampler works on — log lambda, log mu and the
+    level-2 parameters — hence the default ``log_columns``.  A series with a non-finite value or no
+    within-chain variance (a customer whose ``z`` never changes) gives NaN in all six statistics.
+    Needs at least 8 draws per chain."""
+    a = _chains_array(draws.get("level_1"))
+    if a.ndim != 4 or a.shape[3] not in (4, 5):
+        raise ValueError("level_1 draws must be (n_draws, n_customers, 4 or 5) per chain")
+    n, w = a.shape[2], a.shape[3]
+    mask = level1_log_mask(log_columns, w)
+    return level1_diagnostics_frame(_diagnostics(a, n * w, w, mask, device), n, w, mask)
+
+
+def level2_diagnostics(draws: Dict[str, Any], param_names=None, *, device: int = -1) -> pd.DataFrame:
+    """The project's ``az.summary`` of the level-2 draws (bivariate/analysis_abe.py:651-706): one row
+    per level-2 parameter with mean, sd, mcse, ess, rhat and the truncation lag — the estimator of
+    :func:`level1_diagnostics` (not rank-normalised, unlike az.summary's ess_bulk / ess_tail /
+    r_hat), on the parameters as drawn."""
+    a = _chains_array(draws["level_2"])
+    if a.ndim != 3:
+        raise ValueError("level_2 draws must be (n_draws, n_params) per chain")
+    return level2_diagnostics_frame(_diagnostics(a, a.shape[2], 1, 0, device), param_names)
+
+
+def level2_autocorr(draws: Dict[str, Any], max_lag: int = 100, *, device: int = -1) -> np.ndarray:
+    """Per-chain autocorrelation of every level-2 parameter (what ``az.plot_autocorr`` draws,
+    analysis_abe.py:693-703): ``[chain][param][max_lag + 1]``, A_c(t) / A_c(0) of the unsplit chain
+    centred at its mean with divisor n.  ``max_lag`` must be below the number of draws."""
+    L = _L()
+    a = _chains_array(draws["level_2"])
+    if a.ndim != 3:
+        raise ValueError("level_2 draws must be (n_draws, n_params) per chain")
+    out = np.empty((a.shape[0], a.shape[2], max(int(max_lag), 0) + 1), np.float64)
+    check(L.clv_autocorr(int(device), dptr(a), a.shape[0], a.shape[1], a.shape[2], int(max_lag), dptr(out)))
+    return out
+
+
+def summarize_level2(draws_level2: np.ndarray, param_names, decimals: int = 2) -> pd.DataFrame:
+    """analysis_bi_helpers.py:6-13 — 2.5 / 50 / 97.5 % quantiles of each level-2 parameter over the
+    (stacked) draws, rounded.  Host numpy, as the reference."""
+    quantiles = np.percentile(draws_level2, [2.5, 50, 97.5], axis=0)
+    summary = pd.DataFrame(quantiles.T, columns=["2.5%", "50%", "97.5%"], index=param_names)
+    return summary.round(decimals)
+
+
+def extract_correlation(draws_level2: np.ndarray) -> np.ndarray:
+    """analysis_bi_helpers.py:39-48 — 2.5 / 50 / 97.5 % quantiles of corr(log lambda, log mu) from the
+    level-2 covariance draws (last three columns: var, cov, var), rounded to 2 decimals."""
+    cov = draws_level2[:, -2]
+    var_lambda = draws_level2[:, -3]
+    var_mu = draws_level2[:, -1]
+    corr = cov / np.sqrt(var_lambda * var_mu)
+    return np.percentile(corr, [2.5, 50, 97.5]).round(2)
+
+
+def summary_rhat(draws: Dict[str, Any]) -> pd.DataFrame:
+    """Non-split R-hat of lambda and mu per customer for a ``draw_sink="summary"`` / ``"summary+pct"``
+    result, where no draws exist and this is the only diagnostic available (host numpy).
+
+    From the per-chain means of ``lambda``, ``lambda2``, ``mu``, ``mu2`` in ``draws["summary"]`` over
+    n stored draws: within-chain variance s_c^2 = (E[x^2] - E[x]^2) n / (n - 1), W = mean_c s_c^2,
+    B / n = var_c(E[x], ddof=1), R-hat = sqrt(((n - 1) / n W + B / n) / W).  NaN where the variance
+    is not positive; needs at least 2 chains and 2 stored draws.
+
+    ``E[x^2] - E[x]^2`` cancels: its absolute error is about 2^-52 E[x^2], so a chain whose
+    coefficient of variation is below ~1e-7 loses every digit of its variance (and may come out
+    zero or negative: NaN here).  The sampler's lambda and mu vary by tens of percent per customer,
+    which leaves about 13 digits.  No split, no ESS: use ``draw_sink="full"`` and
+    :func:`level1_diagnostics` for those."""
+    sm = draws.get("summary")
+    if not isinstance(sm, dict) or "lambda2" not in sm:
+        raise ValueError("summary_rhat needs a draw_sink='summary' (or 'summary+pct') result")
+    n = int(sm["n_draws"])
+    out = {}
+    for nm in ("lambda", "mu"):
+        m1 = np.asarray(sm[nm], dtype=np.float64)
+        m2 = np.asarray(sm[nm + "2"], dtype=np.float64)
+        if m1.ndim != 2 or m1.shape[0] < 2:
+            raise ValueError("summary_rhat needs at least 2 chains")
+        if n < 2:
+            raise ValueError("summary_rhat needs at least 2 stored draws")
+        s2 = (m2 - m1 * m1) * (n / (n - 1.0))
+        W = s2.mean(axis=0)
+        B_n = m1.var(axis=0, ddof=1)
+        ok = (s2 > 0).all(axis=0)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            r = np.sqrt(((n - 1.0) / n * W + B_n) / W)
+        out[f"rhat_{nm}"] = np.where(ok, r, np.nan)
+    return pd.DataFrame(out)

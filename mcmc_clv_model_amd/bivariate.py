@@ -16,6 +16,10 @@ line and return layout (bivariate/mcmc.py:437-504); the sweeps run on the GPU
   split into shards exchanging the level-2 statistics each sweep by peer stores or device copies,
   ``exchange`` = "auto" | "p2p" | "copy"; ``"auto"``: chains when they divide evenly), with the
   single-device run's output bit for bit (sampler.fit_multi, csrc/group.hip).
+* ``diagnostics``: True adds ``out["diagnostics"] = {"level_1": DataFrame per customer, "level_2":
+  DataFrame per level-2 parameter}`` — split R-hat, ESS, MCSE and truncation lag computed on the GPU
+  from the draws still in HBM (``analysis.level1_diagnostics`` / ``level2_diagnostics``;
+  ``draw_sink="full"`` only, at least 8 stored draws).  False changes nothing.
 """
 from __future__ import annotations
 
@@ -32,7 +36,7 @@ def mcmc_draw_parameters(cal_cbs, covariates: Optional[Sequence[str]] = None, mc
                          trace: int = 100, n_mh_steps: int = 20, *, draw_sink: str = "full",
                          rng: str = "philox", device: int = -1, replay_tape=None,
                          replay_sweeps: Optional[int] = None, devices: Optional[Sequence[int]] = None,
-                         shard: str = "auto", exchange: str = "auto"):
+                         shard: str = "auto", exchange: str = "auto", diagnostics: bool = False):
     """Run the Abe (2009) Gibbs/MH sampler on calibration CBS (bivariate/mcmc.py:437).
 
     Returns dict(level_1=[(n_draws, N, 4) per chain: lambda, mu, tau, z],
@@ -50,4 +54,4 @@ def mcmc_draw_parameters(cal_cbs, covariates: Optional[Sequence[str]] = None, mc
     return fit(p, mcmc=mcmc, burnin=burnin, thin=thin, chains=chains, seed=seed, trace=trace,
                n_mh_steps=n_mh_steps, draw_sink=draw_sink, rng=rng, device=device,
                replay_tape=replay_tape, replay_sweeps=replay_sweeps, devices=devices, shard=shard,
-               exchange=exchange)
+               exchange=exchange, diagnostics=diagnostics)

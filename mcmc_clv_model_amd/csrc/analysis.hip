@@ -484,6 +484,10 @@ int loglik_dev(const double* l1, int64_t n_draws, int64_t n, int32_t width, cons
   return CLV_OK;
 }
 
+}  // namespace
+
+namespace clv {
+
 int sampler_l1(clv_sampler* s, const double** l1, int64_t* n_draws, int32_t* width) {
   if (!s) return fail(CLV_EINVAL, "null sampler");
   if (!s->d_level1) return fail(CLV_ESTATE, "level-1 draws are on the device only with draw_sink == CLV_SINK_FULL");
@@ -499,7 +503,7 @@ int sampler_l1(clv_sampler* s, const double** l1, int64_t* n_draws, int32_t* wid
   return check_l1(*n_draws, s->g.n, *width);
 }
 
-}  // namespace
+}  // namespace clv
 
 extern "C" {
 

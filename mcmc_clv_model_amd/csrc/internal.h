@@ -39,6 +39,10 @@ void stream_copy(DrawStreamState* st, int device, const void* src, void* dst, si
 bool stream_wait(DrawStreamState* st);  // every piece done; false if one failed since the last clear
 void stream_clear_failed(DrawStreamState* st);  // after a full copy has repaired the destination
 
+// The level-1 draws a CLV_SINK_FULL sampler holds in HBM after its run (analysis.hip): *l1 =
+// [chain * draw][n][width], *n_draws = chains x stored draws; CLV_ESTATE without them.
+int sampler_l1(clv_sampler* s, const double** l1, int64_t* n_draws, int32_t* width);
+
 template <class T>
 hipError_t dalloc(T** p, size_t count) {
   *p = nullptr;

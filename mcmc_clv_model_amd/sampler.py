@@ -402,6 +402,25 @@ class HipSampler:
         check(self._L.clv_level1_summary_sampler(self.h, float(mu_cap), dptr(out)))
         return out
 
+    def diagnostics(self, log_columns=("lambda", "mu"), level1: bool = True, level2: bool = True,
+                    param_names=None) -> dict:
+        """clv_diagnostics_sampler: convergence diagnostics (split R-hat, ESS, MCSE, truncation lag;
+        analysis.level1_diagnostics / level2_diagnostics) of the draws this sampler holds in HBM,
+        without the host round trip — {"level_1": DataFrame per customer (full sink only),
+        "level_2": DataFrame per level-2 parameter}, the same bits as the host-array route."""
+        from . import analysis as A
+        w = self.D + 2
+        mask = A.level1_log_mask(log_columns, w)
+        o1 = np.empty((self.n * w, len(_lib.DIAG_STATS)), np.float64) if level1 else None
+        o2 = np.empty((self.D * self.K + self.D * (self.D + 1) // 2, len(_lib.DIAG_STATS)), np.float64) if level2 else None
+        check(self._L.clv_diagnostics_sampler(self.h, mask, dptr(o1), dptr(o2)))
+        out = {}
+        if level1:
+            out["level_1"] = A.level1_diagnostics_frame(o1, self.n, w, mask)
+        if level2:
+            out["level_2"] = A.level2_diagnostics_frame(o2, param_names)
+        return out
+
     def chain_total_loglik(self) -> float:
         out = ctypes.c_double()
         check(self._L.clv_chain_total_loglik_sampler(self.h, ctypes.byref(out)))
@@ -515,14 +534,19 @@ def _assemble(D: int, chains: int, l1, l2, ll, sums, k: int, n_draws: int, draw_
 def fit(p: Problem, *, mcmc: int, burnin: int, thin: int, chains: int, seed, trace: int, n_mh_steps: int,
         draw_sink: str = "full", rng: str = "philox", device: int = -1, replay_tape=None,
         replay_sweeps: Optional[int] = None, devices: Optional[Sequence[int]] = None, shard: str = "auto",
-        exchange: str = "auto") -> dict:
+        exchange: str = "auto", diagnostics: bool = False) -> dict:
     """Run all chains of one problem in one batched launch sequence and return the reference's
     output layout (bi:499-504).  ``devices`` (two or more): the run is spread over those devices
-    in this process (:func:`fit_multi`)."""
+    in this process (:func:`fit_multi`).  ``diagnostics``: also out["diagnostics"] = {"level_1",
+    "level_2"} convergence tables (analysis.level1_diagnostics / level2_diagnostics; full sink
+    only), from the sampler's draws in HBM on one device, from the returned arrays on devices[0]
+    otherwise."""
     if chains < 1:
         raise ValueError("chains must be >= 1")
     if thin < 1:
         raise ValueError("thin must be >= 1")
+    if diagnostics and draw_sink != "full":
+        raise ValueError("diagnostics=True needs draw_sink='full' (analysis.summary_rhat serves a summary run)")
     if devices is not None:
         devices = [int(d) for d in devices]
         if not devices:
@@ -530,9 +554,14 @@ def fit(p: Problem, *, mcmc: int, burnin: int, thin: int, chains: int, seed, tra
         if len(devices) > 1:
             if rng != "philox":
                 raise ValueError("devices= runs need rng='philox' (the replay tape is a single-device test mode)")
-            return fit_multi(p, mcmc=mcmc, burnin=burnin, thin=thin, chains=chains, seed=seed, trace=trace,
-                             n_mh_steps=n_mh_steps, draw_sink=draw_sink, devices=devices, shard=shard,
-                             exchange=exchange)
+            out = fit_multi(p, mcmc=mcmc, burnin=burnin, thin=thin, chains=chains, seed=seed, trace=trace,
+                            n_mh_steps=n_mh_steps, draw_sink=draw_sink, devices=devices, shard=shard,
+                            exchange=exchange)
+            if diagnostics:
+                from . import analysis as A
+                out["diagnostics"] = dict(level_1=A.level1_diagnostics(out, device=devices[0]),
+                                          level_2=A.level2_diagnostics(out, device=devices[0]))
+            return out
         device = devices[0]
     s = HipSampler(p, mcmc=mcmc, burnin=burnin, thin=thin, chains=chains, seed=resolve_seed(seed),
                    n_mh_steps=n_mh_steps, draw_sink=draw_sink, rng=rng, device=device)
@@ -549,8 +578,11 @@ def fit(p: Problem, *, mcmc: int, burnin: int, thin: int, chains: int, seed, tra
         run_with_trace(s, burnin + mcmc, trace, n_chains_label=chains)
         l1, l2, ll = s.read_draws(level1=draw_sink == "full", out=l1)
         sums, k = s.read_summary() if draw_sink in ("summary", "summary+pct") else (None, 0)
-        return _assemble(p.D, chains, l1, l2, ll, sums, k, s.n_draws, draw_sink,
-                         lambda: s.level1_summary(_lib.SUMMARY_MU_CAP))
+        out = _assemble(p.D, chains, l1, l2, ll, sums, k, s.n_draws, draw_sink,
+                        lambda: s.level1_summary(_lib.SUMMARY_MU_CAP))
+        if diagnostics:
+            out["diagnostics"] = s.diagnostics()
+        return out
     finally:
         s.close()
 
