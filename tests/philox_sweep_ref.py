@@ -1,0 +1,322 @@
+"""Float64 model of ONE Philox-mode (production) sweep — TEST INFRASTRUCTURE ONLY, plain numpy.
+
+Written from the reference's equations as ``oracle/ref_cpu.py`` restates them (``p_alive``,
+``tau_churned``, ``log_posterior``, ``draw_eta``, ``level2_posterior``, ``invwishart_from_variates``,
+``lik_terms``) and from the documented Philox stream layout (``oracle/philox.py``).  It is NOT a
+transliteration of ``csrc/kernels.hip``: it divides where the kernel multiplies, evaluates the log
+posterior in the reference's direct form (no expanded quadratic), calls libm exp/log, and draws
+nothing ahead.  ``tests/test_philox_sweep_cpu.py`` pins it to the reference's recorded outputs and to
+``run_chain_bi`` / ``run_chain_tri``; ``tests/test_gpu_production_sweep.py`` holds the device to it.
+
+It follows the reference's semantics with the production path's documented deviations only:
+
+* Q3 cap: a proposal with ``lm > 5`` has log posterior ``-inf`` and NaN never accepts (the
+  reference's own behaviour, taken in the log domain: accept iff ``pm <= 5`` and
+  ``lp' - lp > ln 2 * log2 U``);
+* the proposal clipped to [-70, 70] (bi:323-324);
+* ``min(700, .)`` in tau's exponents (bi:223);
+* natural-scale ``lambda = exp(ll)`` after the MH steps, with no exp(log(.)) storage round trip
+  (quirk Q5), and level 2 sees the log-scale state itself.
+
+Every accept/reject and the alive/churned draw is a comparison of two computed numbers; the model
+returns, per customer, the smallest relative distance of any of them from its threshold (the
+"decision margin"), so a caller can set aside the lanes where two correct float64 evaluations may
+legitimately decide differently.
+"""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+
+from oracle import philox as oph
+from oracle import ref_cpu as orc
+
+LN2 = math.log(2.0)
+MU_CAP = 5.0           # quirk Q3 (bi:309)
+CLIP = 70.0            # bi:323-324
+# comparison tolerance of lambda, mu, tau, eta and the likelihood term; a lane whose decision margin
+# is below it is "borderline"
+RTOL = 1e-12
+# tau's absolute term is TAU_ATOL_ULPS * 2^-52 / (lambda + mu): see tau_atol()
+TAU_ATOL_ULPS = 8.0
+BORDERLINE_CAP = 1e-3  # at most 0.1% of compared lanes per case may be borderline
+# level-2 record: the project's replay-parity figures (S_n summed in another order); ten times the
+# sensitivity measured by test_level2_tolerance_covers_the_measured_sensitivity stays below L2_RTOL
+L2_RTOL, L2_ATOL = 1e-10, 1e-12
+
+
+def l2_deviation(got, ref):
+    """Relative deviation of a level-2 quantity after the absolute allowance: <= L2_RTOL passes."""
+    ref = np.asarray(ref, dtype=np.float64)
+    return np.maximum(np.abs(np.asarray(got) - ref) - L2_ATOL, 0.0) / np.maximum(np.abs(ref), 1e-300)
+
+
+def near_edges(mp, z, tau, frac=0.05):
+    """Churned draws whose tau lies in the first / last ``frac`` of [t_x, T_cal]: where the truncated
+    exponential's log argument is closest to its ends."""
+    span = mp.T_cal - mp.t_x
+    churned = ~np.asarray(z, dtype=bool)
+    return churned & (tau - mp.t_x < frac * span), churned & (mp.T_cal - tau < frac * span)
+
+
+def tau_atol(lam, mu):
+    """Absolute tolerance of tau.  Churned: tau = -log(arg) / ml with arg = (1-u) e^-ml tx + u e^-ml T.
+    d tau = -(d arg / arg) / ml: the condition number of log at arg -> 1 is 1 / |log arg|, so a
+    relative error of arg passes to tau as an ABSOLUTE error (d arg / arg) / ml however small tau is.
+    arg's relative error between two correct evaluations: the two exps at <= 2 ulp (table exp) + 1 ulp
+    (libm) = 3, two products and a sum rounded once each on either side = 3, the log's own rounding 2:
+    8 ulp of 2^-52, divided by ml."""
+    return TAU_ATOL_ULPS * 2.0 ** -52 / (np.asarray(lam) + np.asarray(mu))
+
+
+# ---------------------------------------------------------------------------------------------
+# level 1
+# ---------------------------------------------------------------------------------------------
+def draw_z_tau(t_x, T_cal, lam, mu, u_z, u_tau, e_alive, swap_tau_branch=False):
+    """bi:193-227 with the sweep's Philox variates: z = u_z < P(alive); tau = T + E / mu (alive, E =
+    -log U' of the SLOT_ZTAU words (z, w)) or the truncated-exponential inverse CDF at U of the same
+    words (churned).  Returns (z, tau, relative margin of the z decision).
+    ``swap_tau_branch`` (power checks only): each branch's formula on the other branch's lanes."""
+    ml = mu + lam
+    with np.errstate(under="ignore"):
+        e = np.exp(-(ml * (T_cal - t_x)))
+    a = ml * e
+    b = a + mu * (1.0 - e)
+    z = u_z < a / b
+    lhs = u_z * b
+    with np.errstate(invalid="ignore", divide="ignore"):
+        margin = np.abs(lhs - a) / (lhs + a)   # both sides carry a few ulp of their own size
+    margin = np.where(np.isfinite(margin), margin, 0.0)
+    with np.errstate(under="ignore"):
+        churned = orc.tau_churned(t_x, T_cal, ml, u_tau)
+    alive = T_cal + (1.0 / mu) * e_alive
+    tau = np.where(z != bool(swap_tau_branch), alive, churned)
+    return z, tau, margin
+
+
+def inv_sigma_block(Sigma):
+    """bi:281 / tri:402: the [0:2, 0:2] block of the full inverse (quirk Q4 for D = 3)."""
+    return np.linalg.inv(np.asarray(Sigma, dtype=np.float64))[:2, :2]
+
+
+def lp_magnitude(x, w, mv, P, ll, lm, pl, pm):
+    """Size of the terms that make up lp(pl, pm) - lp(ll, lm): the scale its rounding error is
+    relative to (as ``mag`` in test_device_mh_step_matches_reference_log_posterior)."""
+    pmax = np.abs(P).max()
+    quad = lambda a, b: (np.abs(a - mv[:, 0]) + np.abs(b - mv[:, 1])) ** 2 * pmax  # noqa: E731
+    with np.errstate(over="ignore"):
+        ex = np.exp(np.minimum(ll, 700)) + np.exp(np.minimum(lm, 700)) + np.exp(pl) + np.exp(np.minimum(pm, 700))
+    return (np.abs(x * ll) + np.abs(x * pl) + np.abs(lm) + np.abs(pm) + w * ex
+            + quad(ll, lm) + quad(pl, pm) + np.abs(mv).sum(1) ** 2 * pmax + 1.0)
+
+
+def mh_steps(x, T_cal, z, tau, mv, P, s00, s11, ll, lm, t_l, t_m, log2_u, stages=None):
+    """bi:312-335 for S = len(t_l) steps from (ll, lm): proposal ll + Sigma[0,0] t (variance as the
+    scale, quirk Q2) clipped to [-70, 70]; accept iff pm <= 5 and lp' - lp > ln2 log2 U (false on NaN;
+    any finite lp' from lp = -inf).  Returns (ll, lm, cur, margin, hit_clip, hit_cap)."""
+    n = ll.shape[0]
+    ll, lm = ll.copy(), lm.copy()
+    w = np.where(z, T_cal, tau)
+    xf = np.asarray(x, dtype=np.float64)
+    zf = z.astype(np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        cur = orc.log_posterior(ll, lm, xf, zf, T_cal, tau, mv, P)
+    margin = np.full(n, np.inf)
+    hit_clip = np.zeros(n, bool)
+    hit_cap = np.zeros(n, bool)
+    for j in range(len(t_l)):
+        raw_l = ll + s00 * t_l[j].astype(np.float64)
+        raw_m = lm + s11 * t_m[j].astype(np.float64)
+        pl = np.clip(raw_l, -CLIP, CLIP)
+        pm = np.clip(raw_m, -CLIP, CLIP)
+        hit_clip |= (np.abs(raw_l) >= CLIP) | (np.abs(raw_m) >= CLIP)
+        with np.errstate(invalid="ignore", over="ignore"):
+            plp = orc.log_posterior(pl, pm, xf, zf, T_cal, tau, mv, P)
+            thr = LN2 * log2_u[j].astype(np.float64)
+            d = plp - cur                               # NaN for -inf - -inf: never accepted
+            capped = pm > MU_CAP
+            hit_cap |= capped
+            acc = ~capped & (d > thr)
+            m_lp = np.abs(d - thr) / lp_magnitude(xf, w, mv, P, ll, lm, pl, pm)
+        m_lp = np.where(capped | ~np.isfinite(d), np.inf, m_lp)   # decided by the cap / an infinity
+        margin = np.minimum(margin, np.minimum(m_lp, np.abs(MU_CAP - pm)))
+        if stages is not None:
+            stages.append(dict(pl=pl, pm=pm, plp=plp, cur=cur.copy(), accept=acc))
+        ll[acc] = pl[acc]
+        lm[acc] = pm[acc]
+        cur[acc] = plp[acc]
+    return ll, lm, cur, margin, hit_clip, hit_cap
+
+
+class _One:
+    """The ``Stream`` face draw_eta needs: hands out the given standard normals."""
+    def __init__(self, zeta):
+        self.zeta = zeta
+
+    def standard_normal(self, n, key):
+        assert n == self.zeta.shape[0]
+        return self.zeta
+
+
+def sweep_level1(x, t_x, T_cal, X, lam, mu, beta, Sigma, var, log_s=None, omega2=None,
+                 swap_tau_branch=False, stages=False):
+    """One chain, one sweep's level-1 half (bi:388-396; tri:511-526) from the state (lam, mu) entering
+    it, the (beta K x D, Sigma D x D) its MH uses, and its variates ``var``: u_z, u_tau, e_alive (n),
+    t_l / t_m / log2_u (S x n, the device's fp32 values or the oracle's), eta_z (n, D = 3).
+    Returns a dict: z, tau, lam, mu, ll, lm, (eta, leta), lik (the likelihood term, bi:415-427),
+    margin (the smallest of margin_z, margin_mh) and hit_clip / hit_cap flags; ``stages=True`` adds
+    the per-step proposals and log posteriors under "steps" and the coefficients mv, P."""
+    lam = np.asarray(lam, dtype=np.float64)
+    mu = np.asarray(mu, dtype=np.float64)
+    beta = np.asarray(beta, dtype=np.float64)
+    Sigma = np.asarray(Sigma, dtype=np.float64)
+    z, tau, margin_z = draw_z_tau(t_x, T_cal, lam, mu, var["u_z"], var["u_tau"], var["e_alive"], swap_tau_branch)
+    mv = X @ beta
+    P = inv_sigma_block(Sigma)
+    steps = [] if stages else None
+    ll, lm, cur, margin_mh, hit_clip, hit_cap = mh_steps(
+        x, T_cal, z, tau, mv, P, Sigma[0, 0], Sigma[1, 1], np.log(lam), np.log(mu),
+        var["t_l"], var["t_m"], var["log2_u"], steps)
+    out = dict(z=z, tau=tau, ll=ll, lm=lm, lam=np.exp(ll), mu=np.exp(lm), cur=cur, margin_z=margin_z,
+               margin_mh=margin_mh, margin=np.minimum(margin_z, margin_mh), hit_clip=hit_clip, hit_cap=hit_cap)
+    if Sigma.shape[0] == 3:
+        leta = orc.draw_eta(log_s, X, beta, Sigma, omega2, _One(var["eta_z"]))   # tri:306-333 (log scale)
+        out.update(leta=leta, eta=np.exp(leta))
+    zf = z.astype(np.float64)
+    # bi:415-427 on the natural-scale state (log(exp(ll)) = ll: no round trip)
+    out["lik"] = x * ll + (1 - zf) * lm - (out["lam"] + out["mu"]) * (zf * T_cal + (1 - zf) * tau)
+    if stages:
+        out.update(steps=steps, mv=mv, P=P)
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
+# level 2
+# ---------------------------------------------------------------------------------------------
+def level2_draw(X, Y, hyper, iw_normal, iw_chi2, beta_z):
+    """bi:233-262 / tri:340-380 from the variates: Sigma ~ IW by scipy's Bartlett form, then
+    beta = B_hat + kron(chol Sigma, chol V) z paired with B_hat's row-major ravel (quirk Q1) — the
+    lower-Cholesky factor of the reference's kron(Sigma, V) covariance.  Returns a dict."""
+    V, B_hat, S_n, nu_n = orc.level2_posterior(X, Y, hyper)
+    Sigma = orc.invwishart_from_variates(S_n, np.asarray(iw_normal, dtype=np.float64), np.asarray(iw_chi2, dtype=np.float64))
+    F = np.kron(np.linalg.cholesky(Sigma), np.linalg.cholesky(V))
+    beta = (B_hat.ravel() + F @ np.asarray(beta_z, dtype=np.float64)).reshape(B_hat.shape)
+    return dict(beta=beta, Sigma=Sigma, B_hat=B_hat, S_n=S_n, nu_n=nu_n, V=V, factor=F)
+
+
+def hyper_variates(seed, chain, hsweep, D, K, nu_n, beta_slot_shift=0):
+    """The hyper stream's variates of the level-2 draw that BELONGS TO sweep ``hsweep`` (the sweep
+    whose MH uses it for D = 2 — drawn after sweep hsweep - 1, the first from the initial state; the
+    sweep it follows for D = 3): Bartlett normals in slots HSLOT_NORMAL0 + [0, D(D-1)/2), the beta
+    normals in HSLOT_BETA_NORMAL0 + [0, D K), chi-square q with nu_n - D + 1 + q degrees of freedom.
+    ``beta_slot_shift`` (power checks only) moves the beta normals' slots."""
+    iw = np.array([oph.hyper_normal(seed, chain, oph.HSLOT_NORMAL0 + i, hsweep) for i in range(D * (D - 1) // 2)])
+    chi = np.array([oph.chi2_draw(seed, chain, hsweep, q, nu_n - D + 1 + q) for q in range(D)])
+    bz = np.array([oph.hyper_normal(seed, chain, oph.HSLOT_BETA_NORMAL0 + beta_slot_shift + j, hsweep)
+                   for j in range(D * K)])
+    return iw, chi, bz
+
+
+def l2_record(beta, Sigma):
+    """The stored level-2 row (bi:411-412, tri:549-554): beta.T.ravel(), then Sigma's upper triangle."""
+    D = Sigma.shape[0]
+    return np.concatenate([np.asarray(beta).T.ravel(), Sigma[np.triu_indices(D)]])
+
+
+def l2_unpack(row, D, K):
+    beta = np.asarray(row[: D * K]).reshape(D, K).T.copy()
+    Sigma = np.zeros((D, D))
+    Sigma[np.triu_indices(D)] = row[D * K:]
+    Sigma = Sigma + np.triu(Sigma, 1).T
+    return beta, Sigma
+
+
+# ---------------------------------------------------------------------------------------------
+# a problem as the model sees it, the test cases, and a free-running model chain
+# ---------------------------------------------------------------------------------------------
+class ModelProblem:
+    """The reference's setup (bi:367-374, 467-479; tri:488-499, 615-626) from a CBS DataFrame."""
+
+    def __init__(self, df, covariates, D):
+        cbs, self.X = orc.design_matrix(df, covariates)
+        self.D, (self.N, self.K) = D, self.X.shape
+        self.x = cbs["x"].to_numpy()
+        self.t_x = cbs["t_x"].to_numpy().astype(np.float64)
+        self.T_cal = cbs["T_cal"].to_numpy().astype(np.float64)
+        self.hyper = orc.default_hyper(self.K, D)
+        _, self.lam0, self.mu0 = orc.init_state(self.x, self.t_x, self.T_cal)
+        self.hyper["beta_0"][0, 0] = math.log(self.lam0.mean())
+        self.hyper["beta_0"][0, 1] = math.log(self.mu0.mean())
+        self.log_s = self.omega2 = None
+        if D == 3:
+            self.log_s = cbs["log_s"].to_numpy()
+            self.omega2 = float(cbs["log_s"].var())
+            self.hyper["beta_0"][0, 2] = cbs["log_s"].mean()
+        self.nu_n = self.hyper["nu_00"] + self.N
+
+    def level1(self, lam, mu, beta, Sigma, var, **kw):
+        return sweep_level1(self.x, self.t_x, self.T_cal, self.X, lam, mu, beta, Sigma, var,
+                            log_s=self.log_s, omega2=self.omega2, **kw)
+
+    def level2(self, seed, chain, hsweep, Y, hsweep_of_variates=None, beta_slot_shift=0):
+        hv = hyper_variates(seed, chain, hsweep if hsweep_of_variates is None else hsweep_of_variates,
+                            self.D, self.K, self.nu_n, beta_slot_shift)
+        return level2_draw(self.X, Y, self.hyper, *hv)
+
+
+# The GPU module's cases (ISSUE table): name -> D, covariates, data, N, S, chains, chain_first, seed,
+# burnin, mcmc, thin and the driving ("run" n sweeps / "state" = get_state).
+CASES = {
+    "bi_k1": dict(D=2, covs=[], data=("abe", 300, 0), S=20, chains=3, chain_first=0, seed=20240611,
+                  burnin=0, mcmc=6, thin=1, drive=[("run", 6)]),
+    "bi_k2": dict(D=2, covs=["first_sales_scaled"], data=("abe", 600, 0), S=7, chains=2, chain_first=0, seed=77,
+                  burnin=5, mcmc=4, thin=1, drive=[("run", 5), ("state",), ("run", 4)]),
+    "bi_k5": dict(D=2, covs=["c1", "c2", "c3", "c4"], data=("abe", 384, 4), S=20, chains=1, chain_first=2, seed=1234,
+                  burnin=2, mcmc=6, thin=3, drive=[("run", 1), ("state",)] * 8),
+    "tri_k3": dict(D=3, covs=["gender_F", "age_scaled"], data=("abe", 300, 0), S=23, chains=2, chain_first=0,
+                   seed=99, burnin=0, mcmc=6, thin=1, drive=[("run", 6)]),
+    "tri_k9": dict(D=3, covs=[f"c{k}" for k in range(1, 9)], data=("abe", 384, 8), S=20, chains=2, chain_first=0,
+                   seed=4242, burnin=0, mcmc=5, thin=1, drive=[("run", 5)]),
+    "bi_k1_s0": dict(D=2, covs=[], data=("abe", 300, 0), S=0, chains=2, chain_first=0, seed=5,
+                     burnin=0, mcmc=6, thin=1, drive=[("run", 6)]),
+}
+
+
+def case_frame(case):
+    from tests.helpers import cdnow, with_covariates
+    name, n, n_cov = case["data"]
+    df = cdnow(name, n)
+    return with_covariates(df, n_cov) if n_cov else df
+
+
+def n_sweeps_of(case):
+    return sum(a[1] for a in case["drive"] if a[0] == "run")
+
+
+def oracle_variates(seed, chain, sweep, n, S):
+    """oracle.philox.sweep_variates in the form the model takes, cast as the device casts them: the
+    accept threshold is log2 of the fp32 uniform, rounded to fp32."""
+    v = oph.sweep_variates(seed, chain, sweep, n, S)
+    v["log2_u"] = np.log2(v["u_acc"].astype(np.float64)).astype(np.float32)
+    return v
+
+
+def model_chain(mp: ModelProblem, seed, chain, n_sweeps, S, variates=oracle_variates):
+    """The model run freely (its own state from sweep to sweep) in the reference's order — bi: level
+    2 (the draw belonging to the sweep), then level 1; tri: level 1 with the previous draw (sweep 1:
+    beta_0, gamma_00), then level 2.  Yields (sweep, level-1 dict, level-2 dict used / drawn)."""
+    lam, mu = mp.lam0.copy(), mp.mu0.copy()
+    beta, Sigma = mp.hyper["beta_0"], mp.hyper["gamma_00"].copy()
+    for s in range(1, n_sweeps + 1):
+        var = variates(seed, chain, s, mp.N, S)
+        if mp.D == 2:
+            l2 = mp.level2(seed, chain, s, np.column_stack([np.log(lam), np.log(mu)]))
+            beta, Sigma = l2["beta"], l2["Sigma"]
+        r = mp.level1(lam, mu, beta, Sigma, var)
+        if mp.D == 3:
+            l2 = mp.level2(seed, chain, s, np.column_stack([r["ll"], r["lm"], r["leta"]]))
+            r["beta_in"], r["Sigma_in"] = beta, Sigma
+            beta, Sigma = l2["beta"], l2["Sigma"]
+        lam, mu = r["lam"], r["mu"]
+        yield s, r, l2
