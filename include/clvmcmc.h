@@ -396,9 +396,9 @@ int clv_chain_total_loglik_sampler(clv_sampler* s, double* mean_total);
  * at lag T and made monotone, tau floored at 1 / log10(2 m (n / 2))); mcse = sd / sqrt(ess); and
  * the truncation lag T (-1 when no pair was accepted).  All six are NaN for a series with a
  * non-finite value (after the log) or zero within-chain variance — a customer whose z never
- * changes.  az.summary reports the rank-normalised variants (bulk / tail ESS, rank R-hat): those,
- * and R-hat of quantiles, are out of scope; this estimator is meant for the scales the sampler
- * works on — log lambda, log mu and the level-2 parameters.
+ * changes.  az.summary reports the rank-normalised variants (bulk / tail ESS, rank R-hat): those
+ * are clv_rank_diagnostics below; this estimator is meant for the scales the sampler works on —
+ * log lambda, log mu and the level-2 parameters.
  *   series: [chain][draw][n_series] — level-2 draws [chain][draw][P] as they are, level-1 draws
  *           [chain][draw][n][D+2] with n_series = n (D+2);  out: [n_series][CLV_N_DIAG_STATS].
  *   Series s is logged when bit s % period of log_mask is set (period 1..32; level 1: D+2).
@@ -418,6 +418,50 @@ int clv_diagnostics(int32_t device, const double* series, int32_t n_chains, int6
 int clv_diagnostics_sampler(clv_sampler* s, uint32_t log_mask, double* level1_out, double* level2_out);
 int clv_autocorr(int32_t device, const double* series, int32_t n_chains, int64_t n_draws, int64_t n_series,
                  int32_t max_lag, double* out);
+
+/* ---- Rank-normalised diagnostics on device (csrc/diag.hip) ----
+ * The remaining columns of az.summary (hdi, mcse_sd, ess_bulk, ess_tail, r_hat), after Vehtari,
+ * Gelman, Simpson, Carpenter & Buerkner (2021) as ArviZ implements them; same input, logging and
+ * limits as clv_diagnostics, thirteen doubles per series.  With y the (logged) m x n series,
+ * h = n / 2, the 2 m split chains y[c][0..h) and y[c][n-h..n) (an odd n drops its middle draw),
+ * S = 2 m h pooled split values, and ESS(.), Rhat(.), lag the estimator of clv_diagnostics applied
+ * to split chains:
+ *   z(s)         Phi^-1((r - 3/8) / (S + 1/4)), r the average 1-based rank of s in the pool (ties
+ *                share the mean of their positions); Phi^-1 is Wichura's AS241 (PPND16)
+ *   RHAT_BULK    Rhat(z(split y));  ESS_BULK = ESS(z(split y)), LAG_BULK its truncation lag
+ *   RHAT_FOLDED  Rhat(z(|split y - med|)), med the median of the S split values
+ *   RHAT         max(RHAT_BULK, RHAT_FOLDED): az.summary's r_hat
+ *   ESS_Q05/Q95  ESS(split I(y <= q_p)), q_p numpy's default (linear) quantile of all m n values
+ *   ESS_TAIL     min(ESS_Q05, ESS_Q95)
+ *   ESS_SD       ESS(split (y - mean)^2);  MCSE_SD = sqrt(varvar / evar / 4) with evar = mean((y -
+ *                mean)^2), varvar = (mean((y - mean)^4) - evar^2) / ESS_SD
+ *   HDI_LO/HI    with the m n values sorted and k = floor(hdi_prob m n): (x[i], x[i+k]) for the
+ *                first i < m n - k that minimises x[i+k] - x[i]
+ *   MEDIAN       of all m n values
+ * NaN: a series with a non-finite value (after the log) is NaN in all thirteen; otherwise a
+ * statistic is NaN exactly when its own transformed split series has no within-chain variance
+ * (MCSE_SD also when evar == 0), RHAT and ESS_TAIL when either of their two components is;
+ * HDI_* and MEDIAN are always finite.  A binary series (z) has a finite ESS_BULK but usually a
+ * NaN ESS_Q95: its indicator is all ones.
+ * A series of up to CLV_RANK_LDS_ELEMS values (m n) is sorted and transformed in LDS (two buffers
+ * of that many doubles and the workgroup's scalars: 64 KiB, two workgroups per CU); longer series
+ * take the same code on global-memory scratch.  Every sum runs in an order fixed by (m, n): the
+ * _sampler entry gives the same bits as the host-array one; CLV_ESTATE as clv_diagnostics_sampler.
+ * clv_debug_zscale: ranks and z of the split values (folded: of |split y - med|), [n_series][2 m][h]
+ * each in split-chain order (chain 0 first half, chain 0 second half, chain 1 first half, ...).
+ * CLV_EINVAL before any device call: as clv_diagnostics, and hdi_prob outside (0, 1). */
+#define CLV_RANK_LDS_ELEMS 4080
+enum {
+  CLV_RANK_RHAT = 0, CLV_RANK_RHAT_BULK, CLV_RANK_RHAT_FOLDED, CLV_RANK_ESS_BULK, CLV_RANK_ESS_TAIL,
+  CLV_RANK_ESS_Q05, CLV_RANK_ESS_Q95, CLV_RANK_ESS_SD, CLV_RANK_MCSE_SD, CLV_RANK_HDI_LO, CLV_RANK_HDI_HI,
+  CLV_RANK_MEDIAN, CLV_RANK_LAG_BULK, CLV_N_RANK_STATS
+};
+int clv_rank_diagnostics(int32_t device, const double* series, int32_t n_chains, int64_t n_draws, int64_t n_series,
+                         int32_t period, uint32_t log_mask, double hdi_prob, double* out);
+int clv_rank_diagnostics_sampler(clv_sampler* s, uint32_t log_mask, double hdi_prob, double* level1_out,
+                                 double* level2_out);
+int clv_debug_zscale(int32_t device, const double* series, int32_t n_chains, int64_t n_draws, int64_t n_series,
+                     int32_t folded, double* ranks_out, double* z_out);
 
 /* ---- Data preparation on device ----
  * Event log -> CBS (utils/elog2cbs2param.py:33-94): events (cust, date in ns since the epoch,

@@ -146,6 +146,9 @@ def lib() -> ctypes.CDLL:
         "clv_diagnostics": (c_int32, [c_int32, dp, c_int32, c_int64, c_int64, c_int32, c_uint32, dp]),
         "clv_diagnostics_sampler": (c_int32, [sp, c_uint32, dp, dp]),
         "clv_autocorr": (c_int32, [c_int32, dp, c_int32, c_int64, c_int64, c_int32, dp]),
+        "clv_rank_diagnostics": (c_int32, [c_int32, dp, c_int32, c_int64, c_int64, c_int32, c_uint32, c_double, dp]),
+        "clv_rank_diagnostics_sampler": (c_int32, [sp, c_uint32, c_double, dp, dp]),
+        "clv_debug_zscale": (c_int32, [c_int32, dp, c_int32, c_int64, c_int64, c_int32, dp, dp]),
         "clv_elog2cbs": (c_int32, [c_int32, c_int64, POINTER(c_int64), POINTER(c_int64), dp, c_int64, c_int64, c_int64,
                                    POINTER(c_int64), POINTER(c_int64), POINTER(c_int64), dp, dp, dp, dp,
                                    POINTER(c_int64), dp, dp, POINTER(c_int64), dp]),
@@ -172,6 +175,12 @@ L1_STATS = ("mean_lambda", "lambda_p025", "lambda_p975", "mean_mu", "mean_mu_cap
 
 # Columns of clv_diagnostics() (include/clvmcmc.h CLV_DIAG_*).
 DIAG_STATS = ("mean", "sd", "mcse", "ess", "rhat", "lag")
+
+# Columns of clv_rank_diagnostics() (include/clvmcmc.h CLV_RANK_*), and CLV_RANK_LDS_ELEMS: the
+# longest series (chains x draws) that is ranked in LDS; longer ones take global-memory scratch.
+RANK_STATS = ("rhat", "rhat_bulk", "rhat_folded", "ess_bulk", "ess_tail", "ess_q05", "ess_q95", "ess_sd", "mcse_sd",
+              "hdi_lo", "hdi_hi", "median", "lag_bulk")
+RANK_LDS_ELEMS = 4080
 
 
 def exported_symbols():

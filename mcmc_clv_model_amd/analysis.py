@@ -15,6 +15,9 @@ Reference functions mirrored (same names, arguments, defaults and return layout)
   ArviZ (``az.summary``, ``az.plot_autocorr``) on the level-2 draws, and ``level1_diagnostics``, the
   same convergence check for every customer's parameters (``csrc/diag.hip``: split R-hat and mean
   ESS without rank normalisation, see :func:`level1_diagnostics`).
+* ``level2_summary`` — the nine columns of ``az.summary`` (``analysis_abe.py:690-693``) with the
+  rank-normalised ``ess_bulk``, ``ess_tail`` and ``r_hat``; ``level1_rank_diagnostics`` /
+  ``level2_rank_diagnostics`` give every rank-normalised statistic (``clv_rank_diagnostics``).
 
 The per-customer / per-draw work runs in ``csrc/analysis.hip`` through the C ABI (``clv_predict``,
 ``clv_track``, ``clv_level1_summary``, ``clv_chain_total_loglik``); the host only reshapes and
@@ -37,7 +40,7 @@ from .sampler import resolve_seed
 __all__ = ["draw_future_transactions", "draw_future_transactions_rfm_m", "post_mean_lambdas", "post_mean_mus",
            "chain_total_loglik", "compute_table4", "level1_summary", "posterior_weekly_tracking",
            "level1_diagnostics", "level2_diagnostics", "level2_autocorr", "summarize_level2", "extract_correlation",
-           "summary_rhat"]
+           "summary_rhat", "level1_rank_diagnostics", "level2_rank_diagnostics", "level2_summary"]
 
 
 def _stacked_level1(level1_chains) -> np.ndarray:
@@ -259,8 +262,8 @@ def level1_diagnostics(draws: Dict[str, Any], *, log_columns=("lambda", "mu"), d
     ArviZ WITHOUT rank normalisation: every chain is split in halves, the biased autocovariances of
     the split chains are averaged, Geyer's initial positive sequence is cut at ``lag`` and made
     monotone, ``ess = M h / tau``, ``mcse = sd / sqrt(ess)``.  ``az.summary`` reports the
-    rank-normalised variants; rank-normalised bulk ESS, tail ESS and R-hat of quantiles are out of
-    scope.  The estimator is meant for the scales the sampler works on — log lambda, log mu and the
+    rank-normalised variants: those are :func:`level1_rank_diagnostics` (R-hat and ESS of arbitrary
+    quantiles stay out of scope).  The estimator is meant for the scales the sampler works on — log lambda, log mu and the
     level-2 parameters — hence the default ``log_columns``.  A series with a non-finite value or no
     within-chain variance (a customer whose ``z`` never changes) gives NaN in all six statistics.
     Needs at least 8 draws per chain."""
@@ -276,11 +279,130 @@ def level2_diagnostics(draws: Dict[str, Any], param_names=None, *, device: int =
     """The project's ``az.summary`` of the level-2 draws (bivariate/analysis_abe.py:651-706): one row
     per level-2 parameter with mean, sd, mcse, ess, rhat and the truncation lag — the estimator of
     :func:`level1_diagnostics` (not rank-normalised, unlike az.summary's ess_bulk / ess_tail /
-    r_hat), on the parameters as drawn."""
+    r_hat: :func:`level2_summary` has those, in az.summary's nine columns), on the parameters as
+    drawn."""
     a = _chains_array(draws["level_2"])
     if a.ndim != 3:
         raise ValueError("level_2 draws must be (n_draws, n_params) per chain")
     return level2_diagnostics_frame(_diagnostics(a, a.shape[2], 1, 0, device), param_names)
+
+
+# ---- rank-normalised diagnostics (csrc/diag.hip, clv_rank_diagnostics) -------------------------
+def _check_hdi_prob(hdi_prob) -> float:
+    p = float(hdi_prob)
+    if not 0.0 < p < 1.0:
+        raise ValueError(f"hdi_prob must be in (0, 1) (got {hdi_prob!r})")
+    return p
+
+
+def hdi_column_names(hdi_prob: float = 0.94):
+    """ArviZ's names of the two HDI columns: ("hdi_3%", "hdi_97%") at 0.94."""
+    p = _check_hdi_prob(hdi_prob)
+    return f"hdi_{100 * (1 - p) / 2:g}%", f"hdi_{100 * (1 - (1 - p) / 2):g}%"
+
+
+def level1_rank_diagnostics_frame(stats: np.ndarray, n: int, width: int, log_mask: int) -> pd.DataFrame:
+    """[n * width][13] rank statistics -> one row per customer, columns f"{stat}_{param}"."""
+    a = np.asarray(stats).reshape(n, width, len(_lib.RANK_STATS))
+    cols = {}
+    for j, nm in enumerate(LEVEL1_PARAMS[:width]):
+        pname = f"log_{nm}" if (log_mask >> j) & 1 else nm
+        for k, st in enumerate(_lib.RANK_STATS):
+            cols[f"{st}_{pname}"] = a[:, j, k]
+    return pd.DataFrame(cols)
+
+
+def _level2_names(n_params: int, param_names):
+    names = list(param_names) if param_names is not None else [f"level_2[{i}]" for i in range(n_params)]
+    if len(names) != n_params:
+        raise ValueError(f"param_names has {len(names)} entries for {n_params} level-2 parameters")
+    return names
+
+
+def level2_rank_diagnostics_frame(stats: np.ndarray, param_names=None) -> pd.DataFrame:
+    a = np.asarray(stats)
+    return pd.DataFrame(a, columns=list(_lib.RANK_STATS), index=_level2_names(a.shape[0], param_names))
+
+
+SUMMARY_COLUMNS = ("mean", "sd", "hdi_lo", "hdi_hi", "mcse_mean", "mcse_sd", "ess_bulk", "ess_tail", "r_hat")
+
+
+def level2_summary_frame(stats: np.ndarray, rank_stats: np.ndarray, param_names=None,
+                         hdi_prob: float = 0.94) -> pd.DataFrame:
+    """az.summary's nine columns from the [P][6] statistics of clv_diagnostics (mean, sd, mcse_mean)
+    and the [P][13] of clv_rank_diagnostics (the rest)."""
+    d, r = np.asarray(stats), np.asarray(rank_stats)
+    D, K = _lib.DIAG_STATS.index, _lib.RANK_STATS.index
+    lo, hi = hdi_column_names(hdi_prob)
+    cols = {"mean": d[:, D("mean")], "sd": d[:, D("sd")], lo: r[:, K("hdi_lo")], hi: r[:, K("hdi_hi")],
+            "mcse_mean": d[:, D("mcse")], "mcse_sd": r[:, K("mcse_sd")], "ess_bulk": r[:, K("ess_bulk")],
+            "ess_tail": r[:, K("ess_tail")], "r_hat": r[:, K("rhat")]}
+    return pd.DataFrame(cols, index=_level2_names(d.shape[0], param_names))
+
+
+def _rank_diagnostics(a: np.ndarray, n_series: int, period: int, log_mask: int, hdi_prob: float,
+                      device: int) -> np.ndarray:
+    L = _L()
+    out = np.empty((n_series, len(_lib.RANK_STATS)), np.float64)
+    check(L.clv_rank_diagnostics(int(device), dptr(a), a.shape[0], a.shape[1], n_series, period, log_mask,
+                                 float(hdi_prob), dptr(out)))
+    return out
+
+
+def level1_rank_diagnostics(draws: Dict[str, Any], *, log_columns=("lambda", "mu"), hdi_prob: float = 0.94,
+                            device: int = -1) -> pd.DataFrame:
+    """Per-customer rank-normalised diagnostics of the level-1 draws, on the GPU (``csrc/diag.hip``,
+    ``clv_rank_diagnostics``): what ``az.summary`` computes per variable — Vehtari, Gelman, Simpson,
+    Carpenter & Buerkner (2021) as ArviZ implements them — for every customer's series.
+
+    One row per customer; columns ``f"{stat}_{param}"``, params as in :func:`level1_diagnostics`,
+    stats ``rhat`` (the larger of ``rhat_bulk``, the split R-hat of the rank-normalised draws, and
+    ``rhat_folded``, that of the rank-normalised absolute deviations from the median), ``ess_bulk``
+    with its truncation lag ``lag_bulk``, ``ess_tail`` (the smaller of ``ess_q05`` and ``ess_q95``,
+    the ESS of the indicators of the 5 % and 95 % quantiles), ``ess_sd`` and ``mcse_sd``, the
+    highest-density interval ``hdi_lo`` / ``hdi_hi`` of probability ``hdi_prob`` and the
+    ``median``.  Ranks are invariant under the log, so ``log_columns`` only moves ``mcse_sd``,
+    ``ess_sd``, the HDI and the median to the log scale.  A series with a non-finite value is NaN
+    throughout; otherwise a statistic is NaN exactly when its own transformed series has no
+    within-chain variance — a binary ``z`` usually has a NaN ``ess_q95`` (and so ``ess_tail``):
+    every draw is at or below its 95 % quantile."""
+    a = _chains_array(draws.get("level_1"))
+    if a.ndim != 4 or a.shape[3] not in (4, 5):
+        raise ValueError("level_1 draws must be (n_draws, n_customers, 4 or 5) per chain")
+    n, w = a.shape[2], a.shape[3]
+    mask = level1_log_mask(log_columns, w)
+    p = _check_hdi_prob(hdi_prob)
+    return level1_rank_diagnostics_frame(_rank_diagnostics(a, n * w, w, mask, p, device), n, w, mask)
+
+
+def _level2_array(draws) -> np.ndarray:
+    a = _chains_array(draws["level_2"])
+    if a.ndim != 3:
+        raise ValueError("level_2 draws must be (n_draws, n_params) per chain")
+    return a
+
+
+def level2_rank_diagnostics(draws: Dict[str, Any], param_names=None, *, hdi_prob: float = 0.94,
+                            device: int = -1) -> pd.DataFrame:
+    """Every rank-normalised statistic of :func:`level1_rank_diagnostics` for the level-2 parameters
+    as drawn: one row per parameter, columns ``_lib.RANK_STATS``."""
+    a = _level2_array(draws)
+    p = _check_hdi_prob(hdi_prob)
+    return level2_rank_diagnostics_frame(_rank_diagnostics(a, a.shape[2], 1, 0, p, device), param_names)
+
+
+def level2_summary(draws: Dict[str, Any], param_names=None, *, hdi_prob: float = 0.94,
+                   device: int = -1) -> pd.DataFrame:
+    """The ``az.summary(idata, var_names=["level_2"])`` table of the reference
+    (bivariate/analysis_abe.py:690-693): one row per level-2 parameter, columns ``mean, sd, hdi_3%,
+    hdi_97%, mcse_mean, mcse_sd, ess_bulk, ess_tail, r_hat`` (the HDI names follow ``hdi_prob`` as
+    ArviZ's do), with ArviZ's rank-normalised definitions of the last five; not rounded.  One
+    ``clv_diagnostics`` and one ``clv_rank_diagnostics`` call."""
+    a = _level2_array(draws)
+    p = _check_hdi_prob(hdi_prob)
+    names = _level2_names(a.shape[2], param_names)
+    return level2_summary_frame(_diagnostics(a, a.shape[2], 1, 0, device),
+                                _rank_diagnostics(a, a.shape[2], 1, 0, p, device), names, p)
 
 
 def level2_autocorr(draws: Dict[str, Any], max_lag: int = 100, *, device: int = -1) -> np.ndarray:

@@ -19,7 +19,10 @@ line and return layout (bivariate/mcmc.py:437-504); the sweeps run on the GPU
 * ``diagnostics``: True adds ``out["diagnostics"] = {"level_1": DataFrame per customer, "level_2":
   DataFrame per level-2 parameter}`` — split R-hat, ESS, MCSE and truncation lag computed on the GPU
   from the draws still in HBM (``analysis.level1_diagnostics`` / ``level2_diagnostics``;
-  ``draw_sink="full"`` only, at least 8 stored draws).  False changes nothing.
+  ``draw_sink="full"`` only, at least 8 stored draws).  False changes nothing.  ``"rank"`` gives
+  the same and adds ``"level_1_rank"``, ``"level_2_rank"`` (rank-normalised R-hat, bulk and tail ESS,
+  MCSE of the sd, HDI, median: ``analysis.level1_rank_diagnostics`` / ``level2_rank_diagnostics``)
+  and ``"level_2_summary"``, the nine columns of ``az.summary`` (``analysis.level2_summary``).
 """
 from __future__ import annotations
 
@@ -36,7 +39,7 @@ def mcmc_draw_parameters(cal_cbs, covariates: Optional[Sequence[str]] = None, mc
                          trace: int = 100, n_mh_steps: int = 20, *, draw_sink: str = "full",
                          rng: str = "philox", device: int = -1, replay_tape=None,
                          replay_sweeps: Optional[int] = None, devices: Optional[Sequence[int]] = None,
-                         shard: str = "auto", exchange: str = "auto", diagnostics: bool = False):
+                         shard: str = "auto", exchange: str = "auto", diagnostics=False):
     """Run the Abe (2009) Gibbs/MH sampler on calibration CBS (bivariate/mcmc.py:437).
 
     Returns dict(level_1=[(n_draws, N, 4) per chain: lambda, mu, tau, z],

@@ -8,6 +8,9 @@
 //   clv_diagnostics          host array [chain][draw][n_series]  -> [n_series][CLV_N_DIAG_STATS]
 //   clv_diagnostics_sampler  the level-1 / level-2 draws a sampler holds in HBM (no host copy)
 //   clv_autocorr             host array -> [chain][n_series][max_lag + 1]
+//   clv_rank_diagnostics[_sampler]  the rank-normalised columns of az.summary (rank R-hat, bulk and
+//                            tail ESS, MCSE of the sd, HDI, median): a workgroup per series, see
+//                            "Rank-normalised diagnostics" below -> [n_series][CLV_N_RANK_STATS]
 //
 // Batches of series are transposed to contiguous [series][chain][draw] (the log of the logged
 // series taken on the way), then one wavefront owns a series: it stages it in LDS (series of more
@@ -22,6 +25,7 @@
 #include <cmath>
 #include <string>
 
+#include "fastmath.h"
 #include "internal.h"
 
 using namespace clv;
@@ -62,25 +66,78 @@ __device__ __forceinline__ double wave_sum(double v) {
   return v;
 }
 
-// Mean over the nseg segments of the biased autocovariance at this lane's lag t (tbase = lane 0's):
-// (1/nseg) sum_j (1/h) sum_{i < h - t} c_j[i] c_j[i + t].  Segment j begins at (j / 2) n + (j % 2)
-// (n - h): the split chains of [chain][n] draws, or (nseg 1, h == n) one whole chain.  Lanes with
-// t >= h return 0.
-__device__ __forceinline__ double lag_block(const double* buf, int nseg, int64_t n, int64_t h, int64_t t,
-                                            int64_t tbase) {
+// One segment's biased autocovariance at this lane's lag t (tbase = lane 0's): (1/h) sum_{i < h - t}
+// c[i] c[i + t], the products added in draw order.  Lanes with t >= h return 0.
+__device__ __forceinline__ double lag_chain(const double* c, int64_t h, int64_t t, int64_t tbase) {
   const int64_t full = std::max<int64_t>(0, h - tbase - (DIAG_LANES - 1));  // i + t < h in every lane
   const int64_t any = std::max<int64_t>(0, h - tbase);                      // i + t < h in lane 0
-  double asum = 0.0;
-  for (int j = 0; j < nseg; ++j) {
-    const double* c = buf + (int64_t)(j >> 1) * n + (int64_t)(j & 1) * (n - h);
-    double acc = 0.0;
+  double acc = 0.0;
 #pragma unroll 4
-    for (int64_t i = 0; i < full; ++i) acc += c[i] * c[i + t];
-    for (int64_t i = full; i < any; ++i)
-      if (i + t < h) acc += c[i] * c[i + t];
-    asum += acc / (double)h;
-  }
+  for (int64_t i = 0; i < full; ++i) acc += c[i] * c[i + t];
+  for (int64_t i = full; i < any; ++i)
+    if (i + t < h) acc += c[i] * c[i + t];
+  return acc / (double)h;
+}
+
+// Mean over the nseg segments of lag_chain, added in segment order.  Segment j begins at (j / 2) n +
+// (j % 2) (n - h): the split chains of [chain][n] draws, or (nseg 1, h == n) one whole chain.
+__device__ __forceinline__ double lag_block(const double* buf, int nseg, int64_t n, int64_t h, int64_t t,
+                                            int64_t tbase) {
+  double asum = 0.0;
+  for (int j = 0; j < nseg; ++j)
+    asum += lag_chain(buf + (int64_t)(j >> 1) * n + (int64_t)(j & 1) * (n - h), h, t, tbase);
   return asum / (double)nseg;
+}
+
+// The estimator's tail, by one wavefront on split chains already centred in buf (segments as in
+// lag_block), varmu the variance of their means: W, V (R-hat = sqrt(V / W)) and, when full, the
+// effective sample size with its truncation lag T.  False when W == 0 (no within-chain variance).
+// a_first is the caller's lag_block(buf, M, n, h, lane, 0), the first 64 lags.
+__device__ __forceinline__ bool geyer_ess(const double* buf, int M, int64_t n, int64_t h, double varmu, int lane,
+                                          bool full, double a_first, double& W, double& V, double& ess, int64_t& T) {
+  int64_t tbase = 0;
+  double a = a_first;
+  const double a0 = __shfl(a, 0, DIAG_LANES);
+  W = a0 * (double)h / (double)(h - 1);
+  V = a0 + varmu;
+  if (W == 0.0) return false;
+  if (!full) return true;
+  // rho(t) for non-decreasing t: the next 64 lags are evaluated when t leaves the block in hand
+  auto rho = [&](int64_t t) -> double {
+    while (t >= tbase + DIAG_LANES) {
+      tbase += DIAG_LANES;
+      a = lag_block(buf, M, n, h, tbase + lane, tbase);
+    }
+    return 1.0 - (W - __shfl(a, (int)(t - tbase), DIAG_LANES)) / V;
+  };
+  // Geyer's initial positive sequence with the initial monotone sequence applied as pairs are
+  // passed: a pair (r[t-1], r[t]) enters the sum S = sum_{0..T} r once the pair after it has been
+  // evaluated, capped by the pair before it; the last pair evaluated, (r[T+1], r[T+2]), never does.
+  double even = 1.0, odd = rho(1);
+  int64_t t = 1;
+  double S = 0.0, pe = 0.0, po = 0.0;
+  bool have_prev = false, stored = true;
+  while (t < h - 3 && even + odd > 0.0) {
+    double le = even, lo = odd;
+    if (have_prev && le + lo > pe + po) le = lo = (pe + po) / 2.0;
+    S += le;
+    S += lo;
+    pe = le;
+    po = lo;
+    have_prev = true;
+    even = rho(t + 1);
+    odd = rho(t + 2);
+    stored = even + odd >= 0.0;
+    t += 2;
+  }
+  T = t - 2;
+  double r_last = stored ? even : 0.0;  // r[T+1]
+  if (even > 0.0) r_last = even;
+  double tau = -1.0 + 2.0 * S + r_last;
+  const double Mh = (double)M * (double)h;
+  tau = fmax(tau, 1.0 / log10(Mh));
+  ess = Mh / tau;
+  return true;
 }
 
 // One wavefront per series of the batch; seg [series][chain][n] (centred in place on the global path).
@@ -140,50 +197,12 @@ __global__ __launch_bounds__(DIAG_LANES) void diag_kernel(double* seg, int m, in
   __syncthreads();
   const double varmu = muss / (double)(M - 1);
 
-  int64_t tbase = 0;
-  double a = lag_block(buf, M, n, h, lane, 0);
-  const double a0 = __shfl(a, 0, DIAG_LANES);
-  const double W = a0 * (double)h / (double)(h - 1);
-  const double V = a0 + varmu;
-  if (W == 0.0) {
+  double W, V, ess;
+  int64_t T;
+  if (!geyer_ess(buf, M, n, h, varmu, lane, true, lag_block(buf, M, n, h, lane, 0), W, V, ess, T)) {
     if (lane < CLV_N_DIAG_STATS) o[lane] = NAN;
     return;
   }
-  // rho(t) for non-decreasing t: the next 64 lags are evaluated when t leaves the block in hand
-  auto rho = [&](int64_t t) -> double {
-    while (t >= tbase + DIAG_LANES) {
-      tbase += DIAG_LANES;
-      a = lag_block(buf, M, n, h, tbase + lane, tbase);
-    }
-    return 1.0 - (W - __shfl(a, (int)(t - tbase), DIAG_LANES)) / V;
-  };
-  // Geyer's initial positive sequence with the initial monotone sequence applied as pairs are
-  // passed: a pair (r[t-1], r[t]) enters the sum S = sum_{0..T} r once the pair after it has been
-  // evaluated, capped by the pair before it; the last pair evaluated, (r[T+1], r[T+2]), never does.
-  double even = 1.0, odd = rho(1);
-  int64_t t = 1;
-  double S = 0.0, pe = 0.0, po = 0.0;
-  bool have_prev = false, stored = true;
-  while (t < h - 3 && even + odd > 0.0) {
-    double le = even, lo = odd;
-    if (have_prev && le + lo > pe + po) le = lo = (pe + po) / 2.0;
-    S += le;
-    S += lo;
-    pe = le;
-    po = lo;
-    have_prev = true;
-    even = rho(t + 1);
-    odd = rho(t + 2);
-    stored = even + odd >= 0.0;
-    t += 2;
-  }
-  const int64_t T = t - 2;
-  double r_last = stored ? even : 0.0;  // r[T+1]
-  if (even > 0.0) r_last = even;
-  double tau = -1.0 + 2.0 * S + r_last;
-  const double Mh = (double)M * (double)h;
-  tau = fmax(tau, 1.0 / log10(Mh));
-  const double ess = Mh / tau;
   if (lane == 0) {
     o[CLV_DIAG_MEAN] = mean;
     o[CLV_DIAG_SD] = sd;
@@ -226,6 +245,352 @@ __global__ __launch_bounds__(DIAG_LANES) void acf_kernel(double* seg, int m, int
       if (t <= max_lag) oc[t] = a / a0;
     }
   }
+}
+
+// ---- Rank-normalised diagnostics (Vehtari et al. 2021 as ArviZ implements them; clvmcmc.h) ----
+// One workgroup of four wavefronts per series.  y stays where the gather put it (global memory,
+// read-only here); the workgroup owns two buffers, T (the time-ordered transformed split chains,
+// [2 m][h] contiguous) and P (the sorted pool), in LDS up to CLV_RANK_LDS_ELEMS values per series
+// and in global scratch beyond.  P is sorted by a bitonic network whose compare-exchanges all put the
+// smaller value at the lower index, so that a count that is no power of two needs no padding
+// (the missing tail behaves as +inf and never moves); a value's average rank is (lb + ub + 1) / 2
+// from its lower and upper bound in P.  Every transformed series then goes through the estimator
+// of diag_kernel: split-chain means by one wavefront per split chain (lane-strided, wave_sum),
+// the first 64 lags shared out the same way, then wavefront 0 alone runs geyer_ess (P, free by then,
+// holds the means and the lag terms).  Sums over all m n values are lane-strided over the 256
+// threads, wave_sum, then the four wavefronts in order.
+constexpr int RANK_THREADS = 256;
+constexpr int RANK_WAVES = RANK_THREADS / DIAG_LANES;
+constexpr int RANK_SC = 32;  // doubles of workgroup scalars in front of T and P
+static_assert((2 * CLV_RANK_LDS_ELEMS + RANK_SC) * sizeof(double) <= 64 * 1024, "the LDS path stays within 64 KiB");
+enum { SC_RED = 0, SC_HDI_W = 4, SC_HDI_I = 8, SC_PASS = 12 /* rhat, ess, lag */ };
+
+// Sum over the workgroup, the same bits in every thread (red: RANK_WAVES doubles of LDS).
+__device__ __forceinline__ double block_sum(double v, double* red) {
+  v = wave_sum(v);
+  __syncthreads();
+  if ((threadIdx.x & (DIAG_LANES - 1)) == 0) red[threadIdx.x / DIAG_LANES] = v;
+  __syncthreads();
+  double s = red[0];
+  for (int w = 1; w < RANK_WAVES; ++w) s += red[w];
+  return s;
+}
+
+// Whether flag is set in any thread of the workgroup (red as in block_sum).
+__device__ __forceinline__ bool block_any(int flag, double* red) {
+  return block_sum(__any(flag) ? 1.0 : 0.0, red) != 0.0;
+}
+
+// Ascending sort of p[0 .. cnt) by the whole workgroup; p is complete and visible on return.
+__device__ __forceinline__ void sort_block(double* p, int64_t cnt) {
+  __syncthreads();
+  int64_t half = 1;  // half the power of two that covers cnt: compare-exchanges per step
+  while (2 * half < cnt) half *= 2;
+  auto cmpx = [&](int64_t l, int64_t r) {
+    if (r < cnt) {
+      const double a = p[l], b = p[r];
+      if (b < a) {
+        p[l] = b;
+        p[r] = a;
+      }
+    }
+  };
+  for (int64_t k = 2; (k >> 1) < cnt; k <<= 1) {
+    const int64_t kh = k >> 1;  // two sorted runs of kh: mirror merge, then half-cleaners
+    for (int64_t t = threadIdx.x; t < half; t += RANK_THREADS) {
+      const int64_t off = t & (kh - 1), base = (t - off) * 2;
+      cmpx(base + off, base + k - 1 - off);
+    }
+    __syncthreads();
+    for (int64_t j = k >> 2; j > 0; j >>= 1) {
+      for (int64_t t = threadIdx.x; t < half; t += RANK_THREADS) {
+        const int64_t off = t & (j - 1), l = (t - off) * 2 + off;
+        cmpx(l, l + j);
+      }
+      __syncthreads();
+    }
+  }
+}
+
+__device__ __forceinline__ double median_sorted(const double* p, int64_t cnt) {
+  return (cnt & 1) ? p[cnt >> 1] : (p[(cnt >> 1) - 1] + p[cnt >> 1]) / 2.0;
+}
+
+// numpy's default (linear) quantile of the sorted p: virtual index q (cnt - 1), _lerp's two forms.
+__device__ __forceinline__ double quantile_sorted(const double* p, int64_t cnt, double q) {
+  const double vi = q * (double)(cnt - 1);
+  const double fl = floor(vi), t = vi - fl;
+  const int64_t lo = (int64_t)fl, hi = std::min<int64_t>(lo + 1, cnt - 1);
+  const double a = p[lo], b = p[hi], d = b - a;
+  return t >= 0.5 ? b - d * (1.0 - t) : a + d * t;
+}
+
+// Split chain j of the [chain][n] series g.
+__device__ __forceinline__ const double* split_chain(const double* g, int j, int64_t n, int64_t h) {
+  return g + (int64_t)(j >> 1) * n + (int64_t)(j & 1) * (n - h);
+}
+
+// dst[j h + i] = f(split chain j, draw i) over the 2 m split chains.
+template <class F>
+__device__ __forceinline__ void map_split(const double* g, double* dst, int M, int64_t n, int64_t h, F f) {
+  for (int j = 0; j < M; ++j) {
+    const double* c = split_chain(g, j, n, h);
+    for (int64_t i = threadIdx.x; i < h; i += RANK_THREADS) dst[(int64_t)j * h + i] = f(c[i]);
+  }
+}
+
+// T[j h + i] = Phi^-1((r - 3/8) / (S + 1/4)), r the average rank of f(y) in the sorted pool P of S
+// values; ranks and z also to ranks_out / z_out when given (clv_debug_zscale).
+template <class F>
+__device__ __forceinline__ void zscale_block(const double* g, const double* P, double* T, int M, int64_t n, int64_t h,
+                                             F f, double* ranks_out, double* z_out) {
+  const int64_t S = (int64_t)M * h;
+  const double den = (double)S + 0.25;
+  for (int j = 0; j < M; ++j) {
+    const double* c = split_chain(g, j, n, h);
+    for (int64_t i = threadIdx.x; i < h; i += RANK_THREADS) {
+      const double v = f(c[i]);
+      int64_t lo = 0, hi = S;
+      while (lo < hi) {  // lower bound: values below v
+        const int64_t mid = (lo + hi) >> 1;
+        if (P[mid] < v) lo = mid + 1; else hi = mid;
+      }
+      const int64_t lb = lo;
+      hi = S;
+      while (lo < hi) {  // upper bound: values not above v
+        const int64_t mid = (lo + hi) >> 1;
+        if (P[mid] <= v) lo = mid + 1; else hi = mid;
+      }
+      const double r = (double)(lb + lo + 1) / 2.0;
+      const double z = norm_ppf((r - 0.375) / den);
+      T[(int64_t)j * h + i] = z;
+      if (ranks_out) {
+        ranks_out[(int64_t)j * h + i] = r;
+        z_out[(int64_t)j * h + i] = z;
+      }
+    }
+  }
+}
+
+// The estimator on the transformed split chains in T (centred in place; mus: cap doubles of
+// scratch): res[0..2] = R-hat, ESS (when full), truncation lag, NaN when W == 0.  Called by the
+// whole workgroup; T may be rewritten on return.  Where the scratch has room (2 m x 65 doubles: 130
+// draws per chain) the first 64 lags, which is as far as nearly every series goes, are shared out: a
+// wavefront per split chain leaves its lag_chain terms in the scratch and wavefront 0 adds them in
+// chain order, lag_block's arithmetic.
+__device__ __forceinline__ void split_pass(double* T, double* mus, int64_t cap, int M, int64_t h, bool full,
+                                           double* res) {
+  const int lane = threadIdx.x & (DIAG_LANES - 1), wave = threadIdx.x / DIAG_LANES;
+  __syncthreads();
+  for (int j = wave; j < M; j += RANK_WAVES) {
+    double* c = T + (int64_t)j * h;
+    double a = 0.0;
+    for (int64_t i = lane; i < h; i += DIAG_LANES) a += c[i];
+    const double mu = wave_sum(a) / (double)h;
+    for (int64_t i = lane; i < h; i += DIAG_LANES) c[i] -= mu;
+    if (lane == 0) mus[j] = mu;
+  }
+  __syncthreads();
+  const bool shared_out = (int64_t)M * (DIAG_LANES + 1) <= cap;
+  double* part = mus + M;
+  if (shared_out) {
+    for (int j = wave; j < M; j += RANK_WAVES)
+      part[(int64_t)j * DIAG_LANES + lane] = lag_chain(T + (int64_t)j * h, h, lane, 0);
+    __syncthreads();
+  }
+  if (wave == 0) {
+    double a_first;
+    if (shared_out) {
+      double asum = 0.0;
+      for (int j = 0; j < M; ++j) asum += part[(int64_t)j * DIAG_LANES + lane];
+      a_first = asum / (double)M;
+    } else {
+      a_first = lag_block(T, M, 2 * h, h, lane, 0);
+    }
+    double musum = 0.0;
+    for (int j = 0; j < M; ++j) musum += mus[j];
+    const double mubar = musum / (double)M;
+    double muss = 0.0;
+    for (int j = 0; j < M; ++j) muss += (mus[j] - mubar) * (mus[j] - mubar);
+    double W = 0.0, V = 0.0, ess = NAN;
+    int64_t lag = 0;
+    const bool ok = geyer_ess(T, M, 2 * h, h, muss / (double)(M - 1), lane, full, a_first, W, V, ess, lag);
+    if (lane == 0) {
+      res[0] = ok ? sqrt(V / W) : NAN;
+      res[1] = ok ? ess : NAN;
+      res[2] = ok ? (double)lag : NAN;
+    }
+  }
+  __syncthreads();
+}
+
+// seg [series][chain][n] as gathered (read only); scratch [series][2 m n] on the global path.
+template <bool LDS>
+__global__ __launch_bounds__(RANK_THREADS) void rank_kernel(const double* seg, double* scratch, int m, int64_t n,
+                                                            int64_t nc, int64_t s0, int64_t hdi_k,
+                                                            double* out /*[n_series][CLV_N_RANK_STATS]*/) {
+  extern __shared__ double rank_smem[];
+  const int64_t sidx = blockIdx.x;
+  if (sidx >= nc) return;
+  const int tid = threadIdx.x;
+  const int M = 2 * m;
+  const int64_t N = (int64_t)m * n, h = n / 2, S = (int64_t)M * h;
+  const double* g = seg + sidx * N;
+  double* sc = rank_smem;
+  double* T = LDS ? rank_smem + RANK_SC : scratch + sidx * 2 * N;
+  double* P = T + N;
+  double* o = out + (s0 + sidx) * CLV_N_RANK_STATS;
+
+  double s = 0.0;
+  int bad = 0;
+  for (int64_t i = tid; i < N; i += RANK_THREADS) {
+    const double v = g[i];
+    P[i] = v;
+    s += v;
+    bad |= !std::isfinite(v);
+  }
+  if (block_any(bad, sc + SC_RED)) {
+    if (tid < CLV_N_RANK_STATS) o[tid] = NAN;
+    return;
+  }
+  const double mean = block_sum(s, sc + SC_RED) / (double)N;
+
+  // all m n values sorted: median, the two tail quantiles, the narrowest interval of hdi_k steps
+  sort_block(P, N);
+  const double median = median_sorted(P, N);
+  const double q05 = quantile_sorted(P, N, 0.05), q95 = quantile_sorted(P, N, 0.95);
+  double bw = INFINITY;
+  int64_t bi = INT64_MAX;
+  for (int64_t i = tid; i < N - hdi_k; i += RANK_THREADS) {
+    const double w = P[i + hdi_k] - P[i];
+    if (w < bw) {
+      bw = w;
+      bi = i;
+    }
+  }
+  for (int off = DIAG_LANES / 2; off > 0; off >>= 1) {
+    const double ow = __shfl_xor(bw, off, DIAG_LANES);
+    const long long oi = __shfl_xor((long long)bi, off, DIAG_LANES);
+    if (ow < bw || (ow == bw && oi < bi)) {
+      bw = ow;
+      bi = oi;
+    }
+  }
+  if ((tid & (DIAG_LANES - 1)) == 0) {
+    sc[SC_HDI_W + tid / DIAG_LANES] = bw;
+    sc[SC_HDI_I + tid / DIAG_LANES] = (double)bi;  // below 2^44: exact
+  }
+  __syncthreads();
+  bw = sc[SC_HDI_W];
+  double bid = sc[SC_HDI_I];
+  for (int w = 1; w < RANK_WAVES; ++w)
+    if (sc[SC_HDI_W + w] < bw || (sc[SC_HDI_W + w] == bw && sc[SC_HDI_I + w] < bid)) {
+      bw = sc[SC_HDI_W + w];
+      bid = sc[SC_HDI_I + w];
+    }
+  bi = bw < INFINITY ? (int64_t)bid : 0;  // (a width that overflowed: the first interval)
+  const double hdi_lo = P[bi], hdi_hi = P[bi + hdi_k];
+
+  // the pool of split values: all values unless an odd n drops the middle draws
+  auto ident = [](double v) { return v; };
+  if (S != N) {
+    __syncthreads();
+    map_split(g, P, M, n, h, ident);
+    sort_block(P, S);
+  }
+  const double med = median_sorted(P, S);
+
+  // bulk: z-scale of the split values
+  zscale_block(g, P, T, M, n, h, ident, nullptr, nullptr);
+  split_pass(T, P, N, M, h, true, sc + SC_PASS);
+  const double rhat_bulk = sc[SC_PASS], ess_bulk = sc[SC_PASS + 1], lag_bulk = sc[SC_PASS + 2];
+
+  // folded: z-scale of |split value - median of the pool|, R-hat only
+  auto fold = [med](double v) { return fabs(v - med); };
+  __syncthreads();
+  map_split(g, P, M, n, h, fold);
+  sort_block(P, S);
+  zscale_block(g, P, T, M, n, h, fold, nullptr, nullptr);
+  split_pass(T, P, N, M, h, false, sc + SC_PASS);
+  const double rhat_folded = sc[SC_PASS];
+
+  // tails: the indicators of y <= q05 and y <= q95
+  __syncthreads();
+  map_split(g, T, M, n, h, [q05](double v) { return v <= q05 ? 1.0 : 0.0; });
+  split_pass(T, P, N, M, h, true, sc + SC_PASS);
+  const double ess_q05 = sc[SC_PASS + 1];
+  __syncthreads();
+  map_split(g, T, M, n, h, [q95](double v) { return v <= q95 ? 1.0 : 0.0; });
+  split_pass(T, P, N, M, h, true, sc + SC_PASS);
+  const double ess_q95 = sc[SC_PASS + 1];
+
+  // sd: the squared deviations from the mean
+  __syncthreads();
+  map_split(g, T, M, n, h, [mean](double v) { return (v - mean) * (v - mean); });
+  split_pass(T, P, N, M, h, true, sc + SC_PASS);
+  const double ess_sd = sc[SC_PASS + 1];
+  double e2 = 0.0, e4 = 0.0;
+  for (int64_t i = tid; i < N; i += RANK_THREADS) {
+    const double d = g[i] - mean, c2 = d * d;
+    e2 += c2;
+    e4 += c2 * c2;
+  }
+  const double evar = block_sum(e2, sc + SC_RED) / (double)N;
+  const double m4 = block_sum(e4, sc + SC_RED) / (double)N;
+  const double varvar = (m4 - evar * evar) / ess_sd;
+
+  if (tid == 0) {
+    o[CLV_RANK_RHAT] = (rhat_bulk == rhat_bulk && rhat_folded == rhat_folded) ? fmax(rhat_bulk, rhat_folded) : NAN;
+    o[CLV_RANK_RHAT_BULK] = rhat_bulk;
+    o[CLV_RANK_RHAT_FOLDED] = rhat_folded;
+    o[CLV_RANK_ESS_BULK] = ess_bulk;
+    o[CLV_RANK_ESS_TAIL] = (ess_q05 == ess_q05 && ess_q95 == ess_q95) ? fmin(ess_q05, ess_q95) : NAN;
+    o[CLV_RANK_ESS_Q05] = ess_q05;
+    o[CLV_RANK_ESS_Q95] = ess_q95;
+    o[CLV_RANK_ESS_SD] = ess_sd;
+    o[CLV_RANK_MCSE_SD] = evar == 0.0 ? NAN : sqrt(varvar / evar / 4.0);
+    o[CLV_RANK_HDI_LO] = hdi_lo;
+    o[CLV_RANK_HDI_HI] = hdi_hi;
+    o[CLV_RANK_MEDIAN] = median;
+    o[CLV_RANK_LAG_BULK] = lag_bulk;
+  }
+}
+
+// clv_debug_zscale: the sort and the rank transform of rank_kernel alone, ranks and z written out.
+template <bool LDS>
+__global__ __launch_bounds__(RANK_THREADS) void zscale_kernel(const double* seg, double* scratch, int m, int64_t n,
+                                                              int64_t nc, int64_t s0, int folded, double* ranks_out,
+                                                              double* z_out /*[n_series][2 m][h] each*/) {
+  extern __shared__ double rank_smem[];
+  const int64_t sidx = blockIdx.x;
+  if (sidx >= nc) return;
+  const int tid = threadIdx.x;
+  const int M = 2 * m;
+  const int64_t N = (int64_t)m * n, h = n / 2, S = (int64_t)M * h;
+  const double* g = seg + sidx * N;
+  double* T = LDS ? rank_smem + RANK_SC : scratch + sidx * 2 * N;
+  double* P = T + N;
+  double* ro = ranks_out + (s0 + sidx) * S;
+  double* zo = z_out + (s0 + sidx) * S;
+  int bad = 0;
+  for (int64_t i = tid; i < N; i += RANK_THREADS) bad |= !std::isfinite(g[i]);
+  if (block_any(bad, rank_smem + SC_RED)) {
+    for (int64_t i = tid; i < S; i += RANK_THREADS) ro[i] = zo[i] = NAN;
+    return;
+  }
+  auto ident = [](double v) { return v; };
+  map_split(g, P, M, n, h, ident);
+  sort_block(P, S);
+  if (!folded) {
+    zscale_block(g, P, T, M, n, h, ident, ro, zo);
+    return;
+  }
+  const double med = median_sorted(P, S);
+  auto fold = [med](double v) { return fabs(v - med); };
+  __syncthreads();
+  map_split(g, P, M, n, h, fold);
+  sort_block(P, S);
+  zscale_block(g, P, T, M, n, h, fold, ro, zo);
 }
 
 int check_series(int32_t n_chains, int64_t n_draws, int64_t n_series) {
@@ -282,9 +647,130 @@ int upload(const double* host, size_t count, DevBuf& buf) {
   return CLV_OK;
 }
 
+int check_hdi_prob(double hdi_prob) {
+  if (!(hdi_prob > 0.0 && hdi_prob < 1.0)) return fail(CLV_EINVAL, "hdi_prob must be in (0, 1)");
+  return CLV_OK;
+}
+
+size_t rank_lds_bytes(bool lds, int64_t mn) { return sizeof(double) * (size_t)(RANK_SC + (lds ? 2 * mn : 0)); }
+
+// d_in: device [chain][draw][n_series]; host_out [n_series][CLV_N_RANK_STATS].
+int rank_dev(const double* d_in, int32_t m, int64_t n, int64_t n_series, int period, uint32_t log_mask,
+             double hdi_prob, double* host_out, hipStream_t st) {
+  const int64_t mn = (int64_t)m * n;
+  const int64_t per_batch = batch_series(mn, n_series);
+  const int64_t hdi_k = std::min<int64_t>((int64_t)std::floor(hdi_prob * (double)mn), mn - 1);
+  const bool lds = mn <= CLV_RANK_LDS_ELEMS;
+  DevBuf bseg, bscr, bout;
+  CLV_HIP(hipMalloc(&bseg.p, sizeof(double) * (size_t)(per_batch * mn)));
+  if (!lds) CLV_HIP(hipMalloc(&bscr.p, sizeof(double) * (size_t)(2 * per_batch * mn)));
+  CLV_HIP(hipMalloc(&bout.p, sizeof(double) * (size_t)n_series * CLV_N_RANK_STATS));
+  for (int64_t s0 = 0; s0 < n_series; s0 += per_batch) {
+    const int64_t nc = std::min<int64_t>(per_batch, n_series - s0);
+    launch_gather(d_in, mn, n_series, s0, nc, period, log_mask, bseg.as<double>(), st);
+    CLV_HIP(hipGetLastError());
+    if (lds)
+      hipLaunchKernelGGL(rank_kernel<true>, dim3((unsigned)nc), dim3(RANK_THREADS), rank_lds_bytes(true, mn), st,
+                         bseg.as<double>(), (double*)nullptr, (int)m, n, nc, s0, hdi_k, bout.as<double>());
+    else
+      hipLaunchKernelGGL(rank_kernel<false>, dim3((unsigned)nc), dim3(RANK_THREADS), rank_lds_bytes(false, mn), st,
+                         bseg.as<double>(), bscr.as<double>(), (int)m, n, nc, s0, hdi_k, bout.as<double>());
+    CLV_HIP(hipGetLastError());
+  }
+  CLV_HIP(hipMemcpyAsync(host_out, bout.p, sizeof(double) * (size_t)n_series * CLV_N_RANK_STATS,
+                         hipMemcpyDeviceToHost, st));
+  CLV_HIP(hipStreamSynchronize(st));
+  return CLV_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int clv_rank_diagnostics(int32_t device, const double* series, int32_t n_chains, int64_t n_draws, int64_t n_series,
+                         int32_t period, uint32_t log_mask, double hdi_prob, double* out) {
+  if (!series || !out) return fail(CLV_EINVAL, "null argument");
+  int rc = check_series(n_chains, n_draws, n_series);
+  if (rc) return rc;
+  if (period < 1 || period > 32) return fail(CLV_EINVAL, "period must be in 1..32");
+  rc = check_hdi_prob(hdi_prob);
+  if (rc) return rc;
+  DeviceScope ds(device);
+  DevBuf bin;
+  rc = upload(series, (size_t)n_chains * n_draws * n_series, bin);
+  if (rc) return rc;
+  return rank_dev(bin.as<double>(), n_chains, n_draws, n_series, period, log_mask, hdi_prob, out, nullptr);
+}
+
+int clv_rank_diagnostics_sampler(clv_sampler* s, uint32_t log_mask, double hdi_prob, double* level1_out,
+                                 double* level2_out) {
+  if (!s) return fail(CLV_EINVAL, "null sampler");
+  if (!level1_out && !level2_out) return fail(CLV_EINVAL, "null argument (no output asked for)");
+  int rc = check_hdi_prob(hdi_prob);
+  if (rc) return rc;
+  const Geometry& g = s->g;
+  if (level1_out) {
+    const double* l1;
+    int64_t nd;
+    int32_t w;
+    rc = sampler_l1(s, &l1, &nd, &w);
+    if (rc) return rc;
+    rc = check_series(g.n_chains, g.n_draws, g.n * w);
+    if (rc) return rc;
+    rc = rank_dev(l1, g.n_chains, g.n_draws, g.n * w, w, log_mask, hdi_prob, level1_out, s->stream);
+    if (rc) return rc;
+  }
+  if (level2_out) {
+    int64_t stored = 0;
+    if (s->sweeps_done > g.burnin) stored = (s->sweeps_done - 1 - g.burnin) / g.thin + 1;
+    if (!s->d_level2 || std::min<int64_t>(stored, g.n_draws) < (int64_t)g.n_draws)
+      return fail(CLV_ESTATE, "the run has not stored all of its draws yet");
+    rc = check_series(g.n_chains, g.n_draws, g.l2w);
+    if (rc) return rc;
+    CLV_HIP(hipSetDevice(s->device));
+    CLV_HIP(hipStreamSynchronize(s->stream));
+    rc = persist_flush(s);  // the last level-2 record may still be pending
+    if (rc) return rc;
+    rc = rank_dev(s->d_level2, g.n_chains, g.n_draws, g.l2w, 1, 0u, hdi_prob, level2_out, s->stream);
+    if (rc) return rc;
+  }
+  return CLV_OK;
+}
+
+int clv_debug_zscale(int32_t device, const double* series, int32_t n_chains, int64_t n_draws, int64_t n_series,
+                     int32_t folded, double* ranks_out, double* z_out) {
+  if (!series || !ranks_out || !z_out) return fail(CLV_EINVAL, "null argument");
+  int rc = check_series(n_chains, n_draws, n_series);
+  if (rc) return rc;
+  DeviceScope ds(device);
+  DevBuf bin, bseg, bscr, br, bz;
+  rc = upload(series, (size_t)n_chains * n_draws * n_series, bin);
+  if (rc) return rc;
+  const int64_t mn = (int64_t)n_chains * n_draws, S = 2 * (int64_t)n_chains * (n_draws / 2);
+  const int64_t per_batch = batch_series(mn, n_series);
+  const bool lds = mn <= CLV_RANK_LDS_ELEMS;
+  CLV_HIP(hipMalloc(&bseg.p, sizeof(double) * (size_t)(per_batch * mn)));
+  if (!lds) CLV_HIP(hipMalloc(&bscr.p, sizeof(double) * (size_t)(2 * per_batch * mn)));
+  CLV_HIP(hipMalloc(&br.p, sizeof(double) * (size_t)(n_series * S)));
+  CLV_HIP(hipMalloc(&bz.p, sizeof(double) * (size_t)(n_series * S)));
+  for (int64_t s0 = 0; s0 < n_series; s0 += per_batch) {
+    const int64_t nc = std::min<int64_t>(per_batch, n_series - s0);
+    launch_gather(bin.as<double>(), mn, n_series, s0, nc, 1, 0u, bseg.as<double>(), nullptr);
+    CLV_HIP(hipGetLastError());
+    if (lds)
+      hipLaunchKernelGGL(zscale_kernel<true>, dim3((unsigned)nc), dim3(RANK_THREADS), rank_lds_bytes(true, mn),
+                         nullptr, bseg.as<double>(), (double*)nullptr, (int)n_chains, n_draws, nc, s0, (int)folded,
+                         br.as<double>(), bz.as<double>());
+    else
+      hipLaunchKernelGGL(zscale_kernel<false>, dim3((unsigned)nc), dim3(RANK_THREADS), rank_lds_bytes(false, mn),
+                         nullptr, bseg.as<double>(), bscr.as<double>(), (int)n_chains, n_draws, nc, s0, (int)folded,
+                         br.as<double>(), bz.as<double>());
+    CLV_HIP(hipGetLastError());
+  }
+  CLV_HIP(hipMemcpy(ranks_out, br.p, sizeof(double) * (size_t)(n_series * S), hipMemcpyDeviceToHost));
+  CLV_HIP(hipMemcpy(z_out, bz.p, sizeof(double) * (size_t)(n_series * S), hipMemcpyDeviceToHost));
+  return CLV_OK;
+}
 
 int clv_diagnostics(int32_t device, const double* series, int32_t n_chains, int64_t n_draws, int64_t n_series,
                     int32_t period, uint32_t log_mask, double* out) {

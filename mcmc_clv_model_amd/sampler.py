@@ -403,12 +403,17 @@ class HipSampler:
         return out
 
     def diagnostics(self, log_columns=("lambda", "mu"), level1: bool = True, level2: bool = True,
-                    param_names=None) -> dict:
+                    param_names=None, rank: bool = False, hdi_prob: float = 0.94) -> dict:
         """clv_diagnostics_sampler: convergence diagnostics (split R-hat, ESS, MCSE, truncation lag;
         analysis.level1_diagnostics / level2_diagnostics) of the draws this sampler holds in HBM,
         without the host round trip — {"level_1": DataFrame per customer (full sink only),
-        "level_2": DataFrame per level-2 parameter}, the same bits as the host-array route."""
+        "level_2": DataFrame per level-2 parameter}, the same bits as the host-array route.
+        ``rank``: also the rank-normalised statistics (clv_rank_diagnostics_sampler) —
+        "level_1_rank" (analysis.level1_rank_diagnostics), "level_2_rank" and "level_2_summary"
+        (analysis.level2_rank_diagnostics / level2_summary, az.summary's nine columns)."""
         from . import analysis as A
+        if rank:
+            hdi_prob = A._check_hdi_prob(hdi_prob)
         w = self.D + 2
         mask = A.level1_log_mask(log_columns, w)
         o1 = np.empty((self.n * w, len(_lib.DIAG_STATS)), np.float64) if level1 else None
@@ -419,6 +424,15 @@ class HipSampler:
             out["level_1"] = A.level1_diagnostics_frame(o1, self.n, w, mask)
         if level2:
             out["level_2"] = A.level2_diagnostics_frame(o2, param_names)
+        if rank:
+            r1 = np.empty((self.n * w, len(_lib.RANK_STATS)), np.float64) if level1 else None
+            r2 = np.empty((len(o2), len(_lib.RANK_STATS)), np.float64) if level2 else None
+            check(self._L.clv_rank_diagnostics_sampler(self.h, mask, hdi_prob, dptr(r1), dptr(r2)))
+            if level1:
+                out["level_1_rank"] = A.level1_rank_diagnostics_frame(r1, self.n, w, mask)
+            if level2:
+                out["level_2_rank"] = A.level2_rank_diagnostics_frame(r2, param_names)
+                out["level_2_summary"] = A.level2_summary_frame(o2, r2, param_names, hdi_prob)
         return out
 
     def chain_total_loglik(self) -> float:
@@ -534,17 +548,20 @@ def _assemble(D: int, chains: int, l1, l2, ll, sums, k: int, n_draws: int, draw_
 def fit(p: Problem, *, mcmc: int, burnin: int, thin: int, chains: int, seed, trace: int, n_mh_steps: int,
         draw_sink: str = "full", rng: str = "philox", device: int = -1, replay_tape=None,
         replay_sweeps: Optional[int] = None, devices: Optional[Sequence[int]] = None, shard: str = "auto",
-        exchange: str = "auto", diagnostics: bool = False) -> dict:
+        exchange: str = "auto", diagnostics=False) -> dict:
     """Run all chains of one problem in one batched launch sequence and return the reference's
     output layout (bi:499-504).  ``devices`` (two or more): the run is spread over those devices
     in this process (:func:`fit_multi`).  ``diagnostics``: also out["diagnostics"] = {"level_1",
     "level_2"} convergence tables (analysis.level1_diagnostics / level2_diagnostics; full sink
     only), from the sampler's draws in HBM on one device, from the returned arrays on devices[0]
-    otherwise."""
+    otherwise; ``diagnostics="rank"`` adds "level_1_rank", "level_2_rank" and "level_2_summary"
+    (analysis.level1_rank_diagnostics / level2_rank_diagnostics / level2_summary)."""
     if chains < 1:
         raise ValueError("chains must be >= 1")
     if thin < 1:
         raise ValueError("thin must be >= 1")
+    if isinstance(diagnostics, str) and diagnostics != "rank":
+        raise ValueError(f"diagnostics must be False, True or 'rank' (got {diagnostics!r})")
     if diagnostics and draw_sink != "full":
         raise ValueError("diagnostics=True needs draw_sink='full' (analysis.summary_rhat serves a summary run)")
     if devices is not None:
@@ -561,6 +578,10 @@ def fit(p: Problem, *, mcmc: int, burnin: int, thin: int, chains: int, seed, tra
                 from . import analysis as A
                 out["diagnostics"] = dict(level_1=A.level1_diagnostics(out, device=devices[0]),
                                           level_2=A.level2_diagnostics(out, device=devices[0]))
+                if diagnostics == "rank":
+                    out["diagnostics"].update(level_1_rank=A.level1_rank_diagnostics(out, device=devices[0]),
+                                              level_2_rank=A.level2_rank_diagnostics(out, device=devices[0]),
+                                              level_2_summary=A.level2_summary(out, device=devices[0]))
             return out
         device = devices[0]
     s = HipSampler(p, mcmc=mcmc, burnin=burnin, thin=thin, chains=chains, seed=resolve_seed(seed),
@@ -581,7 +602,7 @@ def fit(p: Problem, *, mcmc: int, burnin: int, thin: int, chains: int, seed, tra
         out = _assemble(p.D, chains, l1, l2, ll, sums, k, s.n_draws, draw_sink,
                         lambda: s.level1_summary(_lib.SUMMARY_MU_CAP))
         if diagnostics:
-            out["diagnostics"] = s.diagnostics()
+            out["diagnostics"] = s.diagnostics(rank=diagnostics == "rank")
         return out
     finally:
         s.close()

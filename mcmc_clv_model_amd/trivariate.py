@@ -20,7 +20,7 @@ def mcmc_draw_parameters_rfm_m(cal_cbs, covariates: Optional[Sequence[str]] = No
                                draw_sink: str = "full", rng: str = "philox", device: int = -1,
                                replay_tape=None, replay_sweeps: Optional[int] = None,
                                devices: Optional[Sequence[int]] = None, shard: str = "auto", exchange: str = "auto",
-                               diagnostics: bool = False):
+                               diagnostics=False):
     """3-dimensional HB Pareto/NBD + spend sampler (trivariate/mcmc.py:580).
 
     Returns {"level_1": [(n_draws, N, 5) per chain: lambda, mu, tau, z, eta],
