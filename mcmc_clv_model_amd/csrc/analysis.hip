@@ -10,8 +10,10 @@
 //   clv_chain_total_loglik*  analysis_bi_helpers.py:52-72
 //
 // Random numbers: Philox4x32-10 keyed by the caller's seed, counter (customer or week, flat draw
-// index, slot, stream); the reference draws from one numpy Generator, so parity is distributional
-// (tests/test_gpu_analysis.py).  Statistics are exact: the means sum the draws in the reference's
+// index, slot, stream); the reference draws from one numpy Generator, so parity with IT is
+// distributional (tests/test_gpu_analysis.py), while every draw is held value by value to a float64
+// model of this counter layout (tests/analysis_stream_ref.py, tests/test_gpu_analysis_stream.py;
+// DESIGN.md section 2).  Statistics are exact: the means sum the draws in the reference's
 // order (numpy's axis-0 reduction is sequential over draws) and the percentiles apply numpy's
 // 'linear' rule to exactly sorted draws.
 #include <hip/hip_runtime.h>

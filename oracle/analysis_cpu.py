@@ -19,16 +19,21 @@ import numpy as np
 from scipy.special import gammaln
 
 
+def future_tau_star(T_cal, draw, T_star):
+    """bi:538-540 (tri:717-722 is the same): the time a customer stays active in (T_cal, T_cal + T_star]."""
+    tau, z = draw[:, 2], draw[:, 3] > 0.5
+    ts = np.full_like(T_cal, T_star, dtype=float)
+    ts[~z] = np.clip(tau[~z] - T_cal[~z], 0.0, T_star)
+    return ts
+
+
 def draw_future_transactions_bi(cbs, draws, T_star=39.0, seed=None):
     rng = np.random.default_rng(seed)
     T_cal = cbs["T_cal"].to_numpy()
     out = []
     for chain in draws["level_1"]:
         for draw in chain:
-            lam, tau, z = draw[:, 0], draw[:, 2], draw[:, 3] > 0.5
-            ts = np.full_like(T_cal, T_star, dtype=float)
-            ts[~z] = np.clip(tau[~z] - T_cal[~z], 0.0, T_star)
-            out.append(rng.poisson(lam=lam * ts))
+            out.append(rng.poisson(lam=draw[:, 0] * future_tau_star(T_cal, draw, T_star)))
     return np.array(out)
 
 

@@ -22,6 +22,8 @@ Fixtures written:
   elog_abe.npz               row f4: cdnow_abeElog.csv and the reference elog2cbs outputs (W with
                              hold-out, D without, W without a sales column)
   generator_bi.npz           row f4: a 20,000-customer sample of the reference's generate_pareto_abe
+  generator_replay.npz       the reference's generate_pareto_abe fed the generator's Philox variates
+                             (tests/analysis_stream_ref.py) through a stub Generator: three small cases
 
 Usage:  PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_goldens.py [--skip-envelope]
 """
@@ -586,6 +588,83 @@ def write_dataprep(rbi):
     print("dataprep", {k: v.shape for k, v in out.items() if k.endswith("_x")}, len(cbs), len(el))
 
 
+# ---------------------------------------------------------------------------------------------
+class PhiloxGeneratorStub:
+    """Stands in for numpy's Generator inside the reference's generate_pareto_abe: hands out the
+    variates of tests/analysis_stream_ref.py (the generator's documented Philox layout) in the
+    reference's call order — uniform (covariates), multivariate_normal (heterogeneity), exponential
+    with an array scale (lifetimes), then one scalar exponential per inter-purchase gap, customer by
+    customer.  A new customer is recognised by a new scale (1 / lambda_i; every customer draws at
+    least one gap because tau > 0)."""
+
+    def __init__(self, seed):
+        from tests import analysis_stream_ref as A
+        self.A, self.seed = A, seed
+        self.n = None
+        self.cust, self.gap, self.scale, self.buf = -1, 0, None, None
+
+    def uniform(self, low, high, size):
+        n, km1 = size
+        assert (low, high) == (-1.0, 1.0)
+        return self.A.gen_covariates(n, km1 + 1, self.seed)[:, 1:]
+
+    def multivariate_normal(self, mean, cov, size):
+        assert not np.any(mean)
+        return self.A.gen_mvn(size, cov, self.seed)
+
+    def exponential(self, scale):
+        if np.ndim(scale) == 1:
+            self.n = len(scale)
+            return scale * self.A.gen_lifetime_exp(self.n, self.seed)
+        if scale != self.scale:
+            self.cust, self.gap, self.scale = self.cust + 1, 0, scale
+            self.buf = np.zeros(0)
+        if self.gap >= self.buf.size:
+            self.buf = np.concatenate([self.buf, self.A.gen_gap_exps([self.cust], self.seed, self.buf.size, 64)[0]])
+        self.gap += 1
+        return scale * float(self.buf[self.gap - 1])
+
+
+def write_generator_replay(rbi):
+    """The reference's generate_pareto_abe driven by the model's Philox variates (tests/
+    analysis_stream_ref.py): inputs, seed, and the reference's CBS columns and event log — what
+    tests/test_analysis_stream_cpu.py replays the model's event rules against."""
+    from unittest import mock
+    from tests import analysis_stream_ref as A
+    rng = np.random.default_rng(20261019)
+    gamma = np.array([[0.6, 0.1], [0.1, 0.9]])
+    cases = {
+        "scalar": dict(n=64, T_cal=32.0, T_star=[20.0, 32.0], beta=np.array([[-1.2, -2.5], [0.3, -0.2]]),
+                       covars=None, seed=A.SEED_LO),
+        "percust": dict(n=48, T_cal=rng.choice([8.0, 20.5, 32.0], size=48), T_star=[32.0, 0.0, 5.5],
+                        beta=np.array([[-1.0, -2.8], [0.4, 0.1], [-0.3, 0.5]]),
+                        covars=rng.uniform(-1.0, 1.0, size=(48, 2)), seed=A.SEED_HI),
+        "k1": dict(n=40, T_cal=32.0, T_star=[32.0], beta=np.array([[-0.5, -3.0]]), covars=None, seed=A.SEED_HI),
+    }
+    out = dict(cases=np.array(list(cases), dtype="U16"), gamma=gamma)
+    for name, c in cases.items():
+        stubs = []
+
+        def factory(seed=None):
+            stubs.append(PhiloxGeneratorStub(seed))
+            return stubs[-1]
+
+        with mock.patch.object(np.random, "default_rng", factory):
+            cbs, elog = rbi.generate_pareto_abe(c["n"], c["T_cal"], c["T_star"], c["beta"], gamma, covars=c["covars"],
+                                                seed=c["seed"])
+        assert len(stubs) == 1 and stubs[0].cust == c["n"] - 1, "the stub lost track of the customers"
+        p = name + "_"
+        out.update({p + "n": c["n"], p + "T_cal": np.asarray(c["T_cal"], dtype=np.float64), p + "seed": np.uint64(c["seed"]),
+                    p + "T_star": np.asarray(c["T_star"], dtype=np.float64), p + "beta": c["beta"],
+                    p + "covars": np.zeros((0, 0)) if c["covars"] is None else c["covars"],
+                    p + "elog_cust": elog["cust"].to_numpy(np.float64), p + "elog_t": elog["t"].to_numpy(np.float64),
+                    p + "cbs_columns": np.array(list(cbs.columns), dtype="U16")})
+        for col in cbs.columns:
+            out[p + "cbs_" + col] = cbs[col].to_numpy()
+        print("generator_replay", name, len(cbs), len(elog), list(cbs.columns))
+    np.savez_compressed(os.path.join(HERE, "generator_replay.npz"), **out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--skip-envelope", action="store_true")
@@ -597,7 +676,7 @@ def main():
     steps = [("pin", lambda: pin_oracle(rbi, rtri)), ("data", write_data), ("philox", write_philox_kat),
              ("formulas", lambda: write_formulas(rbi, rtri)), ("replay", lambda: write_replay(rbi, rtri, set(a.replay_names.split(",")) if a.replay_names else None)),
              ("published", write_published), ("analysis", lambda: write_analysis(rbi, rtri)),
-             ("dataprep", lambda: write_dataprep(rbi))]
+             ("dataprep", lambda: write_dataprep(rbi)), ("generator_replay", lambda: write_generator_replay(rbi))]
     if not a.skip_envelope:
         steps.append(("envelope", write_envelope))
         steps.append(("envelope_full", lambda: write_envelope_full(rbi, rtri)))
