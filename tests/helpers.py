@@ -26,6 +26,13 @@ def cdnow(name: str = "abe", n: int | None = None) -> pd.DataFrame:
     return df
 
 
+def cdnow_tiled(n: int) -> pd.DataFrame:
+    """cdnow("full") rows taken cyclically up to n, index reset: a deterministic CBS of any size that
+    keeps the real x = 0 / t_x = 0 / t_x near T rows."""
+    df = cdnow("full")
+    return df.iloc[np.arange(n) % len(df)].copy().reset_index(drop=True)
+
+
 def with_covariates(df: pd.DataFrame, n_cov: int, seed: int = 4242) -> pd.DataFrame:
     """c1..c{n_cov}: U(-1,1) covariate columns (the c4/c5 covariate model) added to a CBS."""
     df = df.copy()

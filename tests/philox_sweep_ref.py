@@ -259,10 +259,13 @@ class ModelProblem:
         return sweep_level1(self.x, self.t_x, self.T_cal, self.X, lam, mu, beta, Sigma, var,
                             log_s=self.log_s, omega2=self.omega2, **kw)
 
-    def level2(self, seed, chain, hsweep, Y, hsweep_of_variates=None, beta_slot_shift=0):
+    def level2(self, seed, chain, hsweep, Y, hsweep_of_variates=None, beta_slot_shift=0, rows=None):
+        """``rows`` (power checks only): the customers whose rows of X and Y enter the statistics; the
+        variates keep the whole problem's nu_n."""
         hv = hyper_variates(seed, chain, hsweep if hsweep_of_variates is None else hsweep_of_variates,
                             self.D, self.K, self.nu_n, beta_slot_shift)
-        return level2_draw(self.X, Y, self.hyper, *hv)
+        X = self.X if rows is None else self.X[rows]
+        return level2_draw(X, Y if rows is None else Y[rows], self.hyper, *hv)
 
 
 # The GPU module's cases (ISSUE table): name -> D, covariates, data, N, S, chains, chain_first, seed,
@@ -283,10 +286,90 @@ CASES = {
 }
 
 
+BLOCK = 256            # customers per workgroup (CLV_BLOCK)
+NT = 256               # lanes of the level-2 workgroup: it holds units u, u + NT, then strides by NT
+
+
+def _instance_case(D, K):
+    """One case per compiled (D, K) instance.  N = 257 / 512 / 256 by (K - 1) % 3 — a last block of one
+    active lane, no partly filled block, one single full block — so each occurs for K < 6 and K >= 6
+    (covariates in registers / in LDS) for both D.  S = 6: one full MH chunk of 4 and a partial one."""
+    n = (257, 512, 256)[(K - 1) % 3]
+    return dict(D=D, covs=[f"c{k}" for k in range(1, K)], data=("abe", n, K - 1), S=6, chains=2, chain_first=K % 2,
+                seed=1000 + 10 * D + K, burnin=0, mcmc=3, thin=1, drive=[("run", 3)])
+
+
+INSTANCE_CASES = {f"{'bi' if D == 2 else 'tri'}{K}": _instance_case(D, K) for D in (2, 3) for K in range(1, 10)}
+
+# Coverage events the model's free run of each instance case produces (chains x 3 sweeps; recorded and
+# asserted by test_philox_sweep_cpu.test_instance_coverage_table_is_what_the_model_produces): an x = 0
+# customer, a churned tau in the first / last 5% of [t_x, T], a proposal at the +-70 clip, a proposal
+# above the mu cap.  The GPU module asserts exactly these per case.  Every case has x0, near_tx and
+# near_T.  The trivariate cases propose sweep 1 with gamma_00's variances (4 + K), so all of them hit
+# the clip (6..117 lanes) and the cap (337..967 lanes).  The bivariate cases propose with a drawn
+# Sigma: 257..512 customers x 2 chains x 3 sweeps x 6 steps never reach the +-70 clip, and K = 1..4
+# never propose above the mu cap either (K = 5..9: 1 or 2 lanes; bi_k1 of CASES: 19) — the clip's code is shared and the
+# trivariate cases cover it.
+COVERAGE_EVENTS = ("x0", "near_tx", "near_T", "clip", "cap")
+_EDGES = ("x0", "near_tx", "near_T")
+INSTANCE_COVERAGE = {**{f"bi{K}": _EDGES for K in (1, 2, 3, 4)},
+                     **{f"bi{K}": _EDGES + ("cap",) for K in (5, 6, 7, 8, 9)},
+                     **{f"tri{K}": COVERAGE_EVENTS for K in range(1, 10)}}
+
+
+def grid_geometry(case):
+    """(blocks, blocks per unit, units per rank, global units) of a world-size-1 run: the library's
+    plan rule (clv_create) restated, so a case can assert the geometry it is meant to reach."""
+    nb = -(-case["data"][1] // BLOCK)
+    bpu = case["blocks_per_unit"]
+    if not bpu:  # clv_default_blocks_per_unit: at most 2 NT units
+        bpu = 1
+        while -(-nb // bpu) > 2 * NT:
+            bpu *= 2
+    units = -(-nb // bpu)
+    return nb, bpu, units, units
+
+
+def _grid_case(D, K, n, chains, bpu, modes, seed, geometry, drop):
+    return dict(D=D, covs=[f"c{k}" for k in range(1, K)], data=("tiled", n, K - 1), S=4, chains=chains, chain_first=0,
+                seed=seed, burnin=0, mcmc=2, thin=1, drive=[("run", 2)], blocks_per_unit=bpu, modes=modes,
+                geometry=geometry, drop=drop)
+
+
+# The level-2 reduction paths and large customer indices.  modes: kernel -> the persistent flag asserted;
+# geometry: (blocks, blocks per unit, units per rank, global units) asserted before the run; drop: the
+# customer ranges [lo, hi) left out of the level-2 model and the log-likelihood mean by the power
+# checks (blocks 0, 256 and the last; or the whole last unit).
+_N300, _N600, _N41 = 299 * BLOCK + 1, 599 * BLOCK + 1, 10300
+_BLOCKS_300 = {"block 0": (0, BLOCK), "block 256": (256 * BLOCK, 257 * BLOCK), "last block": (299 * BLOCK, _N300)}
+GRID_CASES = {
+    # persistent: lanes 0..43 of the level-2 workgroup hold two blocks, level-2 workgroup alone on its
+    # CU, a last block of one lane; fused tail: hyper_sum_units' two-unit branch, second unit in 44 lanes
+    "g_bi1_300": _grid_case(2, 1, _N300, 1, 0, dict(default=True, launch_per_sweep=False), 3101,
+                            (300, 1, 300, 300), _BLOCKS_300),
+    # NS = 19 > 16: hyper_variates, then the strided loop (two trips)
+    "g_tri4_300": _grid_case(3, 4, _N300, 1, 0, dict(default=True, launch_per_sweep=False), 3102,
+                             (300, 1, 300, 300), _BLOCKS_300),
+    # 600 units > 2 NT: the strided loop with NS <= 16, three trips (blocks_per_unit = 1 set explicitly)
+    "g_bi2_600u": _grid_case(2, 2, _N600, 1, 1, dict(default=False), 3103, (600, 1, 600, 600),
+                             {"block 0": (0, BLOCK), "block 256": (256 * BLOCK, 257 * BLOCK),
+                              "block 512": (512 * BLOCK, 513 * BLOCK), "last block": (599 * BLOCK, _N600)}),
+    # unit arrival counters; unit sums by the tail loop only / one batch of 8 / two batches; a last unit
+    # of 1 / 1 / 9 blocks over zero padding; two chains' counters side by side
+    "g_bi5_u2": _grid_case(2, 5, _N41, 2, 2, dict(default=False), 3104, (41, 2, 21, 21), {"last unit": (20 * 2 * BLOCK, _N41)}),
+    "g_bi5_u8": _grid_case(2, 5, _N41, 2, 8, dict(default=False), 3105, (41, 8, 6, 6), {"last unit": (5 * 8 * BLOCK, _N41)}),
+    "g_bi5_u16": _grid_case(2, 5, _N41, 2, 16, dict(default=False), 3106, (41, 16, 3, 3), {"last unit": (2 * 16 * BLOCK, _N41)}),
+    # the same through the NS > 16 branch (NS = 34, covariates in LDS)
+    "g_tri9_u16": _grid_case(3, 9, _N41, 2, 16, dict(default=False), 3107, (41, 16, 3, 3), {"last unit": (2 * 16 * BLOCK, _N41)}),
+}
+GRID_RUNS = [(n, m) for n, c in GRID_CASES.items() for m in c["modes"]]
+ALL_CASES = {**CASES, **INSTANCE_CASES, **GRID_CASES}
+
+
 def case_frame(case):
-    from tests.helpers import cdnow, with_covariates
+    from tests.helpers import cdnow, cdnow_tiled, with_covariates
     name, n, n_cov = case["data"]
-    df = cdnow(name, n)
+    df = cdnow_tiled(n) if name == "tiled" else cdnow(name, n)
     return with_covariates(df, n_cov) if n_cov else df
 
 

@@ -47,6 +47,27 @@ Power: the same device outputs are compared again with one thing wrong at a time
 inputs (variates of sweep s + 1; chain key + 1; t_l and t_m swapped; the tau variate's branches
 swapped; the bivariate level-2 draw's variates of sweep s instead of s + 1; the beta normals' slots
 shifted by one); each must fail for more than half the customers, or the level-2 record outright.
+
+The same comparison is pointed at the rest of the kernel by two more tables of philox_sweep_ref:
+
+* INSTANCE_CASES (test_every_instance_matches_model): one case per compiled (D, K), D in {2, 3}, K in
+  1..9, at N = 257 / 512 / 256, under the kernel the library picks and under CLV_PERSISTENT=0 (never
+  =1).  launch_info()["persistent"] is asserted where capi.hip documents the instance's scratch (bi K
+  <= 8, tri K <= 4: persistent; tri K = 9: never) and printed for bi K = 9 and tri K = 5..8 (MI355X
+  build: bi 9 and tri 5 persistent, tri 6..8 launch per sweep).  The coverage events asserted per
+  case are exactly those of INSTANCE_COVERAGE, which the CPU module pins to the model's free run.
+  Measured over the 36 runs: no lane set aside; tau 2.8e-15, lambda 2.9e-15, mu 3.5e-15, eta 2.0e-15,
+  log-likelihood 2.6e-16, beta 6.5e-12, Sigma 2.5e-11 elementwise, 0 beyond the absolute term.
+* GRID_CASES (test_reduction_paths_match_model): 300 and 600 blocks per chain and 2 / 8 / 16 blocks per
+  unit on the full CDNOW CBS tiled cyclically — the second slot of the level-2 workgroup's lanes, the
+  strided unit loop, the unit arrival counters and batched unit sums over a partly filled last unit,
+  customer indices >= 65,536.  Each case asserts its geometry before the run.  Power on the model's
+  side: one block's rows (block 0, 256, 512, the one-customer last block) or the whole last unit left
+  out of the level-2 model and of the log-likelihood's sum must fail both; the next chain key's
+  variates must fail more than half the customers with index >= 65,536.  Measured over the 9 runs: 2
+  of 306,690 lanes set aside at g_bi2_600u, none elsewhere; tau 6.8e-15, lambda 2.7e-15, mu 3.6e-15,
+  eta 2.0e-15, log-likelihood 2.6e-16, level-2 record 5.4e-13 beyond the absolute term (beta 1.0e-10,
+  Sigma 9.6e-10 elementwise on entries near zero).  All 45 runs together take 5 s.
 """
 import ctypes
 
@@ -91,7 +112,10 @@ def _device_variates(L, seed, chain, sweep, n, S):
 class Device:
     """What one run of a case left on the device, indexed by sweep."""
 
-    def __init__(self, L, case, mp, persistent):
+    def __init__(self, L, case, mp, persistent, blocks_per_unit=0, geometry=None):
+        """``persistent``: the launch_info flag asserted (None: whatever the build chose, kept in
+        self.persistent); ``geometry``: (blocks, blocks per unit, units per rank, global units) asserted
+        against the handle before the run."""
         from mcmc_clv_model_amd.sampler import HipSampler, build_problem
         self.case, self.mp = case, mp
         self.C, self.T = case["chains"], M.n_sweeps_of(case)
@@ -100,8 +124,18 @@ class Device:
         self.states = {}
         with HipSampler(p, mcmc=case["mcmc"], burnin=case["burnin"], thin=case["thin"], chains=self.C,
                         seed=case["seed"], n_mh_steps=case["S"], draw_sink="full",
-                        chain_first=case["chain_first"]) as s:
-            assert s.launch_info()["persistent"] == persistent
+                        chain_first=case["chain_first"], blocks_per_unit=blocks_per_unit) as s:
+            self.persistent = s.launch_info()["persistent"]
+            assert persistent is None or self.persistent == persistent
+            if geometry is not None:
+                nb, bpu, upr, units = geometry
+                assert blocks_per_unit or L.clv_default_blocks_per_unit(mp.N) == bpu
+                # the handle's own plan: launch_info counts the customer workgroups (+ 1 level-2 workgroup
+                # per chain when persistent), partials() the unit partials [chain][stride][units per rank]
+                assert s.launch_info()["workgroups"] == (nb + self.persistent) * self.C
+                _, nd, stride = s.partials()
+                assert stride == mp.K * mp.D + mp.D * (mp.D + 1) // 2 + 1 and nd == self.C * stride * upr
+                assert upr == units == -(-nb // bpu)  # world size 1: every unit is this rank's
             for act in case["drive"]:
                 if act[0] == "run":
                     s.run(act[1])
@@ -151,9 +185,14 @@ def _close(got, ref, atol=0.0):
     return np.abs(got - ref) <= M.RTOL * np.abs(ref) + atol
 
 
-def compare(dev, chains, var_of=None, swap_t=False, swap_tau_branch=False, l2_sweep_shift=0, beta_slot_shift=0):
+def compare(dev, chains, var_of=None, swap_t=False, swap_tau_branch=False, l2_sweep_shift=0, beta_slot_shift=0,
+            l1_cache=None, drop=None, level2=True):
     """Model against device over the given chains.  Returns dict(fail (chain, customer) mask, l2_fail, ll_fail,
-    lanes, set_aside, n_l1, n_l2, dev_* largest relative deviations, edge counts)."""
+    lanes, set_aside, n_l1, n_l2, dev_* largest relative deviations, edge counts).
+    ``l1_cache``: a dict that keeps the level-1 model's results per (chain, sweep) between calls with the
+    same level-1 inputs; ``drop`` (power checks only): a customer mask left out of the level-2 model's X
+    and Y (nu_n unchanged) and of the log-likelihood's sum (still divided by N) — what a unit missing
+    from the reduction would give; ``level2=False`` skips the level-2 comparison."""
     mp, case = dev.mp, dev.case
     D, N = mp.D, mp.N
     var_of = var_of or (lambda c, s: dev.var[c, s])
@@ -172,7 +211,11 @@ def compare(dev, chains, var_of=None, swap_t=False, swap_tau_branch=False, l2_sw
                 v = dict(var_of(c, s))
                 if swap_t:
                     v["t_l"], v["t_m"] = v["t_m"], v["t_l"]
-                r = mp.level1(ent[0], ent[1], hyp[0], hyp[1], v, swap_tau_branch=swap_tau_branch)
+                r = l1_cache.get((c, s)) if l1_cache is not None else None
+                if r is None:
+                    r = mp.level1(ent[0], ent[1], hyp[0], hyp[1], v, swap_tau_branch=swap_tau_branch)
+                    if l1_cache is not None:
+                        l1_cache[c, s] = r
                 clear = r["margin"] > M.RTOL
                 out["n_l1"] += ci == 0
                 out["lanes"] += N
@@ -200,13 +243,13 @@ def compare(dev, chains, var_of=None, swap_t=False, swap_tau_branch=False, l2_sw
                     # the stored value is the mean of the likelihood term (bi:423-428); a lane set
                     # aside contributes the term of the device's own draw
                     lik = np.where(clear, r["lik"], orc.lik_terms(mp.x, mp.T_cal, row[:, 0], row[:, 1], z_dev, row[:, 2]))
-                    ll_dev, ll_ref = dev.ll[c, dev.idx(s)], lik.mean()
+                    ll_dev, ll_ref = dev.ll[c, dev.idx(s)], lik.mean() if drop is None else lik[~drop].sum() / N
                     out["loglik"] = max(out["loglik"], abs(ll_dev - ll_ref) / abs(ll_ref))
                     if not _close(ll_dev, ll_ref):
                         out["ll_fail"] = True
                 out["fail"][ci] |= bad & clear
         # level 2: the draw belonging to sweep hs, from the device's own level-1 output
-        for hs in range(1, dev.T + 2):
+        for hs in range(1, dev.T + 2 if level2 else 0):
             rec = dev.hyper_of(c, hs) if (D == 2 or hs <= dev.T) else None
             if D == 2:
                 src = dev.post(c, hs - 1)
@@ -217,7 +260,7 @@ def compare(dev, chains, var_of=None, swap_t=False, swap_tau_branch=False, l2_sw
                 continue
             out["n_l2"] += ci == 0
             l2 = mp.level2(case["seed"], case["chain_first"] + c, hs, Y, hsweep_of_variates=hs + l2_sweep_shift,
-                           beta_slot_shift=beta_slot_shift)
+                           beta_slot_shift=beta_slot_shift, rows=None if drop is None else ~drop)
             for k, got in (("beta", rec[0]), ("Sigma", rec[1])):
                 out[k] = max(out[k], float((np.abs(got - l2[k]) / np.abs(l2[k])).max()))
                 net = float(M.l2_deviation(got, l2[k]).max())  # what the comparison bounds by L2_RTOL
@@ -276,3 +319,114 @@ def test_production_sweep_matches_model(L, monkeypatch, name, mode):
     assert compare(dev, [0], beta_slot_shift=1)["l2_fail"]
     if case["D"] == 2:
         assert compare(dev, [0], l2_sweep_shift=-1)["l2_fail"]
+
+
+# ---------------------------------------------------------------------------------------------
+# every compiled instance (philox_sweep_ref.INSTANCE_CASES) and the level-2 reduction paths
+# (GRID_CASES): the same comparison, pointed at the rest of the kernel
+# ---------------------------------------------------------------------------------------------
+def _report(name, dev, r):
+    print(f"{name} ({'persistent' if dev.persistent else 'launch per sweep'}): {r['n_l1']} sweeps and {r['n_l2']} level-2 "
+          f"draws per chain x {dev.C} chains, {r['lanes']} lanes compared, {r['set_aside']} set aside; largest relative "
+          f"deviation tau {r['tau']:.2e} lambda {r['lam']:.2e} mu {r['mu']:.2e} eta {r['eta']:.2e} "
+          f"log-lik {r['loglik']:.2e} beta {r['beta']:.2e} Sigma {r['Sigma']:.2e} (elementwise; {r['l2_net']:.2e} beyond the "
+          f"absolute term); x = 0 lanes {r['x0']}, churned tau "
+          f"near t_x {r['near_tx']} / near T {r['near_T']} of {r['z_lanes']}, clip lanes {r['clip']}, cap lanes {r['cap']}")
+
+
+def _assert_parity(r, expect):
+    assert (r["n_l1"], r["n_l2"]) == expect
+    assert r["set_aside"] <= M.BORDERLINE_CAP * r["lanes"]
+    assert not r["fail"].any(), f"{r['fail'].sum()} (chain, customer) lanes differ from the model"
+    assert not r["ll_fail"], "a stored log-likelihood value differs from the model"
+    assert not r["l2_fail"], "a level-2 record differs from the model"
+
+
+def _set_kernel(monkeypatch, mode):
+    """The kernel the library picks by itself, or the opt-out — never CLV_PERSISTENT=1: forcing a
+    spilling instance into a resident grid makes workgroups wait out their bound (capi.hip)."""
+    if mode == "launch_per_sweep":
+        monkeypatch.setenv("CLV_PERSISTENT", "0")
+    else:
+        monkeypatch.delenv("CLV_PERSISTENT", raising=False)
+
+
+# (sweeps, level-2 draws) per chain of every instance case: one run(3), every sweep stored
+INSTANCE_EXPECT = {name: (3, 3) for name in M.INSTANCE_CASES}
+
+
+def instance_persistent_by_default(D, K):
+    """The instances capi.hip documents with 0 B of scratch run persistently; trivariate K = 9 (768 B
+    per lane) never; bivariate K = 9 and trivariate K = 5..8: what the build's scratch gives (None)."""
+    if (D == 2 and K <= 8) or (D == 3 and K <= 4):
+        return True
+    return False if (D, K) == (3, 9) else None
+
+
+INSTANCE_RUNS = [(n, m) for n in M.INSTANCE_CASES for m in ("default", "launch_per_sweep")]
+
+
+@pytest.mark.parametrize("name,mode", INSTANCE_RUNS, ids=[f"{n}-{m}" for n, m in INSTANCE_RUNS])
+def test_every_instance_matches_model(L, monkeypatch, name, mode):
+    case = M.INSTANCE_CASES[name]
+    _set_kernel(monkeypatch, mode)
+    persistent = instance_persistent_by_default(case["D"], len(case["covs"]) + 1) if mode == "default" else False
+    mp = M.ModelProblem(M.case_frame(case), case["covs"], case["D"])
+    dev = Device(L, case, mp, persistent)
+    if persistent is None:
+        print(f"{name}: the build runs this instance {'persistently' if dev.persistent else 'launch per sweep'} by default")
+    r = compare(dev, range(dev.C))
+    _report(name, dev, r)
+    _assert_parity(r, INSTANCE_EXPECT[name])
+    # exactly the coverage events the model's free run of this case shows (asserted on the CPU)
+    for ev in M.INSTANCE_COVERAGE[name]:
+        assert r[ev] > 0, ev
+    if mode != "default":
+        return
+
+    # ---- power: one thing wrong at a time in the model's inputs, same device outputs, chain 0
+    def l1_share(**kw):
+        return compare(dev, [0], level2=False, **kw)["fail"].mean()
+
+    shares = dict(next_sweep=l1_share(var_of=lambda c, s: dev.var[c, s + 1]),
+                  next_chain_key=l1_share(var_of=lambda c, s: dev.var_next_key[s]),
+                  t_swapped=l1_share(swap_t=True))
+    print(f"{name}: power, share of customers failing: " + ", ".join(f"{k} {v:.2f}" for k, v in shares.items()))
+    for k, v in shares.items():
+        assert v > 0.5, (k, v)
+    assert compare(dev, [0], beta_slot_shift=1)["l2_fail"]
+
+
+GRID_EXPECT = {name: (2, 2) for name in M.GRID_CASES}  # one run(2), both sweeps stored
+FIRST_LARGE_INDEX = 65536  # customer indices from here on need more than 16 bits of the Philox counter word
+
+
+@pytest.mark.parametrize("name,mode", M.GRID_RUNS, ids=[f"{n}-{m}" for n, m in M.GRID_RUNS])
+def test_reduction_paths_match_model(L, monkeypatch, name, mode):
+    case = M.GRID_CASES[name]
+    _set_kernel(monkeypatch, mode)
+    mp = M.ModelProblem(M.case_frame(case), case["covs"], case["D"])
+    # the geometry this case is meant to reach, from N and blocks_per_unit by the plan rule
+    assert M.grid_geometry(case) == case["geometry"]
+    dev = Device(L, case, mp, case["modes"][mode], blocks_per_unit=case["blocks_per_unit"], geometry=case["geometry"])
+    l1 = {}
+    r = compare(dev, range(dev.C), l1_cache=l1)
+    _report(name, dev, r)
+    _assert_parity(r, GRID_EXPECT[name])
+    assert r["x0"] > 0 and r["near_tx"] > 0 and r["near_T"] > 0
+
+    # ---- power, on the model's side: a block (or the last unit) missing from the reduction breaks
+    # the level-2 record and the log-likelihood; wrong variates break the large customer indices
+    for what, (lo, hi) in case["drop"].items():
+        assert 0 <= lo < hi <= mp.N
+        drop = np.zeros(mp.N, bool)
+        drop[lo:hi] = True
+        d = compare(dev, [0], l1_cache=l1, drop=drop)
+        print(f"{name}: power, customers [{lo}, {hi}) ({what}) left out: level-2 record off by {d['l2_net']:.1e}, "
+              f"log-likelihood by {d['loglik']:.1e}")
+        assert d["l2_fail"] and d["ll_fail"], what
+    fail = compare(dev, [0], var_of=lambda c, s: dev.var_next_key[s], level2=False)["fail"][0]
+    large = fail[FIRST_LARGE_INDEX:] if mp.N > FIRST_LARGE_INDEX else fail
+    print(f"{name}: power, next_chain_key fails {large.mean():.2f} of the {large.size} customers with index >= "
+          f"{FIRST_LARGE_INDEX if mp.N > FIRST_LARGE_INDEX else 0}")
+    assert large.mean() > 0.5

@@ -11,8 +11,15 @@ here it is pinned to the REFERENCE, never to the kernel:
   oracle.philox's variates (the oracle through a stub Stream), to the GPU module's tolerances;
 * at every shape the GPU module uses, the share of (chain, sweep, customer) lanes whose decision
   margin is below the comparison tolerance stays within the 0.1% cap, and the level-2 tolerance
-  covers ten times the measured sensitivity to the variates' and Y's documented uncertainty.
+  covers ten times the measured sensitivity to the variates' and Y's documented uncertainty — for
+  CASES, INSTANCE_CASES (every compiled (D, K)) and GRID_CASES (up to 153,345 customers) alike;
+* the coverage events the GPU module asserts per instance case (INSTANCE_COVERAGE) are exactly those
+  the model's free run of the case produces;
+* at the grid cases' sizes numpy's mean of the likelihood terms and the exactly rounded one differ by
+  at most a tenth of the log-likelihood's comparison tolerance.
 """
+import math
+
 import numpy as np
 import pytest
 
@@ -211,19 +218,38 @@ def test_model_sweep_agrees_with_the_oracle_chain(name):
 
 
 # ---------------------------------------------------------------------------------------------
-@pytest.fixture(scope="module")
-def free_runs():
-    """Every GPU case's chains run freely through the model with oracle.philox's variates."""
-    out = {}
-    for name, case in M.CASES.items():
+class _FreeRuns(dict):
+    """Every GPU case's chains run freely through the model with oracle.philox's variates (on first use)."""
+
+    def __missing__(self, name):
+        case = M.ALL_CASES[name]
         mp = M.ModelProblem(M.case_frame(case), case["covs"], case["D"])
         assert mp.N == case["data"][1]
-        out[name] = (mp, {c: list(M.model_chain(mp, case["seed"], case["chain_first"] + c, M.n_sweeps_of(case), case["S"]))
-                          for c in range(case["chains"])})
-    return out
+        self[name] = (mp, {c: list(M.model_chain(mp, case["seed"], case["chain_first"] + c, M.n_sweeps_of(case), case["S"]))
+                           for c in range(case["chains"])})
+        return self[name]
 
 
-@pytest.mark.parametrize("name", list(M.CASES))
+@pytest.fixture(scope="module")
+def free_runs():
+    return _FreeRuns()
+
+
+def coverage_of(mp, chains):
+    """Lanes of each coverage event (philox_sweep_ref.COVERAGE_EVENTS) over a case's free run."""
+    n = dict.fromkeys(M.COVERAGE_EVENTS, 0)
+    for runs in chains.values():
+        for s, r, _ in runs:
+            edges = M.near_edges(mp, r["z"], r["tau"])
+            n["x0"] += int(((mp.x == 0) & (mp.t_x == 0)).sum())
+            n["near_tx"] += int(edges[0].sum())
+            n["near_T"] += int(edges[1].sum())
+            n["clip"] += int(r["hit_clip"].sum())
+            n["cap"] += int(r["hit_cap"].sum())
+    return n
+
+
+@pytest.mark.parametrize("name", list(M.ALL_CASES))
 def test_borderline_share_is_within_the_cap(free_runs, name):
     """The cap is a condition on the model alone: no device involved."""
     mp, chains = free_runs[name]
@@ -243,13 +269,13 @@ def test_borderline_share_is_within_the_cap(free_runs, name):
     assert (mp.x == 0).any() and near_tx > 0 and near_T > 0
 
 
-@pytest.mark.parametrize("name", list(M.CASES))
+@pytest.mark.parametrize("name", list(M.ALL_CASES))
 def test_level2_tolerance_covers_the_measured_sensitivity(free_runs, name):
     """The hyper variates are pinned to <= 1e-12 relative (test_device_hyper_variates_match_oracle) and
     the device's Y is the log-scale state, within 2 ulp of log of the stored natural-scale one: the
     level-2 tolerance must cover ten times what those move beta and Sigma at this shape."""
     mp, chains = free_runs[name]
-    case = M.CASES[name]
+    case = M.ALL_CASES[name]
     rng = np.random.default_rng(1)
     worst = raw = 0.0
     runs = chains[0]
@@ -272,3 +298,28 @@ def test_level2_tolerance_covers_the_measured_sensitivity(free_runs, name):
     print(f"{name}: level-2 sensitivity {worst:.3e} beyond atol {M.L2_ATOL:.0e} (elementwise relative, no atol: "
           f"{raw:.3e}; tolerance {M.L2_RTOL:.1e})")
     assert 10 * worst <= M.L2_RTOL
+
+
+@pytest.mark.parametrize("name", list(M.INSTANCE_CASES))
+def test_instance_coverage_table_is_what_the_model_produces(free_runs, name):
+    """philox_sweep_ref.INSTANCE_COVERAGE, which the GPU module asserts per case, is exactly the set of
+    coverage events the model's free run of the case produces."""
+    mp, chains = free_runs[name]
+    n = coverage_of(mp, chains)
+    print(f"{name}: N {mp.N}, coverage lanes " + ", ".join(f"{k} {v}" for k, v in n.items()))
+    assert {k for k, v in n.items() if v > 0} == set(M.INSTANCE_COVERAGE[name])
+
+
+@pytest.mark.parametrize("name", list(M.GRID_CASES))
+def test_loglik_mean_does_not_depend_on_the_summation_order(free_runs, name):
+    """The stored log-likelihood is a mean over up to 153,345 terms, summed on the device per block, per
+    unit and over the units.  numpy's pairwise mean of the model's terms, which the GPU module compares
+    it with at RTOL, and the exactly rounded mean (math.fsum) differ by at most a tenth of RTOL."""
+    mp, chains = free_runs[name]
+    worst = 0.0
+    for runs in chains.values():
+        for s, r, _ in runs:
+            exact = math.fsum(r["lik"]) / mp.N
+            worst = max(worst, abs(r["lik"].mean() - exact) / abs(exact))
+    print(f"{name}: {mp.N} terms, numpy mean against fsum mean {worst:.2e} relative (a tenth of RTOL: {0.1 * M.RTOL:.0e})")
+    assert worst <= 0.1 * M.RTOL
