@@ -3,7 +3,9 @@
 //
 //   clv_elog2cbs            utils/elog2cbs2param.py:33-94 (date-based event log, calibration and
 //                           hold-out statistics): stable radix sorts by (customer, date), same-day
-//                           merge, one lane per customer over its date-ordered events.
+//                           merge, one lane per customer over its date-ordered events.  Same-day
+//                           sales are summed sequentially in input order: a tested property
+//                           (tests/test_gpu_elog.py, case `order`), like every sort path and edge.
 //   clv_generate_pareto_abe bivariate/mcmc.py:95-187 (Abe 2009 simulation: covariates, log-normal
 //                           heterogeneity, exponential lifetimes, Poisson purchase process) with
 //                           the CBS of bi:75-89 formed in the same pass, one lane per customer.

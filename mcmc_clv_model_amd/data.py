@@ -102,6 +102,8 @@ def elog2cbs(elog: pd.DataFrame, units="week", T_cal=None, T_tot=None, *, device
     if "sales" not in elog.columns:
         out["sales"] = out["sales"].astype(np.int64)  # the reference sums the integer 1s it inserts
         out["sales_x"] = out["sales_x"].astype(np.int64)
+    elif not (o["x"][:k] > 0).any():
+        out["sales_x"] = out["sales_x"].astype(np.int64)  # all the integer 0 of elog2cbs2param.py:79
     if T_cal_ts < T_tot_ts:
         out["T_star"] = o["T_star"][:k]
         out["x_star"] = o["x_star"][:k].astype(np.float64)  # left merge + fillna: float like the reference

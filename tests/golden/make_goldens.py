@@ -24,6 +24,9 @@ Fixtures written:
   generator_bi.npz           row f4: a 20,000-customer sample of the reference's generate_pareto_abe
   generator_replay.npz       the reference's generate_pareto_abe fed the generator's Philox variates
                              (tests/analysis_stream_ref.py) through a stub Generator: three small cases
+  elog_cases.npz             the reference's elog2cbs outputs on the seeded cases of tests/elog_ref.py that
+                             it can run (inputs are rebuilt from the seeds, not stored), written only if
+                             the model of tests/elog_ref.py reproduces every one of them
 
 Usage:  PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_goldens.py [--skip-envelope]
 """
@@ -665,6 +668,34 @@ def write_generator_replay(rbi):
     np.savez_compressed(os.path.join(HERE, "generator_replay.npz"), **out)
 
 
+def write_elog_cases():
+    """The reference's elog2cbs on the cases of tests/elog_ref.py (REFERENCE_CASES, and ``shuffled``
+    without its sales column).  Refuses to write unless the model matches each output: integer
+    columns equal, ratio and sales columns bit for bit, litt within its derived bound."""
+    sys.path.insert(0, REF)
+    from src.models.utils.elog2cbs2param import elog2cbs as ref_elog2cbs  # noqa: E402
+    from tests import elog_ref as E
+    out, ratio = {}, []
+    for name in E.REFERENCE_CASES + ("shuffled_nosales",):
+        with_sales = name != "shuffled_nosales"
+        inputs, _ = E.ELOG_CASES[name.replace("_nosales", "")]()
+        cust, date_ns, sales, units, T_cal, T_tot = inputs
+        df = pd.DataFrame(dict(cust=cust, date=pd.to_datetime(date_ns), sales=sales))
+        cbs = ref_elog2cbs(df if with_sales else df[["cust", "date"]], units=units, T_cal=T_cal, T_tot=T_tot)
+        got = E.frame_columns(cbs)
+        bad = E.mismatches(got, E.run_model(inputs, with_sales=with_sales), ratio)
+        print("elog case", name, len(cbs), "rows", "litt ratio %.3f" % ratio[-1], bad or "ok")
+        if bad:
+            raise SystemExit(f"the elog model differs from the reference on {name}: {bad}; refusing to write fixtures")
+        out[f"{name}__columns"] = np.array(list(cbs.columns), dtype="U16")
+        out[f"{name}__kinds"] = np.array([cbs[c].dtype.kind for c in cbs.columns], dtype="U1")
+        for c, v in got.items():
+            out[f"{name}__{c}"] = v.astype("U") if v.dtype == object else v
+    out["litt_ratio_max"] = np.float64(max(ratio))
+    np.savez_compressed(os.path.join(HERE, "elog_cases.npz"), **out)
+    print("elog cases: largest |litt - model| / (2^-52 litt_abs) =", max(ratio))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--skip-envelope", action="store_true")
@@ -676,7 +707,8 @@ def main():
     steps = [("pin", lambda: pin_oracle(rbi, rtri)), ("data", write_data), ("philox", write_philox_kat),
              ("formulas", lambda: write_formulas(rbi, rtri)), ("replay", lambda: write_replay(rbi, rtri, set(a.replay_names.split(",")) if a.replay_names else None)),
              ("published", write_published), ("analysis", lambda: write_analysis(rbi, rtri)),
-             ("dataprep", lambda: write_dataprep(rbi)), ("generator_replay", lambda: write_generator_replay(rbi))]
+             ("dataprep", lambda: write_dataprep(rbi)), ("generator_replay", lambda: write_generator_replay(rbi)),
+             ("elog_cases", write_elog_cases)]
     if not a.skip_envelope:
         steps.append(("envelope", write_envelope))
         steps.append(("envelope_full", lambda: write_envelope_full(rbi, rtri)))
