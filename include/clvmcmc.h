@@ -485,6 +485,37 @@ int clv_generate_pareto_abe(int32_t device, int64_t n, int32_t K, const double* 
                             int64_t* n_events, const int64_t* elog_offsets, int64_t elog_rows, int64_t* elog_cust,
                             double* elog_t);
 
+/* ---- Pareto/NBD maximum-likelihood baseline on device (csrc/pnbd.hip) ----
+ * The classical Pareto/NBD the reference fits with lifetimes.ParetoNBDFitter and compares both HB
+ * models against: bivariate/analysis_abe.py:205-217 (fit, conditional expected purchases for the
+ * Table 2 rows) and :426-438 (the birth-aligned "Pareto/NBD (MLE)" curve of Figure 2);
+ * full_analysis.py:245, :437.  params = (r, alpha, s, beta), all > 0 and finite (CLV_EINVAL
+ * otherwise).  Per customer x (repeat count), t_x, T with 0 <= t_x <= T:
+ *   L = Gamma(r+x) alpha^r beta^s / Gamma(r) { (alpha+T)^-(r+x) (beta+T)^-s + s I },
+ *   I = int_{t_x}^{T} (alpha+y)^-(r+x) (beta+y)^-(s+1) dy,
+ * evaluated through an Euler-transformed hypergeometric series of positive terms that stops when
+ * its remainder bound is below 2^-53 of the sum, or after 2048 terms (z = |alpha - beta| /
+ * (max(alpha, beta) + t) up to about 0.98).  A customer that reaches the cap is counted, and its
+ * values are NaN: nothing is truncated silently.
+ * A handle keeps x, t_x, T and the optional weights (NULL = 1) on the device for the evaluations
+ * of a fit; creating one fails with CLV_EINVAL for n <= 0, a null column, a negative x or weight,
+ * t_x outside [0, T] or a non-finite value.
+ * The eval entry writes sums[6] = sum w log L, its derivatives with respect to (log r, log alpha,
+ * log s, log beta), sum w; *n_unconverged (may be NULL) = customers at the term cap, sums[0] is NaN
+ * then.  Sums are per-256-customer block partials added in a fixed order: the same bits on every
+ * call.  The customers entry writes out[n][3] = log L, P(alive | x, t_x, T), E[Y(t_star) | x, t_x,
+ * T] (t_star >= 0).  The track entry writes cum[j] = sum_i E[X(max(times[j] - birth_week[i], 0))],
+ * E[X(t)] = r beta / alpha (1 - (beta / (beta + t))^(s-1)) / (s - 1), reduced in the same fixed
+ * order for every time; n_times in 1..65535. */
+typedef struct clv_pnbd clv_pnbd;
+int clv_pnbd_create(int32_t device, int64_t n, const int32_t* x, const double* t_x, const double* T,
+                    const double* weights, clv_pnbd** out);
+void clv_pnbd_destroy(clv_pnbd* h);
+int clv_pnbd_eval(clv_pnbd* h, const double* params, double* sums, int64_t* n_unconverged);
+int clv_pnbd_customers(clv_pnbd* h, const double* params, double t_star, double* out);
+int clv_pnbd_track(int32_t device, int64_t n, const double* birth_week, const double* times, int32_t n_times,
+                   const double* params, double* cum);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,7 +10,10 @@ of utils/analysis_bi_helpers.py and the weekly tracking curve, also on the GPU (
 the convergence diagnostics the reference asks of ArviZ (analysis_abe.py:651-706): split R-hat, ESS,
 MCSE and autocorrelation for the level-2 draws and for every customer (level1_diagnostics), and
 az.summary's table with its rank-normalised ess_bulk, ess_tail and r_hat (level2_summary,
-level1_rank_diagnostics, level2_rank_diagnostics).
+level1_rank_diagnostics, level2_rank_diagnostics).  The classical Pareto/NBD fitted by maximum
+likelihood, the baseline both HB models are measured against (analysis_abe.py:205-217, :426-438), is
+mle.ParetoNBDFitter, a drop-in for what the reference uses of lifetimes', with pnbd_weekly_tracking
+and mape_aggregate (analysis_bi_helpers.py:29).
 
 The per-sweep work runs in hand-written HIP kernels for gfx950 (csrc/), bound through the C
 ABI in include/clvmcmc.h.  There is no CPU fallback.
@@ -21,11 +24,13 @@ from .analysis import (chain_total_loglik, compute_table4, draw_future_transacti
                        level2_summary, post_mean_lambdas, post_mean_mus, posterior_weekly_tracking,
                        summarize_level2, summary_rhat)
 from .bivariate import mcmc_draw_parameters
+from .mle import ParetoNBDFitter, mape_aggregate, pnbd_weekly_tracking
 from .trivariate import mcmc_draw_parameters_rfm_m
 
 __all__ = ["mcmc_draw_parameters", "mcmc_draw_parameters_rfm_m", "draw_future_transactions",
            "draw_future_transactions_rfm_m", "post_mean_lambdas", "post_mean_mus", "chain_total_loglik",
            "compute_table4", "posterior_weekly_tracking", "level1_diagnostics", "level2_diagnostics",
            "level2_autocorr", "summarize_level2", "extract_correlation", "summary_rhat",
-           "level1_rank_diagnostics", "level2_rank_diagnostics", "level2_summary"]
+           "level1_rank_diagnostics", "level2_rank_diagnostics", "level2_summary", "ParetoNBDFitter",
+           "pnbd_weekly_tracking", "mape_aggregate"]
 __version__ = "0.1.0"

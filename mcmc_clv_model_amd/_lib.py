@@ -155,6 +155,11 @@ def lib() -> ctypes.CDLL:
         "clv_generate_pareto_abe": (c_int32, [c_int32, c_int64, c_int32, dp, dp, dp, dp, c_int32, dp, c_uint64,
                                               POINTER(c_int64), dp, dp, dp, dp, POINTER(c_uint8), POINTER(c_int64), dp,
                                               POINTER(c_int64), POINTER(c_int64), c_int64, POINTER(c_int64), dp]),
+        "clv_pnbd_create": (c_int32, [c_int32, c_int64, POINTER(c_int32), dp, dp, dp, POINTER(sp)]),
+        "clv_pnbd_destroy": (None, [sp]),
+        "clv_pnbd_eval": (c_int32, [sp, dp, dp, POINTER(c_int64)]),
+        "clv_pnbd_customers": (c_int32, [sp, dp, c_double, dp]),
+        "clv_pnbd_track": (c_int32, [c_int32, c_int64, dp, dp, c_int32, dp, dp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)

@@ -1,0 +1,392 @@
+// The classical Pareto/NBD likelihood on device: the maximum-likelihood baseline the reference takes
+// from lifetimes.ParetoNBDFitter (bivariate/analysis_abe.py:205-217, :426-438; full_analysis.py:245,
+// :437).  DESIGN.md section 4e; float64 model: tests/pnbd_ref.py.
+//
+//   clv_pnbd_create / _destroy   the CBS columns (x, t_x, T, weights) resident for a fit
+//   clv_pnbd_eval                sum w log L and its gradient with respect to log(r, alpha, s, beta)
+//   clv_pnbd_customers           per customer log L, P(alive), E[Y(t*) | x, t_x, T]
+//   clv_pnbd_track               cum[j] = sum_i E[X(max(times[j] - birth_week[i], 0))]
+//
+// Per customer, with theta = (r, alpha, s, beta), a = r + s + x, M = max(alpha, beta) and
+// z(t) = |alpha - beta| / (M + t) in [0, 1):
+//   L = Gamma(r+x) alpha^r beta^s / Gamma(r) { (alpha+T)^-(r+x) (beta+T)^-s + s I }
+//   I = int_{t_x}^{T} (alpha+y)^-(r+x) (beta+y)^-(s+1) dy = [H(t_x) - H(T)] / a
+//   H(t) = 2F1(a, b; a+1; z(t)) / (M+t)^a,  b = s+1 if alpha >= beta, r+x otherwise
+// 2F1 is never summed directly (with b = r+x its terms grow before they decay and overflow for x
+// in the hundreds): Euler's transformation gives 2F1(a, b; a+1; z) = (1-z)^(1-b) G(a+1-b, a+1; z),
+// G(c1, c; z) = sum_n (c1)_n / (c)_n z^n, whose terms are positive with ratios < z, so the remainder
+// after u_n is at most u_n z / (1 - z): an exact stopping rule.  Everything is carried in logs.
+// The gradient comes from the same loop: du_n/dc1 = u_n sum_{k<n} 1/(c1+k), du_n/dc =
+// -u_n sum_{k<n} 1/(c+k), du_n/dz = n u_n / z, and psi(r+x) - psi(r) = sum_{k<x} 1/(r+k).
+//
+// One lane per customer.  No float atomics: each 256-customer block reduces its lanes by an LDS
+// tree, and a second kernel adds the block partials in a fixed order (lane t takes partials
+// t, t + 256, ... in turn, then the same tree), so the sums do not depend on the grid size and are
+// bitwise the same on every call.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <limits>
+#include <string>
+#include <vector>
+
+#include "internal.h"
+
+using namespace clv;
+
+struct clv_pnbd {
+  int device = 0;
+  int64_t n = 0, nb = 0;  // customers, 256-customer blocks
+  int32_t* d_x = nullptr;
+  double *d_tx = nullptr, *d_T = nullptr, *d_w = nullptr;
+  double* d_part = nullptr;  // [nb][PNBD_NS] block partials
+  double* d_out = nullptr;   // [PNBD_NS]
+};
+
+namespace {
+
+constexpr int PNBD_NS = 7;            // sum w log L, 4 gradient sums, sum w, unconverged customers
+constexpr int PNBD_TERM_CAP = 2048;   // series terms after u_0 (reaches z of about 0.98)
+constexpr double PNBD_EPS = 0x1p-53;  // relative remainder at which the series stops
+constexpr int PNBD_MAX_GRID = 2048;
+
+struct Params {
+  double r, a, s, b;
+};
+
+// log G(c1, c; z) and d log G / d(c1, c, z); conv = the remainder rule was met within the cap.
+struct Series {
+  double lg, gc1, gc, gz;
+  bool conv;
+};
+
+__host__ __device__ inline Series pnbd_series(double c1, double c, double z) {
+  double u = 1.0, G = 1.0, s1 = 0.0, s2 = 0.0, d1 = 0.0, d2 = 0.0, dz = 0.0;
+  const double q = z / (1.0 - z);
+  bool conv = false;
+  for (int n = 0;; ++n) {
+    if (u * q <= PNBD_EPS * G) {
+      conv = true;
+      break;
+    }
+    if (n == PNBD_TERM_CAP) break;
+    const double i1 = 1.0 / (c1 + n), i2 = 1.0 / (c + n);
+    s1 += i1;
+    s2 += i2;
+    u = u * (((c1 + n) * i2) * z);
+    G += u;
+    d1 += u * s1;
+    d2 += u * s2;
+    dz += (n + 1.0) * u;
+  }
+  Series o;
+  o.lg = log(G);
+  o.gc1 = d1 / G;
+  o.gc = -d2 / G;
+  o.gz = (z > 0.0 ? dz / z : c1 / c) / G;
+  o.conv = conv;
+  return o;
+}
+
+// log H(t) and its derivatives with respect to (r, alpha, s, beta).
+struct LogH {
+  double lh, d[4];
+  bool conv;
+};
+
+__host__ __device__ inline LogH pnbd_log_h(double t, double x, const Params& p) {
+  const bool swap = p.a < p.b;
+  const double M = (swap ? p.b : p.a) + t;
+  const double z = fabs(p.a - p.b) / M;
+  const double aa = p.r + p.s + x;
+  const Series g = pnbd_series(swap ? p.s + 1.0 : p.r + x, aa + 1.0, z);
+  const double bm1 = swap ? p.r + x - 1.0 : p.s;  // b - 1
+  const double l1z = log1p(-z), lM = log(M);
+  LogH o;
+  o.conv = g.conv;
+  o.lh = g.lg - bm1 * l1z - aa * lM;
+  const double w = g.gz + bm1 / (1.0 - z);                // d log H / dz
+  const double z_big = (1.0 - z) / M, z_small = -1.0 / M;  // dz / d(larger of alpha, beta), d(smaller)
+  if (swap) {
+    o.d[0] = g.gc - l1z - lM;
+    o.d[2] = g.gc1 + g.gc - lM;
+    o.d[1] = w * z_small;
+    o.d[3] = w * z_big - aa / M;
+  } else {
+    o.d[0] = g.gc1 + g.gc - lM;
+    o.d[2] = g.gc - l1z - lM;
+    o.d[1] = w * z_big - aa / M;
+    o.d[3] = w * z_small;
+  }
+  return o;
+}
+
+// One customer: log L, its gradient with respect to log(r, alpha, s, beta), and P(alive) =
+// A / (A + s I) with A the survivor term.  A series that hit the cap makes all of them NaN.
+struct Point {
+  double logL, g[4], p_alive;
+  bool conv;
+};
+
+__host__ __device__ inline Point pnbd_point(int32_t xi, double tx, double T, const Params& p) {
+  const double x = (double)xi, rx = p.r + x;
+  double dig = 0.0;  // psi(r + x) - psi(r)
+  for (int32_t k = 0; k < xi; ++k) dig += 1.0 / (p.r + k);
+  const double laT = log(p.a + T), lbT = log(p.b + T);
+  const double logA = -rx * laT - p.s * lbT;
+  const double dA[4] = {-laT, -rx / (p.a + T), -lbT, -p.s / (p.b + T)};
+  double logsI = -INFINITY;
+  double dI[4] = {0.0, 0.0, 0.0, 0.0};
+  bool conv = true;
+  if (tx < T) {
+    const LogH h1 = pnbd_log_h(tx, x, p), h2 = pnbd_log_h(T, x, p);
+    conv = h1.conv && h2.conv;
+    const double d = h2.lh - h1.lh;
+    const double e = exp(d), om = -expm1(d);  // 1 - H(T) / H(t_x)
+    const double aa = p.r + p.s + x;
+    if (om > 0.0) {
+      logsI = log(p.s) + h1.lh + log(om) - log(aa);
+      for (int j = 0; j < 4; ++j) dI[j] = (h1.d[j] - e * h2.d[j]) / om;
+      dI[0] -= 1.0 / aa;
+      dI[2] += 1.0 / p.s - 1.0 / aa;
+    }
+  }
+  const double mx = fmax(logA, logsI);
+  const double eA = exp(logA - mx), eI = exp(logsI - mx);
+  const double den = eA + eI;
+  const double wA = eA / den, wI = eI / den;
+  Point o;
+  o.conv = conv;
+  o.logL = lgamma(rx) - lgamma(p.r) + p.r * log(p.a) + p.s * log(p.b) + (mx + log(den));
+  const double base[4] = {dig + log(p.a), p.r / p.a, log(p.b), p.s / p.b};
+  const double scale[4] = {p.r, p.a, p.s, p.b};
+  for (int j = 0; j < 4; ++j) o.g[j] = (base[j] + wA * dA[j] + wI * dI[j]) * scale[j];
+  o.p_alive = wA;
+  if (!conv) {
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    o.logL = o.p_alive = nan;
+    for (int j = 0; j < 4; ++j) o.g[j] = nan;
+  }
+  return o;
+}
+
+// -expm1(-k l) / k, and l at k = 0.
+__host__ __device__ inline double pnbd_phi(double k, double l) { return k == 0.0 ? l : -expm1(-k * l) / k; }
+
+// E[X(t)] = r beta / alpha phi(s - 1, log((beta + t) / beta)).
+__host__ __device__ inline double pnbd_expected(double t, const Params& p) {
+  return p.r * p.b / p.a * pnbd_phi(p.s - 1.0, log1p(t / p.b));
+}
+
+// red[k][0] = sum over the 256 lanes of red[k][lane], tree offsets 128, 64, ..., 1.
+template <int NSUM>
+__device__ __forceinline__ void tree256(double (*red)[256]) {
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) {
+    if ((int)threadIdx.x < off)
+      for (int k = 0; k < NSUM; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + off];
+    __syncthreads();
+  }
+}
+
+__global__ __launch_bounds__(256) void pnbd_eval_kernel(const int32_t* x, const double* tx, const double* T,
+                                                        const double* w, int64_t n, int64_t nb, Params p,
+                                                        double* part /*[nb][PNBD_NS]*/) {
+  __shared__ double red[PNBD_NS][256];
+  for (int64_t b = blockIdx.x; b < nb; b += gridDim.x) {
+    const int64_t i = b * 256 + threadIdx.x;
+    double v[PNBD_NS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (i < n) {
+      const Point q = pnbd_point(x[i], tx[i], T[i], p);
+      const double wi = w ? w[i] : 1.0;
+      v[0] = wi * q.logL;
+      for (int j = 0; j < 4; ++j) v[1 + j] = wi * q.g[j];
+      v[5] = wi;
+      v[6] = q.conv ? 0.0 : 1.0;
+    }
+    for (int k = 0; k < PNBD_NS; ++k) red[k][threadIdx.x] = v[k];
+    tree256<PNBD_NS>(red);
+    if (threadIdx.x < PNBD_NS) part[b * PNBD_NS + threadIdx.x] = red[threadIdx.x][0];
+    __syncthreads();
+  }
+}
+
+// out[row][k] = fixed-order sum over b < nb of part[(row * nb + b) * ns + k]; grid (ns, rows).
+__global__ __launch_bounds__(256) void pnbd_final_kernel(const double* part, int64_t nb, int ns, double* out) {
+  __shared__ double red[1][256];
+  const int k = blockIdx.x;
+  const int64_t row = blockIdx.y;
+  double acc = 0.0;
+  for (int64_t b = threadIdx.x; b < nb; b += 256) acc += part[(row * nb + b) * ns + k];
+  red[0][threadIdx.x] = acc;
+  tree256<1>(red);
+  if (threadIdx.x == 0) out[row * ns + k] = red[0][0];
+}
+
+__global__ __launch_bounds__(256) void pnbd_customers_kernel(const int32_t* x, const double* tx, const double* T,
+                                                             int64_t n, Params p, double t_star,
+                                                             double* out /*[n][3]*/) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const Point q = pnbd_point(x[i], tx[i], T[i], p);
+    const double Ti = T[i];
+    out[i * 3 + 0] = q.logL;
+    out[i * 3 + 1] = q.p_alive;
+    out[i * 3 + 2] = q.p_alive * (p.r + (double)x[i]) * (p.b + Ti) / (p.a + Ti) *
+                     pnbd_phi(p.s - 1.0, log1p(t_star / (p.b + Ti)));
+  }
+}
+
+// part[j][b] = tree sum over block b's customers of E[X(max(times[j] - birth, 0))]; grid (blocks, times).
+__global__ __launch_bounds__(256) void pnbd_track_kernel(const double* birth, const double* times, int64_t n,
+                                                         int64_t nb, Params p, double* part /*[n_times][nb]*/) {
+  __shared__ double red[1][256];
+  const double tj = times[blockIdx.y];
+  for (int64_t b = blockIdx.x; b < nb; b += gridDim.x) {
+    const int64_t i = b * 256 + threadIdx.x;
+    red[0][threadIdx.x] = i < n ? pnbd_expected(fmax(tj - birth[i], 0.0), p) : 0.0;
+    tree256<1>(red);
+    if (threadIdx.x == 0) part[(int64_t)blockIdx.y * nb + b] = red[0][0];
+    __syncthreads();
+  }
+}
+
+int check_params(const double* params, Params* p) {
+  if (!params) return fail(CLV_EINVAL, "pnbd: null params");
+  for (int j = 0; j < 4; ++j)
+    if (!(params[j] > 0.0) || !std::isfinite(params[j]))
+      return fail(CLV_EINVAL, "pnbd: params (r, alpha, s, beta) must be positive and finite");
+  *p = Params{params[0], params[1], params[2], params[3]};
+  return CLV_OK;
+}
+
+unsigned grid_for(int64_t nb) { return (unsigned)std::min<int64_t>(nb, PNBD_MAX_GRID); }
+
+}  // namespace
+
+extern "C" {
+
+int clv_pnbd_create(int32_t device, int64_t n, const int32_t* x, const double* t_x, const double* T,
+                    const double* weights, clv_pnbd** out) {
+  if (!out) return fail(CLV_EINVAL, "pnbd: null handle pointer");
+  *out = nullptr;
+  if (n <= 0) return fail(CLV_EINVAL, "pnbd: n must be >= 1");
+  if (!x || !t_x || !T) return fail(CLV_EINVAL, "pnbd: null x, t_x or T");
+  for (int64_t i = 0; i < n; ++i) {
+    if (x[i] < 0) return fail(CLV_EINVAL, "pnbd: negative x at customer " + std::to_string(i));
+    if (!std::isfinite(t_x[i]) || !std::isfinite(T[i]))
+      return fail(CLV_EINVAL, "pnbd: non-finite t_x or T at customer " + std::to_string(i));
+    if (t_x[i] < 0.0 || t_x[i] > T[i])
+      return fail(CLV_EINVAL, "pnbd: 0 <= t_x <= T violated at customer " + std::to_string(i));
+    if (weights && (!std::isfinite(weights[i]) || weights[i] < 0.0))
+      return fail(CLV_EINVAL, "pnbd: negative or non-finite weight at customer " + std::to_string(i));
+  }
+  int count = 0;
+  if (hipGetDeviceCount(&count) != hipSuccess || count < 1) return fail(CLV_EHIP, "no HIP device visible");
+  if (device >= count) return fail(CLV_EINVAL, "pnbd: no such device");
+  clv_pnbd* h = new clv_pnbd();
+  h->n = n;
+  h->nb = (n + 255) / 256;
+  DeviceScope ds(device);
+  int rc = [&]() -> int {
+    CLV_HIP(hipGetDevice(&h->device));
+    CLV_HIP(dalloc(&h->d_x, (size_t)n));
+    CLV_HIP(dalloc(&h->d_tx, (size_t)n));
+    CLV_HIP(dalloc(&h->d_T, (size_t)n));
+    if (weights) CLV_HIP(dalloc(&h->d_w, (size_t)n));
+    CLV_HIP(dalloc(&h->d_part, (size_t)h->nb * PNBD_NS));
+    CLV_HIP(dalloc(&h->d_out, (size_t)PNBD_NS));
+    CLV_HIP(hipMemcpy(h->d_x, x, sizeof(int32_t) * n, hipMemcpyHostToDevice));
+    CLV_HIP(hipMemcpy(h->d_tx, t_x, sizeof(double) * n, hipMemcpyHostToDevice));
+    CLV_HIP(hipMemcpy(h->d_T, T, sizeof(double) * n, hipMemcpyHostToDevice));
+    if (weights) CLV_HIP(hipMemcpy(h->d_w, weights, sizeof(double) * n, hipMemcpyHostToDevice));
+    return CLV_OK;
+  }();
+  if (rc != CLV_OK) {
+    clv_pnbd_destroy(h);
+    return rc;
+  }
+  *out = h;
+  return CLV_OK;
+}
+
+void clv_pnbd_destroy(clv_pnbd* h) {
+  if (!h) return;
+  {
+    DeviceScope ds(h->device);
+    (void)hipFree(h->d_x);
+    (void)hipFree(h->d_tx);
+    (void)hipFree(h->d_T);
+    (void)hipFree(h->d_w);
+    (void)hipFree(h->d_part);
+    (void)hipFree(h->d_out);
+  }
+  delete h;
+}
+
+int clv_pnbd_eval(clv_pnbd* h, const double* params, double* sums, int64_t* n_unconverged) {
+  if (!h || !sums) return fail(CLV_EINVAL, "pnbd: null handle or sums");
+  Params p;
+  int rc = check_params(params, &p);
+  if (rc) return rc;
+  DeviceScope ds(h->device);
+  hipLaunchKernelGGL(pnbd_eval_kernel, dim3(grid_for(h->nb)), dim3(256), 0, nullptr, (const int32_t*)h->d_x,
+                     (const double*)h->d_tx, (const double*)h->d_T, (const double*)h->d_w, h->n, h->nb, p, h->d_part);
+  CLV_HIP(hipGetLastError());
+  hipLaunchKernelGGL(pnbd_final_kernel, dim3(PNBD_NS, 1), dim3(256), 0, nullptr, (const double*)h->d_part, h->nb,
+                     PNBD_NS, h->d_out);
+  CLV_HIP(hipGetLastError());
+  double res[PNBD_NS];
+  CLV_HIP(hipMemcpy(res, h->d_out, sizeof(res), hipMemcpyDeviceToHost));
+  for (int k = 0; k < 6; ++k) sums[k] = res[k];
+  if (n_unconverged) *n_unconverged = (int64_t)res[6];
+  return CLV_OK;
+}
+
+int clv_pnbd_customers(clv_pnbd* h, const double* params, double t_star, double* out) {
+  if (!h || !out) return fail(CLV_EINVAL, "pnbd: null handle or output");
+  Params p;
+  int rc = check_params(params, &p);
+  if (rc) return rc;
+  if (!(t_star >= 0.0) || !std::isfinite(t_star)) return fail(CLV_EINVAL, "pnbd: t_star must be >= 0 and finite");
+  DeviceScope ds(h->device);
+  DevBuf bo;
+  CLV_HIP(hipMalloc(&bo.p, sizeof(double) * 3 * (size_t)h->n));
+  hipLaunchKernelGGL(pnbd_customers_kernel, dim3(grid_for(h->nb)), dim3(256), 0, nullptr, (const int32_t*)h->d_x,
+                     (const double*)h->d_tx, (const double*)h->d_T, h->n, p, t_star, bo.as<double>());
+  CLV_HIP(hipGetLastError());
+  CLV_HIP(hipMemcpy(out, bo.p, sizeof(double) * 3 * (size_t)h->n, hipMemcpyDeviceToHost));
+  return CLV_OK;
+}
+
+int clv_pnbd_track(int32_t device, int64_t n, const double* birth_week, const double* times, int32_t n_times,
+                   const double* params, double* cum) {
+  if (n <= 0 || n_times < 1 || n_times > 65535) return fail(CLV_EINVAL, "pnbd: n must be >= 1 and n_times in 1..65535");
+  if (!birth_week || !times || !cum) return fail(CLV_EINVAL, "pnbd: null argument");
+  Params p;
+  int rc = check_params(params, &p);
+  if (rc) return rc;
+  for (int64_t i = 0; i < n; ++i)
+    if (!std::isfinite(birth_week[i])) return fail(CLV_EINVAL, "pnbd: non-finite birth_week");
+  for (int32_t j = 0; j < n_times; ++j)
+    if (!std::isfinite(times[j])) return fail(CLV_EINVAL, "pnbd: non-finite time");
+  DeviceScope ds(device);
+  const int64_t nb = (n + 255) / 256;
+  DevBuf bb, bt, bp, bo;
+  CLV_HIP(hipMalloc(&bb.p, sizeof(double) * (size_t)n));
+  CLV_HIP(hipMalloc(&bt.p, sizeof(double) * (size_t)n_times));
+  CLV_HIP(hipMalloc(&bp.p, sizeof(double) * (size_t)n_times * (size_t)nb));
+  CLV_HIP(hipMalloc(&bo.p, sizeof(double) * (size_t)n_times));
+  CLV_HIP(hipMemcpy(bb.p, birth_week, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
+  CLV_HIP(hipMemcpy(bt.p, times, sizeof(double) * (size_t)n_times, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(pnbd_track_kernel, dim3(grid_for(nb), (unsigned)n_times), dim3(256), 0, nullptr,
+                     bb.as<const double>(), bt.as<const double>(), n, nb, p, bp.as<double>());
+  CLV_HIP(hipGetLastError());
+  hipLaunchKernelGGL(pnbd_final_kernel, dim3(1, (unsigned)n_times), dim3(256), 0, nullptr, bp.as<const double>(), nb, 1,
+                     bo.as<double>());
+  CLV_HIP(hipGetLastError());
+  CLV_HIP(hipMemcpy(cum, bo.p, sizeof(double) * (size_t)n_times, hipMemcpyDeviceToHost));
+  return CLV_OK;
+}
+
+}  // extern "C"
