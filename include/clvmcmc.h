@@ -386,6 +386,48 @@ int clv_chain_total_loglik(int32_t device, const double* level1, int64_t n_draws
                            const int32_t* x, const double* T_cal, double* mean_total);
 int clv_chain_total_loglik_sampler(clv_sampler* s, double* mean_total);
 
+/* ---- Posterior customer lifetime value and customer equity (csrc/ltv.hip) ----
+ * What Abe (2015) derives from the level-1 draws.  Per stacked draw and customer, with
+ * a = mu + delta (delta the continuous discount rate per time unit of the data), H the horizon in
+ * that unit (infinity allowed) and m the value per transaction — eta * value_scale for width 5,
+ * monetary[i] (1 when monetary is NULL: discounted expected transactions, "DERT") for width 4:
+ *   value    = (lambda m) / a                      H infinite (multiply, divide: no other rounding)
+ *            = ((lambda m) (-expm1(-(a H)))) / a   H finite
+ *   residual = z value                             the value left after T_cal
+ * out_customers [n][CLV_N_LTV_STATS], over the draws: mean (sum in draw order / n_draws), sd
+ * (numpy's std, ddof 1: NaN at one draw) and numpy-'linear' 2.5 / 50 / 97.5 percentiles of value
+ * and of residual; the means of z, of 1 / (periods_per_year mu) (expected lifetime in years) and of
+ * exp(-periods_per_year mu) (one-year survival).
+ * out_draws [n_draws][CLV_N_LTV_DRAW_STATS], over the customers: equity = sum residual,
+ * value_total = sum value, n_alive = sum z, mu_share = (sum mu / a) / n — every sum in the fixed
+ * order of clv_pnbd_eval (zero-padded 256-customer blocks by the 256-tree, the block partials by
+ * the same scheme), so the bits do not depend on the launch geometry or the customer batch.
+ * CLV_EINVAL before any device call: a bad level-1 shape (n_draws, n < 1, width not 4 or 5, more
+ * than 2^22 stacked draws), delta negative or not finite, horizon <= 0 or NaN, value_scale or
+ * periods_per_year not finite, monetary given with width 5, a null pointer.  The _sampler variant
+ * uses the draws a CLV_SINK_FULL sampler holds in HBM (CLV_ESTATE as clv_predict_sampler). */
+enum {
+  CLV_LTV_VALUE_MEAN = 0, CLV_LTV_VALUE_SD, CLV_LTV_VALUE_P025, CLV_LTV_VALUE_P50, CLV_LTV_VALUE_P975,
+  CLV_LTV_RESIDUAL_MEAN, CLV_LTV_RESIDUAL_SD, CLV_LTV_RESIDUAL_P025, CLV_LTV_RESIDUAL_P50, CLV_LTV_RESIDUAL_P975,
+  CLV_LTV_P_ALIVE, CLV_LTV_LIFETIME_YRS, CLV_LTV_SURVIVAL_1YR, CLV_N_LTV_STATS
+};
+enum {
+  CLV_LTV_DRAW_EQUITY = 0, CLV_LTV_DRAW_VALUE_TOTAL, CLV_LTV_DRAW_N_ALIVE, CLV_LTV_DRAW_MU_SHARE,
+  CLV_N_LTV_DRAW_STATS
+};
+int clv_lifetime_value(int32_t device, const double* level1, int64_t n_draws, int64_t n, int32_t width,
+                       const double* monetary /* NULL or [n] */, double delta, double horizon /* inf allowed */,
+                       double value_scale, double periods_per_year, double* out_customers, double* out_draws);
+int clv_lifetime_value_sampler(clv_sampler* s, const double* monetary, double delta, double horizon,
+                               double value_scale, double periods_per_year, double* out_customers,
+                               double* out_draws);
+/* The limits of csrc/ltv.hip: out[0] customers per reduction block (256), out[1] draws per LDS
+ * tile of the transposing pass, out[2] keys per sort batch, out[3] the most stacked draws, out[4]
+ * draws per LDS tile of the sd kernel.  The
+ * environment variable CLV_LTV_BATCH (customers, rounded up to whole blocks) lowers the customer
+ * batch: a test knob, the results do not depend on it. */
+int clv_ltv_info(int64_t* out);
+
 /* ---- Convergence diagnostics on device (csrc/diag.hip) ----
  * The reference checks convergence with ArviZ on its level-2 draws (bivariate/analysis_abe.py:
  * 651-706: az.summary, az.plot_autocorr).  Here a series is m chains x n draws (n >= 8) of one

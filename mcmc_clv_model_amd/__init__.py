@@ -13,16 +13,18 @@ az.summary's table with its rank-normalised ess_bulk, ess_tail and r_hat (level2
 level1_rank_diagnostics, level2_rank_diagnostics).  The classical Pareto/NBD fitted by maximum
 likelihood, the baseline both HB models are measured against (analysis_abe.py:205-217, :426-438), is
 mle.ParetoNBDFitter, a drop-in for what the reference uses of lifetimes', with pnbd_weekly_tracking
-and mape_aggregate (analysis_bi_helpers.py:29).
+and mape_aggregate (analysis_bi_helpers.py:29).  What Abe (2015) derives from the draws, which the
+reference stops short of: every customer's posterior lifetime value, the customer equity and the
+elasticity of CLV to the covariates (lifetime_value, customer_equity, lifetime_value_elasticities).
 
 The per-sweep work runs in hand-written HIP kernels for gfx950 (csrc/), bound through the C
 ABI in include/clvmcmc.h.  There is no CPU fallback.
 """
-from .analysis import (chain_total_loglik, compute_table4, draw_future_transactions,
+from .analysis import (chain_total_loglik, compute_table4, customer_equity, draw_future_transactions,
                        draw_future_transactions_rfm_m, extract_correlation, level1_diagnostics,
                        level1_rank_diagnostics, level2_autocorr, level2_diagnostics, level2_rank_diagnostics,
-                       level2_summary, post_mean_lambdas, post_mean_mus, posterior_weekly_tracking,
-                       summarize_level2, summary_rhat)
+                       level2_summary, lifetime_value, lifetime_value_elasticities, post_mean_lambdas,
+                       post_mean_mus, posterior_weekly_tracking, summarize_level2, summary_rhat)
 from .bivariate import mcmc_draw_parameters
 from .mle import ParetoNBDFitter, mape_aggregate, pnbd_weekly_tracking
 from .trivariate import mcmc_draw_parameters_rfm_m
@@ -32,5 +34,6 @@ __all__ = ["mcmc_draw_parameters", "mcmc_draw_parameters_rfm_m", "draw_future_tr
            "compute_table4", "posterior_weekly_tracking", "level1_diagnostics", "level2_diagnostics",
            "level2_autocorr", "summarize_level2", "extract_correlation", "summary_rhat",
            "level1_rank_diagnostics", "level2_rank_diagnostics", "level2_summary", "ParetoNBDFitter",
-           "pnbd_weekly_tracking", "mape_aggregate"]
+           "pnbd_weekly_tracking", "mape_aggregate", "lifetime_value", "customer_equity",
+           "lifetime_value_elasticities"]
 __version__ = "0.1.0"

@@ -143,6 +143,10 @@ def lib() -> ctypes.CDLL:
         "clv_level1_summary_sampler": (c_int32, [sp, c_double, dp]),
         "clv_chain_total_loglik": (c_int32, [c_int32, dp, c_int64, c_int64, c_int32, POINTER(c_int32), dp, dp]),
         "clv_chain_total_loglik_sampler": (c_int32, [sp, dp]),
+        "clv_lifetime_value": (c_int32, [c_int32, dp, c_int64, c_int64, c_int32, dp, c_double, c_double, c_double,
+                                         c_double, dp, dp]),
+        "clv_lifetime_value_sampler": (c_int32, [sp, dp, c_double, c_double, c_double, c_double, dp, dp]),
+        "clv_ltv_info": (c_int32, [POINTER(c_int64)]),
         "clv_diagnostics": (c_int32, [c_int32, dp, c_int32, c_int64, c_int64, c_int32, c_uint32, dp]),
         "clv_diagnostics_sampler": (c_int32, [sp, c_uint32, dp, dp]),
         "clv_autocorr": (c_int32, [c_int32, dp, c_int32, c_int64, c_int64, c_int32, dp]),
@@ -186,6 +190,25 @@ DIAG_STATS = ("mean", "sd", "mcse", "ess", "rhat", "lag")
 RANK_STATS = ("rhat", "rhat_bulk", "rhat_folded", "ess_bulk", "ess_tail", "ess_q05", "ess_q95", "ess_sd", "mcse_sd",
               "hdi_lo", "hdi_hi", "median", "lag_bulk")
 RANK_LDS_ELEMS = 4080
+
+# Columns of clv_lifetime_value() (include/clvmcmc.h CLV_LTV_* / CLV_LTV_DRAW_*).
+LTV_STATS = ("value_mean", "value_sd", "value_p025", "value_p50", "value_p975", "residual_mean", "residual_sd",
+             "residual_p025", "residual_p50", "residual_p975", "p_alive", "lifetime_yrs", "survival_1yr")
+LTV_DRAW_STATS = ("equity", "value_total", "n_alive", "mu_share")
+LTV_BATCH_ENV = "CLV_LTV_BATCH"  # customers per sort batch (whole 256-customer blocks): the tests' knob
+# The limits of csrc/ltv.hip (clv_ltv_info reports the library's own; tests/test_ltv_cpu.py compares):
+# customers per reduction block, draws per LDS tile of the transposing pass, keys per sort batch,
+# the most stacked draws, draws per LDS tile of the sd kernel.
+LTV_BLOCK, LTV_TILE_DRAWS, LTV_BATCH_KEYS, LTV_MAX_DRAWS, LTV_SD_TILE_DRAWS = 256, 16, 1 << 27, 1 << 22, 32
+
+
+def ltv_info() -> dict:
+    """The limits of csrc/ltv.hip (clv_ltv_info): customers per reduction block, draws per tile of
+    the transposing pass, keys per sort batch, the most stacked draws, draws per tile of the sd kernel."""
+    out = (c_int64 * 5)()
+    check(lib().clv_ltv_info(out))
+    return dict(block=int(out[0]), tile_draws=int(out[1]), batch_keys=int(out[2]), max_draws=int(out[3]),
+                sd_tile_draws=int(out[4]))
 
 
 def exported_symbols():

@@ -18,6 +18,9 @@ Reference functions mirrored (same names, arguments, defaults and return layout)
 * ``level2_summary`` — the nine columns of ``az.summary`` (``analysis_abe.py:690-693``) with the
   rank-normalised ``ess_bulk``, ``ess_tail`` and ``r_hat``; ``level1_rank_diagnostics`` /
   ``level2_rank_diagnostics`` give every rank-normalised statistic (``clv_rank_diagnostics``).
+* ``lifetime_value``, ``customer_equity``, ``lifetime_value_elasticities`` — what Abe (2015) derives
+  from the level-1 draws and the reference leaves out: every customer's posterior lifetime value,
+  the value of the customer base and the elasticity of CLV to the covariates (``csrc/ltv.hip``).
 
 The per-customer / per-draw work runs in ``csrc/analysis.hip`` through the C ABI (``clv_predict``,
 ``clv_track``, ``clv_level1_summary``, ``clv_chain_total_loglik``); the host only reshapes and
@@ -40,7 +43,8 @@ from .sampler import resolve_seed
 __all__ = ["draw_future_transactions", "draw_future_transactions_rfm_m", "post_mean_lambdas", "post_mean_mus",
            "chain_total_loglik", "compute_table4", "level1_summary", "posterior_weekly_tracking",
            "level1_diagnostics", "level2_diagnostics", "level2_autocorr", "summarize_level2", "extract_correlation",
-           "summary_rhat", "level1_rank_diagnostics", "level2_rank_diagnostics", "level2_summary"]
+           "summary_rhat", "level1_rank_diagnostics", "level2_rank_diagnostics", "level2_summary",
+           "lifetime_value", "customer_equity", "lifetime_value_elasticities"]
 
 
 def _stacked_level1(level1_chains) -> np.ndarray:
@@ -201,6 +205,141 @@ def posterior_weekly_tracking(draws, birth_week, times, seed: Optional[int] = 0,
     out = np.empty(t.shape[0], np.float64)
     check(L.clv_track(int(device), dptr(a), nd, n, w, dptr(b), dptr(t), t.shape[0], resolve_seed(seed), dptr(out)))
     return out
+
+
+# ---- customer lifetime value and customer equity (csrc/ltv.hip) --------------------------------
+def ltv_params(discount_rate=0.15, periods_per_year=52.0, horizon=None, omega2=0.0) -> dict:
+    """The scalars clv_lifetime_value takes, validated (ValueError) on the host: delta =
+    log1p(discount_rate) / periods_per_year, horizon (None = infinite), value_scale = exp(omega2 / 2)."""
+    r, ppy, w2 = float(discount_rate), float(periods_per_year), float(omega2)
+    if not (np.isfinite(r) and r >= 0.0):
+        raise ValueError(f"discount_rate must be finite and >= 0 (got {discount_rate!r})")
+    if not (np.isfinite(ppy) and ppy > 0.0):
+        raise ValueError(f"periods_per_year must be finite and > 0 (got {periods_per_year!r})")
+    if not np.isfinite(w2):
+        raise ValueError(f"omega2 must be finite (got {omega2!r})")
+    h = np.inf if horizon is None else float(horizon)
+    if np.isnan(h) or h <= 0.0:
+        raise ValueError(f"horizon must be > 0 or None for an infinite one (got {horizon!r})")
+    with np.errstate(over="ignore"):
+        scale = float(np.exp(w2 / 2.0))
+    if not np.isfinite(scale):
+        raise ValueError(f"exp(omega2 / 2) overflows (omega2 = {omega2!r})")
+    return dict(delta=float(np.log1p(r) / ppy), horizon=h, value_scale=scale, periods_per_year=ppy)
+
+
+def ltv_monetary(monetary, n: int, width: int) -> Optional[np.ndarray]:
+    """The per-customer value per transaction of a width-4 (bivariate) run as a float64 [n] array."""
+    if monetary is None:
+        return None
+    if width == 5:
+        raise ValueError("monetary is for the bivariate model's draws: the trivariate model's value per "
+                         "transaction is its eta column (scaled through omega2)")
+    m = np.ascontiguousarray(np.asarray(monetary, dtype=np.float64))
+    if m.shape != (n,):
+        raise ValueError(f"monetary must have one entry per customer ({n}); got shape {m.shape}")
+    if not np.isfinite(m).all():
+        raise ValueError("monetary must be finite")
+    return m
+
+
+def ltv_frames(cust: np.ndarray, per_draw: np.ndarray, par: dict) -> dict:
+    return dict(customers=pd.DataFrame(cust, columns=list(_lib.LTV_STATS)),
+                draws=pd.DataFrame(per_draw, columns=list(_lib.LTV_DRAW_STATS)),
+                delta=par["delta"], horizon=par["horizon"])
+
+
+def lifetime_value(draws: Dict[str, Any], *, discount_rate: float = 0.15, periods_per_year: float = 52.0,
+                   horizon: Optional[float] = None, monetary=None, omega2: float = 0.0,
+                   device: int = -1) -> Dict[str, Any]:
+    """Posterior customer lifetime value and customer equity from the level-1 draws, on the GPU
+    (``csrc/ltv.hip``, ``clv_lifetime_value``): Abe (2015)'s ``CLV = eta lambda / (mu + delta)`` per
+    draw and customer, summarised per customer over the draws and per draw over the customers.
+
+    ``delta = log1p(discount_rate) / periods_per_year`` is the continuous discount rate per time unit
+    of the data (15 % a year on weekly data: 0.0027); ``horizon`` (that unit; None = infinite) cuts
+    the value at ``H``: ``value = lambda m (1 - exp(-(mu + delta) H)) / (mu + delta)``, the discounted
+    expected value of a customer alive at time 0; ``residual = z value`` is what is left after
+    ``T_cal``.  ``m``, the value per transaction, is ``eta exp(omega2 / 2)`` for the trivariate model
+    (eta is the median of the log-normal spend, ``omega2`` the sampler's var(log_s): 0 keeps eta) and
+    ``monetary`` (one entry per customer; default 1: discounted expected transactions, the DERT of
+    Fader, Hardie & Lee 2005) for the bivariate one.
+
+    Returns ``{"customers": DataFrame, one row per customer, columns _lib.LTV_STATS (mean, sd,
+    2.5 / 50 / 97.5 percentiles of value and of residual, p_alive, lifetime_yrs = E[1 / (ppy mu)],
+    survival_1yr = E[exp(-ppy mu)]), "draws": DataFrame, one row per stacked draw, columns
+    _lib.LTV_DRAW_STATS (equity = sum of residual, value_total, n_alive, mu_share = mean over
+    customers of mu / (mu + delta)), "delta": float, "horizon": float}``.  Unlike plugging posterior
+    means into the formula (``compute_table4``) these are posterior means of the non-linear
+    quantities, with intervals.  Arguments are checked before any device is touched."""
+    par = ltv_params(discount_rate, periods_per_year, horizon, omega2)
+    a = _stacked_level1(draws.get("level_1"))
+    nd, n, w = a.shape
+    m = ltv_monetary(monetary, n, w)
+    L = _L()
+    cust = np.empty((n, len(_lib.LTV_STATS)), np.float64)
+    per_draw = np.empty((nd, len(_lib.LTV_DRAW_STATS)), np.float64)
+    check(L.clv_lifetime_value(int(device), dptr(a), nd, n, w, dptr(m), par["delta"], par["horizon"],
+                               par["value_scale"], par["periods_per_year"], dptr(cust), dptr(per_draw)))
+    return ltv_frames(cust, per_draw, par)
+
+
+def customer_equity(ltv: Dict[str, Any]) -> pd.DataFrame:
+    """The value of the customer base: one row with mean, sd (ddof 1) and the 2.5 / 50 / 97.5
+    percentiles over the draws of ``equity`` (the value left in the customers after T_cal) and, as
+    ``value_total_*``, of ``value_total`` (the same customers, all alive at time 0).  Host numpy."""
+    row = {}
+    for col, pre in (("equity", ""), ("value_total", "value_total_")):
+        v = ltv["draws"][col].to_numpy()
+        p = np.percentile(v, [2.5, 50.0, 97.5])
+        with np.errstate(invalid="ignore", divide="ignore"):
+            sd = v.std(ddof=1) if v.size > 1 else np.nan
+        row.update({pre + "mean": v.mean(), pre + "sd": sd, pre + "p025": p[0], pre + "p50": p[1], pre + "p975": p[2]})
+    return pd.DataFrame([row])
+
+
+ELASTICITY_COMPONENTS = ("purchase_rate", "lifetime", "spend", "total")
+
+
+def lifetime_value_elasticities(draws: Dict[str, Any], covariates, *, discount_rate: float = 0.15,
+                                periods_per_year: float = 52.0, ltv: Optional[Dict[str, Any]] = None,
+                                device: int = -1) -> pd.DataFrame:
+    """Abe (2015)'s decomposition of the elasticity of CLV to each covariate, per draw s and covariate
+    k (the intercept excluded): ``purchase_rate = beta_lambda,k``, ``lifetime = -beta_mu,k
+    mu_share_s``, ``spend = beta_eta,k`` (0 for the bivariate model) and their ``total`` — d log CLV /
+    d x_k of ``CLV = eta lambda / (mu + delta)`` averaged over the customers, which holds for the
+    infinite horizon only.  beta comes from ``draws["level_2"]`` (rows ``[beta[:, 0] (K), beta[:, 1]
+    (K), (beta[:, 2] (K)), Sigma's upper triangle]``, K = len(covariates) + 1), ``mu_share`` from
+    ``ltv["draws"]`` (:func:`lifetime_value`, computed here on the GPU when ``ltv`` is not given).
+    Returns a DataFrame indexed by (covariate, component) with mean, p025 and p975 over the draws."""
+    covariates = list(covariates)
+    K = len(covariates) + 1
+    l2 = np.concatenate([np.asarray(c, dtype=np.float64) for c in draws["level_2"]], axis=0)
+    if l2.ndim != 2:
+        raise ValueError("level_2 draws must be (n_draws, n_params) per chain")
+    D = {2 * K + 3: 2, 3 * K + 6: 3}.get(l2.shape[1])
+    if D is None:
+        raise ValueError(f"level_2 rows of width {l2.shape[1]} do not fit {len(covariates)} covariates plus the "
+                         f"intercept (expected {2 * K + 3} or {3 * K + 6})")
+    if ltv is None:
+        ltv = lifetime_value(draws, discount_rate=discount_rate, periods_per_year=periods_per_year, device=device)
+    if np.isfinite(ltv.get("horizon", np.inf)):
+        raise ValueError("the elasticity decomposition holds for the infinite horizon: ltv was computed with "
+                         f"horizon = {ltv['horizon']}")
+    share = ltv["draws"]["mu_share"].to_numpy()
+    if share.shape[0] != l2.shape[0]:
+        raise ValueError(f"ltv has {share.shape[0]} draws, level_2 has {l2.shape[0]}")
+    rows, index = [], []
+    for k, name in enumerate(covariates, start=1):
+        rate = l2[:, k]
+        life = -l2[:, K + k] * share
+        spend = l2[:, 2 * K + k] if D == 3 else np.zeros_like(rate)
+        for comp, v in zip(ELASTICITY_COMPONENTS, (rate, life, spend, rate + life + spend)):
+            p = np.percentile(v, [2.5, 97.5])
+            rows.append((v.mean(), p[0], p[1]))
+            index.append((name, comp))
+    idx = pd.MultiIndex.from_arrays([[i[0] for i in index], [i[1] for i in index]], names=["covariate", "component"])
+    return pd.DataFrame(rows, columns=["mean", "p025", "p975"], index=idx)
 
 
 # ---- convergence diagnostics (csrc/diag.hip) -------------------------------------------------

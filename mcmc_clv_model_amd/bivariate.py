@@ -23,6 +23,10 @@ line and return layout (bivariate/mcmc.py:437-504); the sweeps run on the GPU
   the same and adds ``"level_1_rank"``, ``"level_2_rank"`` (rank-normalised R-hat, bulk and tail ESS,
   MCSE of the sd, HDI, median: ``analysis.level1_rank_diagnostics`` / ``level2_rank_diagnostics``)
   and ``"level_2_summary"``, the nine columns of ``az.summary`` (``analysis.level2_summary``).
+* ``lifetime_value``: True, or a dict of ``analysis.lifetime_value``'s keywords (``discount_rate``,
+  ``periods_per_year``, ``horizon``, ``monetary``, ``omega2``), adds ``out["lifetime_value"]``: the
+  posterior customer lifetime value per customer and the customer equity per draw, computed on the
+  GPU from the draws still in HBM (``csrc/ltv.hip``; ``draw_sink="full"`` only).  None changes nothing.
 """
 from __future__ import annotations
 
@@ -39,7 +43,7 @@ def mcmc_draw_parameters(cal_cbs, covariates: Optional[Sequence[str]] = None, mc
                          trace: int = 100, n_mh_steps: int = 20, *, draw_sink: str = "full",
                          rng: str = "philox", device: int = -1, replay_tape=None,
                          replay_sweeps: Optional[int] = None, devices: Optional[Sequence[int]] = None,
-                         shard: str = "auto", exchange: str = "auto", diagnostics=False):
+                         shard: str = "auto", exchange: str = "auto", diagnostics=False, lifetime_value=None):
     """Run the Abe (2009) Gibbs/MH sampler on calibration CBS (bivariate/mcmc.py:437).
 
     Returns dict(level_1=[(n_draws, N, 4) per chain: lambda, mu, tau, z],
@@ -57,4 +61,4 @@ def mcmc_draw_parameters(cal_cbs, covariates: Optional[Sequence[str]] = None, mc
     return fit(p, mcmc=mcmc, burnin=burnin, thin=thin, chains=chains, seed=seed, trace=trace,
                n_mh_steps=n_mh_steps, draw_sink=draw_sink, rng=rng, device=device,
                replay_tape=replay_tape, replay_sweeps=replay_sweeps, devices=devices, shard=shard,
-               exchange=exchange, diagnostics=diagnostics)
+               exchange=exchange, diagnostics=diagnostics, lifetime_value=lifetime_value)

@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "internal.h"
+#include "percentile.h"
 #include "philox.h"
 
 using namespace clv;
@@ -246,28 +247,6 @@ __global__ __launch_bounds__(256) void sums_mean_kernel(const double* sums, int 
     for (int c = 0; c < n_chains; ++c) acc += sums[((int64_t)c * CLV_N_SUM_STATS + stat[k]) * n + i];
     out[i * CLV_N_L1_STATS + dst[k]] = (k == 5 && D != 3) ? 0.0 : acc / tot;
   }
-}
-
-// numpy.percentile(a, q, method='linear') of a sorted segment (numpy/lib/_function_base_impl.py:
-// virtual index (n-1) q, floor/next neighbours, _lerp with the t >= 0.5 branch); float32 segments
-// (the percentile store) are widened to double before the interpolation, as numpy would on them.
-template <class T>
-__device__ double np_percentile_sorted(const T* a, int64_t n, double q_percent) {
-  const double q = q_percent / 100.0;
-  const double v = (double)(n - 1) * q;
-  int64_t prev, next;
-  if (v >= (double)(n - 1)) {
-    prev = next = n - 1;
-  } else if (v < 0.0) {
-    prev = next = 0;
-  } else {
-    prev = (int64_t)floor(v);
-    next = prev + 1;
-  }
-  const double gamma = v - floor(v);
-  const double lo = (double)a[prev], hi = (double)a[next];
-  const double diff = hi - lo;
-  return gamma >= 0.5 ? hi - diff * (1.0 - gamma) : lo + diff * gamma;
 }
 
 template <class T>

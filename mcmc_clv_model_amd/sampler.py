@@ -435,6 +435,20 @@ class HipSampler:
                 out["level_2_summary"] = A.level2_summary_frame(o2, r2, param_names, hdi_prob)
         return out
 
+    def lifetime_value(self, *, discount_rate: float = 0.15, periods_per_year: float = 52.0, horizon=None,
+                       monetary=None, omega2: float = 0.0) -> dict:
+        """clv_lifetime_value_sampler: analysis.lifetime_value (posterior customer lifetime value per
+        customer, customer equity per draw) of the draws this sampler holds in HBM, without the
+        host round trip; the same bits as the host-array route."""
+        from . import analysis as A
+        par = A.ltv_params(discount_rate, periods_per_year, horizon, omega2)
+        m = A.ltv_monetary(monetary, self.n, self.D + 2)
+        cust = np.empty((self.n, len(_lib.LTV_STATS)), np.float64)
+        per_draw = np.empty((self.chains * self.n_draws, len(_lib.LTV_DRAW_STATS)), np.float64)
+        check(self._L.clv_lifetime_value_sampler(self.h, dptr(m), par["delta"], par["horizon"], par["value_scale"],
+                                                 par["periods_per_year"], dptr(cust), dptr(per_draw)))
+        return A.ltv_frames(cust, per_draw, par)
+
     def chain_total_loglik(self) -> float:
         out = ctypes.c_double()
         check(self._L.clv_chain_total_loglik_sampler(self.h, ctypes.byref(out)))
@@ -548,14 +562,17 @@ def _assemble(D: int, chains: int, l1, l2, ll, sums, k: int, n_draws: int, draw_
 def fit(p: Problem, *, mcmc: int, burnin: int, thin: int, chains: int, seed, trace: int, n_mh_steps: int,
         draw_sink: str = "full", rng: str = "philox", device: int = -1, replay_tape=None,
         replay_sweeps: Optional[int] = None, devices: Optional[Sequence[int]] = None, shard: str = "auto",
-        exchange: str = "auto", diagnostics=False) -> dict:
+        exchange: str = "auto", diagnostics=False, lifetime_value=None) -> dict:
     """Run all chains of one problem in one batched launch sequence and return the reference's
     output layout (bi:499-504).  ``devices`` (two or more): the run is spread over those devices
     in this process (:func:`fit_multi`).  ``diagnostics``: also out["diagnostics"] = {"level_1",
     "level_2"} convergence tables (analysis.level1_diagnostics / level2_diagnostics; full sink
     only), from the sampler's draws in HBM on one device, from the returned arrays on devices[0]
     otherwise; ``diagnostics="rank"`` adds "level_1_rank", "level_2_rank" and "level_2_summary"
-    (analysis.level1_rank_diagnostics / level2_rank_diagnostics / level2_summary)."""
+    (analysis.level1_rank_diagnostics / level2_rank_diagnostics / level2_summary).
+    ``lifetime_value``: True or a dict of analysis.lifetime_value's keywords adds
+    out["lifetime_value"] (customer lifetime value per customer, customer equity per draw; full
+    sink only), routed as the diagnostics are."""
     if chains < 1:
         raise ValueError("chains must be >= 1")
     if thin < 1:
@@ -564,6 +581,7 @@ def fit(p: Problem, *, mcmc: int, burnin: int, thin: int, chains: int, seed, tra
         raise ValueError(f"diagnostics must be False, True or 'rank' (got {diagnostics!r})")
     if diagnostics and draw_sink != "full":
         raise ValueError("diagnostics=True needs draw_sink='full' (analysis.summary_rhat serves a summary run)")
+    ltv_kw = lifetime_value_kwargs(lifetime_value, draw_sink)
     if devices is not None:
         devices = [int(d) for d in devices]
         if not devices:
@@ -573,7 +591,7 @@ def fit(p: Problem, *, mcmc: int, burnin: int, thin: int, chains: int, seed, tra
                 raise ValueError("devices= runs need rng='philox' (the replay tape is a single-device test mode)")
             out = fit_multi(p, mcmc=mcmc, burnin=burnin, thin=thin, chains=chains, seed=seed, trace=trace,
                             n_mh_steps=n_mh_steps, draw_sink=draw_sink, devices=devices, shard=shard,
-                            exchange=exchange)
+                            exchange=exchange, lifetime_value=lifetime_value)
             if diagnostics:
                 from . import analysis as A
                 out["diagnostics"] = dict(level_1=A.level1_diagnostics(out, device=devices[0]),
@@ -603,9 +621,34 @@ def fit(p: Problem, *, mcmc: int, burnin: int, thin: int, chains: int, seed, tra
                         lambda: s.level1_summary(_lib.SUMMARY_MU_CAP))
         if diagnostics:
             out["diagnostics"] = s.diagnostics(rank=diagnostics == "rank")
+        if ltv_kw is not None:
+            out["lifetime_value"] = s.lifetime_value(**ltv_kw)
         return out
     finally:
         s.close()
+
+
+def lifetime_value_kwargs(lifetime_value, draw_sink: str):
+    """The ``lifetime_value=`` keyword of the fit functions as analysis.lifetime_value's keywords
+    (None: not asked for), validated before the run starts."""
+    if lifetime_value is None or lifetime_value is False:
+        return None
+    if lifetime_value is True:
+        kw = {}
+    elif isinstance(lifetime_value, dict):
+        kw = dict(lifetime_value)
+    else:
+        raise ValueError(f"lifetime_value must be None, True or a dict of keywords (got {lifetime_value!r})")
+    if draw_sink != "full":
+        raise ValueError("lifetime_value needs draw_sink='full' (it is computed from the level-1 draws)")
+    from . import analysis as A
+    allowed = ("discount_rate", "periods_per_year", "horizon", "monetary", "omega2")
+    bad = sorted(set(kw) - set(allowed))
+    if bad:
+        raise ValueError(f"lifetime_value takes the keywords {allowed} (got {bad})")
+    A.ltv_params(kw.get("discount_rate", 0.15), kw.get("periods_per_year", 52.0), kw.get("horizon"),
+                 kw.get("omega2", 0.0))
+    return kw
 
 
 def multi_plan(chains: int, n_dev: int, draw_sink: str, shard: str = "auto"):
@@ -628,7 +671,8 @@ def multi_plan(chains: int, n_dev: int, draw_sink: str, shard: str = "auto"):
 
 
 def fit_multi(p: Problem, *, mcmc: int, burnin: int, thin: int, chains: int, seed, trace: int, n_mh_steps: int,
-              draw_sink: str, devices: Sequence[int], shard: str = "auto", exchange: str = "auto") -> dict:
+              draw_sink: str, devices: Sequence[int], shard: str = "auto", exchange: str = "auto",
+              lifetime_value=None) -> dict:
     """One run over several devices of this process (SURVEY §8b ``devices=``), same output as the
     single-device run, bit for bit:
 
@@ -640,8 +684,18 @@ def fit_multi(p: Problem, *, mcmc: int, burnin: int, thin: int, chains: int, see
       (:class:`HipGroup`: peer stores from persistent kernels where every grid fits at once, else
       device-to-device copies; ``exchange`` forces one);
     * ``"auto"``: chains when they divide evenly over the devices (and the sink is not
-      "summary+pct", whose percentiles pool all chains), else customers."""
+      "summary+pct", whose percentiles pool all chains), else customers.
+
+    ``lifetime_value``: as :func:`fit`, computed from the returned arrays on ``devices[0]``."""
     import threading
+    ltv_kw = lifetime_value_kwargs(lifetime_value, draw_sink)
+
+    def finish(out):
+        if ltv_kw is not None:
+            from . import analysis as A
+            out["lifetime_value"] = A.lifetime_value(out, device=int(devices[0]), **ltv_kw)
+        return out
+
     n_dev = len(devices)
     shard, groups = multi_plan(chains, n_dev, draw_sink, shard)
     seed = resolve_seed(seed)
@@ -683,7 +737,7 @@ def fit_multi(p: Problem, *, mcmc: int, burnin: int, thin: int, chains: int, see
             if draw_sink == "summary":
                 rs = [sm.read_summary() for sm in samplers]
                 sums, k = np.concatenate([r[0] for r in rs], axis=0), rs[0][1]
-            return _assemble(p.D, chains, l1, l2, ll, sums, k, samplers[0].n_draws, draw_sink, None)
+            return finish(_assemble(p.D, chains, l1, l2, ll, sums, k, samplers[0].n_draws, draw_sink, None))
         finally:
             for sm in samplers:
                 sm.close()
@@ -722,7 +776,7 @@ def fit_multi(p: Problem, *, mcmc: int, burnin: int, thin: int, chains: int, see
         out = _assemble(p.D, chains, l1, l2, ll, sums, k, shards[0].n_draws, draw_sink,
                         lambda: np.concatenate([sh.level1_summary(_lib.SUMMARY_MU_CAP) for sh in shards], axis=0))
         out["exchange"] = group.exchange
-        return out
+        return finish(out)
     finally:
         if group is not None:
             group.close()
