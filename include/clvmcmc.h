@@ -169,7 +169,14 @@ int clv_clock_ghz(clv_sampler* s, double* ghz);
  * (the governor moves on a millisecond scale).  Measurement only.  Synchronizes the stream. */
 int clv_clock_probe(clv_sampler* s, double us, double* ghz);
 /* How clv_run launches: out[6] = (persistent 0/1, persistent-kernel workgroups per CU, CUs,
- * workgroups per sweep, reserved (0), reserved (0)).
+ * logical workgroups per sweep (one per customer block, + one level-2 workgroup per chain when
+ * persistent), workgroups dispatched, layout of the persistent grid: 0 none, 1 block, 2 split,
+ * -1 block after a split launch aborted).
+ * Split layout (bivariate, world_size == 1, n_mh_steps <= 20, at most 256 blocks): 512-thread
+ * workgroups of six customer and two helper wavefronts, one per CU, chosen where that grid is
+ * resident whole (clv_debug_split_choice) and the block layout would put two workgroups on a CU;
+ * CLV_PERSIST_LAYOUT = block | split forces one (split only where it can run).  Same results to
+ * the bit.
  * Persistent = one launch for all of a clv_run's sweeps with every customer block resident, chosen
  * at create when world_size == 1, Philox mode, every workgroup fits at once (with a residency
  * margin) and few enough CUs hold two of them for it to pay (clv_debug_persist_choice), unless
@@ -322,6 +329,19 @@ int clv_debug_persist_fits(int64_t grid_wgs, int32_t blocks_per_cu, int32_t n_cu
  * crossover); CLV_PERSISTENT=1 forces it wherever it fits, =0 never. */
 int clv_debug_persist_choice(int32_t D, int32_t K, int32_t n_chains, int64_t grid_wgs, int32_t blocks_per_cu,
                              int32_t n_cu);
+/* Host only, the split layout of the persistent grid (n_chains chains of nb blocks of 256 customers,
+ * 1 <= nb <= 256; a chain's 4 nb wave rows of 64 customers dealt six at a time to its workgroups).
+ * clv_debug_split_fits: 1 if its n_chains x (ceil(2 nb / 3) + 1) one-per-CU workgroups are taken as
+ * resident at once on n_cu CUs admitting blocks_per_cu (>= 1) each, less one CU per 64.
+ * clv_debug_split_choice: fits, and the block layout would double up (n_chains x (nb + 1) > n_cu).
+ * clv_debug_split_layout: out[physical workgroup][8] = chain, first wave row (-1: the chain's
+ * level-2 workgroup), wave rows hosted, then the workgroup's two hand-off records as (kind, block):
+ * kind 1 = four rows summed into the block's slot, 2 = rows 0, 1 summed into the block's slot (the
+ * prefix of a split block), 3 = rows 2, 3 of a split block as two extension records, -1 = none;
+ * out[.][7] = the first extension record's index in the chain's record table (kind 3), else -1. */
+int clv_debug_split_fits(int32_t n_chains, int32_t nb, int32_t blocks_per_cu, int32_t n_cu);
+int clv_debug_split_choice(int32_t n_chains, int32_t nb, int32_t blocks_per_cu, int32_t n_cu);
+int clv_debug_split_layout(int32_t n_chains, int32_t nb, int32_t* out);
 
 /* ---- In-process multi-device runs (SURVEY.md §8b devices=, §8e) ----
  * A group drives the n shards of one problem from one host thread: shards[r] = the sampler of rank

@@ -358,6 +358,34 @@ bool clv::persist_worth(int D, int K, int n_chains, int64_t grid_wgs, int n_cu) 
   return n_cu > 0 && grid_wgs > 0;
 }
 
+// The split layout's residency rule.  Its 512-thread workgroups fill a CU each (8 waves of up to 256
+// VGPRs, ~95 KB of LDS), so the grid of chains x (split_wgs(nb) + 1) workgroups needs that many CUs
+// free at once, and the dispatcher has nowhere else to put a workgroup: one slot per CU, less a
+// margin of one CU per 64 (4 of 256; c2 and c3 take 252).  The block rule's margin is one slot per 32
+// CUs of two-slot CUs; here a slot is a whole CU, so the same share of the card would leave c2 out.
+// Every wait stays bounded, and a handle whose split launch aborts goes back to the block layout.
+bool clv::persist_split_fits(int n_chains, int nb, int blocks_per_cu, int n_cu) {
+  if (n_chains < 1 || nb < 1 || nb > SPLIT_MAX_NB || blocks_per_cu < 1 || n_cu < 1) return false;
+  const int64_t grid = (int64_t)n_chains * (split_wgs(nb) + 1);
+  const int64_t margin = std::max(1, n_cu / 64);
+  return grid <= n_cu - margin;
+}
+
+// Worth choosing only where the block layout doubles up: with one block workgroup per CU no SIMD
+// holds two customer waves and there is nothing to balance.
+bool clv::persist_split_pays(int n_chains, int nb, int n_cu) { return (int64_t)n_chains * (nb + 1) > n_cu; }
+
+// Chain by chain, each chain's workgroups in order (workgroup p hosts wave rows 6p .. 6p + 5), its
+// level-2 workgroup last: consecutive dispatch positions go round the XCDs, so every chain spreads
+// over all of them.
+std::vector<int32_t> clv::persist_split_layout(int n_chains, int nb) {
+  const int per = split_wgs(nb) + 1;
+  std::vector<int32_t> map((size_t)n_chains * per);
+  for (int c = 0; c < n_chains; ++c)
+    for (int p = 0; p < per; ++p) map[(size_t)c * per + p] = (c << 16) | p;
+  return map;
+}
+
 namespace {
 
 // Persistent grid: which (chain, block) each dispatched workgroup runs.  The grid has more
@@ -558,6 +586,24 @@ int clv_create(const clv_config* cfg, const clv_data* data, const clv_prior* pri
     if ((!env || std::string(env) != "0") && (force || scratch <= PERSIST_SCRATCH_MAX) && persist_grid_fits(grid, s->persist_bpc, s->n_cu) &&
         (force || persist_worth(g.D, g.K, (int)C, grid, s->n_cu)))
       s->persistent = true;
+    // Layout of the persistent grid.  Split (persist_kernel_split: 6 customer + 2 helper wavefronts
+    // per CU) for bivariate models whose sweep's variates fit the pool, where its grid is resident
+    // whole with 0 B of scratch and the block layout would double up; CLV_PERSIST_LAYOUT=block |
+    // split forces one (tests, A/B; split still only where it can run).
+    if (s->persistent && g.D == 2 && g.S <= PRE_STEPS && nb_local <= SPLIT_MAX_NB) {
+      const char* lay = std::getenv("CLV_PERSIST_LAYOUT");
+      const std::string want = lay ? lay : "";
+      if (lay && want != "block" && want != "split")
+        return cleanup_fail(fail(CLV_EINVAL, "CLV_PERSIST_LAYOUT must be block or split"));
+      int bpc = 0;
+      size_t sscratch = SIZE_MAX;
+      if (want != "block" && persist_split_resources(g.D, g.K, &bpc, &sscratch) == hipSuccess && sscratch == 0 &&
+          persist_split_fits((int)C, (int)nb_local, bpc, s->n_cu) &&
+          (want == "split" || persist_split_pays((int)C, (int)nb_local, s->n_cu)))
+        s->split = true;
+      else
+        (void)hipGetLastError();
+    }
   }
   // World size > 1: the same persistent kernel exchanging unit partials with its peers over xGMI
   // (clv_p2p_connect) when the grid fits at once here, as above, and on every rank (the caller
@@ -608,7 +654,8 @@ int clv_create(const clv_config* cfg, const clv_data* data, const clv_prior* pri
     CLV_HIPC(dalloc(&s->d_peers, g.world_size));
   }
   if (s->persistent || s->p2p_capable || s->fx_capable) {  // (fused exchange: the snapshot buffers)
-    CLV_HIPC(dalloc(&s->d_pblock, (size_t)C * std::max(nb_local, 1) * g.stride));
+    // (the split layout's records: the block slots and two more per split block)
+    CLV_HIPC(dalloc(&s->d_pblock, (size_t)C * split_records(std::max((int)nb_local, 1)) * g.stride));
     if (s->persistent) {  // deferred level-2 draws (CLV_DEFER=0: every launch draws its last one)
       const char* env = std::getenv("CLV_DEFER");
       s->defer = !(env && std::string(env) == "0");
@@ -642,6 +689,11 @@ int clv_create(const clv_config* cfg, const clv_data* data, const clv_prior* pri
       std::vector<int32_t> map = persist_wg_map((int)C, (int)nb_local, s->n_cu);
       CLV_HIPC(dalloc(&s->d_wgmap, map.size()));
       CLV_HIPC(hipMemcpy(s->d_wgmap, map.data(), sizeof(int32_t) * map.size(), hipMemcpyHostToDevice));
+    }
+    if (s->split) {
+      std::vector<int32_t> map = persist_split_layout((int)C, (int)nb_local);
+      CLV_HIPC(dalloc(&s->d_wgmap_split, map.size()));
+      CLV_HIPC(hipMemcpy(s->d_wgmap_split, map.data(), sizeof(int32_t) * map.size(), hipMemcpyHostToDevice));
     }
   }
 #ifdef CLV_STAMPS
@@ -762,6 +814,7 @@ void clv_destroy(clv_sampler* s) {
   if (s->d_mail) (void)hipFree(s->d_mail);
   if (s->d_peers) (void)hipFree(s->d_peers);
   if (s->d_wgmap) (void)hipFree(s->d_wgmap);
+  if (s->d_wgmap_split) (void)hipFree(s->d_wgmap_split);
   if (s->own_stream && s->own) (void)hipStreamDestroy(s->own);
   delete s;
 }
@@ -880,8 +933,11 @@ int clv_launch_info(const clv_sampler* s, int64_t* out) {
   out[1] = s->persist_bpc;
   out[2] = s->n_cu;
   out[3] = (int64_t)(s->g.nb_local + (s->persistent ? 1 : 0)) * s->g.n_chains;
-  out[4] = 0;  // (reserved: was the MH-variate producer / consumer chunks, removed in round 4)
-  out[5] = 0;  // (reserved: was the stride kernel's grid, removed)
+  // out[3] counts logical workgroups (one per block, + the level-2 one) in either layout; the
+  // workgroups actually dispatched and the layout (LAYOUT_*; -LAYOUT_BLOCK: block after a split
+  // launch aborted)
+  out[4] = s->split ? (int64_t)(split_wgs(s->g.nb_local) + 1) * s->g.n_chains : out[3];
+  out[5] = !s->persistent ? LAYOUT_NONE : s->split ? LAYOUT_SPLIT : s->split_reverted ? -LAYOUT_BLOCK : LAYOUT_BLOCK;
   return CLV_OK;
 }
 
@@ -1011,7 +1067,7 @@ int clv::persist_launch(clv_sampler* s, int64_t n_sweeps) {
   if (s->slots_dirty) {  // a completed launch leaves every hand-off slot empty; else fill them
     // every hand-off slot empty (all-ones bytes: the sentinel NaN)
     CLV_HIP(hipMemsetAsync(s->d_hyp2, 0xFF, sizeof(double) * 2 * g.n_chains * HS, s->stream));
-    CLV_HIP(hipMemsetAsync(s->d_pblock, 0xFF, sizeof(double) * g.n_chains * g.nb_local * g.stride, s->stream));
+    CLV_HIP(hipMemsetAsync(s->d_pblock, 0xFF, sizeof(double) * g.n_chains * split_records(g.nb_local) * g.stride, s->stream));
     s->slots_dirty = false;
   }
   const size_t sums_bytes = sizeof(double) * (size_t)g.n_chains * CLV_N_SUM_STATS * g.n;
@@ -1034,7 +1090,12 @@ int clv::persist_launch(clv_sampler* s, int64_t n_sweeps) {
   // on the driver's 20-sweep run than the dispatch's own timestamps, same duration to 0.2%)
   if (e0) CLV_HIP(hipEventRecord(e0, s->stream));
   s->host_ns[2] = host_now_ns();
-  CLV_HIP(launch_persist(a, s->sweeps_done + 1, n_sweeps, s->stream, nullptr, nullptr));
+  if (s->split) {
+    a.wg_map = s->d_wgmap_split;
+    CLV_HIP(launch_persist_split(a, s->sweeps_done + 1, n_sweeps, s->stream));
+  } else {
+    CLV_HIP(launch_persist(a, s->sweeps_done + 1, n_sweeps, s->stream, nullptr, nullptr));
+  }
   s->host_ns[3] = host_now_ns();
   if (e1) CLV_HIP(hipEventRecord(e1, s->stream));
   // the launch's end event; timed launches are harvested later (clv_kernel_time or a full slot set)
@@ -1082,7 +1143,13 @@ int clv::persist_wait(clv_sampler* s) {
     if (s->d_sums_prev) CLV_HIP(hipMemcpy(s->d_sums, s->d_sums_prev, sums_bytes, hipMemcpyDeviceToDevice));
     s->slots_dirty = true;
     if (g.world_size > 1) s->p2p_ready = false;  // mail slots are in an unknown state now
-    const std::string diag = take_wait_diag(s);
+    std::string diag = take_wait_diag(s);
+    if (s->split) {  // its one-workgroup-per-CU grid was not resident whole (or a fault): the block
+                     // layout, with its wider margin, for the rest of the handle's life
+      s->split = false;
+      s->split_reverted = true;
+      diag += "; the split layout's launch aborted: this handle uses the block layout from now on";
+    }
     return fail(CLV_EHIP, std::string(g.world_size > 1
                                           ? "persistent sweep kernel: a wait timed out (a peer rank not running, or not all "
                                             "resident?); state unchanged"
@@ -1638,6 +1705,40 @@ int clv_debug_persist_choice(int32_t D, int32_t K, int32_t n_chains, int64_t gri
 
 int clv_debug_persist_fits(int64_t grid_wgs, int32_t blocks_per_cu, int32_t n_cu) {
   return persist_grid_fits(grid_wgs, blocks_per_cu, n_cu) ? 1 : 0;
+}
+
+int clv_debug_split_fits(int32_t n_chains, int32_t nb, int32_t blocks_per_cu, int32_t n_cu) {
+  return persist_split_fits(n_chains, nb, blocks_per_cu, n_cu) ? 1 : 0;
+}
+
+int clv_debug_split_choice(int32_t n_chains, int32_t nb, int32_t blocks_per_cu, int32_t n_cu) {
+  return persist_split_fits(n_chains, nb, blocks_per_cu, n_cu) && persist_split_pays(n_chains, nb, n_cu) ? 1 : 0;
+}
+
+int clv_debug_split_layout(int32_t n_chains, int32_t nb, int32_t* out) {
+  if (!out || n_chains < 1 || nb < 1 || nb > SPLIT_MAX_NB || n_chains >= (1 << 15)) return fail(CLV_EINVAL, "bad arguments");
+  const std::vector<int32_t> m = persist_split_layout(n_chains, nb);
+  const int nwg = split_wgs(nb);
+  for (size_t i = 0; i < m.size(); ++i) {
+    int32_t* o = out + 8 * i;
+    const int p = m[i] & 0xFFFF;
+    o[0] = m[i] >> 16;
+    for (int k = 1; k < 8; ++k) o[k] = -1;
+    if (p == nwg) continue;  // the chain's level-2 workgroup
+    const int r0 = SPLIT_CW * p;
+    o[1] = r0;
+    o[2] = std::min(SPLIT_CW, 4 * nb - r0);
+    // the two records (persist_kernel_split): wavefront 0 writes the first, wavefront 1 the second
+    const int b0 = (p & 1) ? (r0 - 2) / 4 : r0 / 4, b1 = (p & 1) ? (r0 + 2) / 4 : r0 / 4 + 1;
+    o[3] = (p & 1) ? 3 : 1;  // 3: rows 2, 3 into extension records 2 (b / 3), + 1;  1: a whole block's slot
+    o[4] = b0;
+    if (b1 < nb) {
+      o[5] = (p & 1) ? 1 : 2;  // 2: the prefix r0 + r1 into the block's slot
+      o[6] = b1;
+    }
+    o[7] = (p & 1) ? nb + 2 * (b0 / 3) : -1;  // first extension record
+  }
+  return CLV_OK;
 }
 
 int clv_debug_wg_map(int32_t n_chains, int32_t nb, int32_t n_cu, int32_t* out) {

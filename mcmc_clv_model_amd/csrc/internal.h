@@ -25,6 +25,14 @@ int persist_flush(clv_sampler* s);  // the deferred level-2 draw, if one is pend
 // admitting blocks_per_cu of its workgroups each (capi.hip).
 bool persist_grid_fits(int64_t grid_wgs, int blocks_per_cu, int n_cu);
 bool persist_worth(int D, int K, int n_chains, int64_t grid_wgs, int n_cu);
+// The split layout (kernels.hip persist_kernel_split): one workgroup per CU, so a chain of nb
+// blocks takes split_wgs(nb) + 1 CUs.  persist_split_fits: nb within the layout's range and the
+// whole grid resident (its own rule, capi.hip); persist_split_pays: the block layout would put two
+// workgroups on some CU.  persist_split_layout: per physical workgroup the chain and the chain's
+// workgroup index (chain << 16 | p; p = split_wgs(nb): the level-2 workgroup; first wave row 6 p).
+bool persist_split_fits(int n_chains, int nb, int blocks_per_cu, int n_cu);
+bool persist_split_pays(int n_chains, int nb, int n_cu);
+std::vector<int32_t> persist_split_layout(int n_chains, int nb);
 
 // Level-1 draws streamed to a host buffer during the run (drawstream.hip): the pieces a sampler has
 // in flight in the process-wide copy pool, and whether any failed.
@@ -134,6 +142,9 @@ struct clv_sampler {
   int rb_hyper_swaps = 0;           // hyper / hyper_alt swaps since it (its hyper is in hyper_alt if odd)
   bool persistent = false;          // clv_run uses persist_kernel (all workgroups resident)
   int persist_bpc = 0, n_cu = 0;    // persist_kernel occupancy (workgroups per CU), CUs
+  bool split = false;               // the persistent launch uses the split layout (persist_kernel_split)
+  bool split_reverted = false;      // a split launch aborted: block layout for the handle's lifetime
+  int32_t* d_wgmap_split = nullptr; // split grid: linear workgroup -> (chain << 16 | chain's workgroup)
   // world size > 1: persistent kernel with the peer (xGMI) exchange
   bool p2p_capable = false;         // the grid fits at once and the unit partials fit UMAIL
   bool p2p_persist_fits = false;    // (p2p_capable as chosen at create; clv_p2p_set_persistent may clear p2p_capable)

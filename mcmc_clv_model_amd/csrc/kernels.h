@@ -20,6 +20,17 @@ constexpr int MAIL_TAIL = MAX_WORLD;   // peer mail: after the [2][world][chain]
                                        // progress word per rank (the sweep its level-2 side last polled for)
 constexpr int CLK_RING = 1024;         // shader-clock record (SweepArgs::clk): sweeps kept
 constexpr int DIAG_WORDS = 16;         // wait-timeout record (SweepArgs::diag, see kernels.hip report_wait)
+constexpr int PRE_STEPS = 20;         // persistent kernel: MH steps per sweep it can draw ahead into LDS
+// Split layout of the persistent sweep (persist_kernel_split): 512-thread workgroups of six
+// customer wavefronts and two helper wavefronts, a chain's wave rows dealt six at a time.
+constexpr int SPLIT_CW = 6;            // customer wavefronts per workgroup
+constexpr int SPLIT_NT = 512;          // threads per workgroup
+constexpr int SPLIT_MAX_NB = 256;      // one level-2 lane per block
+enum : int { LAYOUT_NONE = 0, LAYOUT_BLOCK = 1, LAYOUT_SPLIT = 2 };
+// Physical customer workgroups per chain: ceil(4 nb / 6).
+__host__ __device__ inline int split_wgs(int nb) { return (2 * nb + 2) / 3; }
+// Hand-off records per chain: the nb block slots, then rows 2 and 3 of every split block (b % 3 == 1).
+__host__ __device__ inline int split_records(int nb) { return nb + 2 * ((nb + 1) / 3); }
 enum : int { WAIT_HYPER = 1, WAIT_BLOCKS = 2, WAIT_P2P_MAIL = 3, WAIT_FX_MAIL = 4 };
 
 // Doubles of peer-mail slots before the progress words.
@@ -161,6 +172,8 @@ hipError_t launch_sweep(const SweepArgs& a, bool replay, hipStream_t st, hipEven
 hipError_t launch_group(const GroupArgs& a, hipStream_t st);
 hipError_t launch_persist(const SweepArgs& a, int64_t s_first, int64_t n_sweeps, hipStream_t st,
                           hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
+hipError_t launch_persist_split(const SweepArgs& a, int64_t s_first, int64_t n_sweeps, hipStream_t st);
+hipError_t persist_split_resources(int D, int K, int* blocks_per_cu, size_t* scratch_bytes);
 hipError_t persist_occupancy(int D, int K, bool p2p, int* blocks_per_cu);
 hipError_t persist_scratch_bytes(int D, int K, bool p2p, size_t* bytes);  // spilled instances: > 0
 // The deferred level-2 draw alone (a.pend_in, no sweeps): one level-2 workgroup per chain.

@@ -207,11 +207,11 @@ __device__ __forceinline__ void block_reduce(double (&v)[NS], double (*red)[NS],
 // at most G of them are live in registers: every element is summed over the lanes in exactly the
 // order of block_reduce (lane l + lane l+32, then row pairs, then the DPP rotate), whatever its
 // partner in the swaps — results are bitwise those of block_reduce on the materialised array.
-template <int NS, int G, int NT = BLOCK, class Gen>
-__device__ __forceinline__ void block_reduce_gen(const Gen& gen, double (*red)[NS], double* out) {
+// Its wavefront part alone: the wave's row of sums into red[wave] (no barrier).
+template <int NS, int G, class Gen>
+__device__ __forceinline__ void wave_reduce_gen(const Gen& gen, double (*red)[NS]) {
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
-  constexpr int NW = NT / 64;
 #pragma unroll
   for (int base = 0; base < NS; base += G) {
     constexpr int GG = G;
@@ -253,6 +253,12 @@ __device__ __forceinline__ void block_reduce_gen(const Gen& gen, double (*red)[N
       }
     }
   }
+}
+
+template <int NS, int G, int NT = BLOCK, class Gen>
+__device__ __forceinline__ void block_reduce_gen(const Gen& gen, double (*red)[NS], double* out) {
+  constexpr int NW = NT / 64;
+  wave_reduce_gen<NS, G>(gen, red);
   __syncthreads();
   if (threadIdx.x < NS) {
     double t = red[0][threadIdx.x];
@@ -1489,7 +1495,6 @@ __device__ __forceinline__ void mh_run(Cust<D, K, CL>& cu, const SlotPhilox& ph,
 // then only the dependent fp64 accept/reject chain.  Steps >= S carry log U = +inf (never taken).
 // The variates live in LDS, one column per lane (each lane reads back only what it wrote: no
 // barrier), not in 60 VGPRs: the persistent kernel's customer path spilled with them in registers.
-constexpr int PRE_STEPS = 20;
 constexpr int PRE_LDS_BYTES = PRE_STEPS * BLOCK * 12;  // float2 (t_l, t_m) + float log U per step and lane
 struct PreVariates {
   float2* t;  // [PRE_STEPS][BLOCK]
@@ -1506,35 +1511,37 @@ __device__ __forceinline__ int opaque_uniform(int x) {
   return x;
 }
 
-template <int NQ = PRE_STEPS / MH_CHUNK_STEPS>
-__device__ __forceinline__ void mh_pre_variates(const SlotPhilox& ph, int S_, const PreVariates& v) {
+// NT: columns of the pool (threads of the workgroup that own one); q0 (wave-uniform): the first
+// chunk drawn here (the split layout's helper waves draw the chunks below it).
+template <int NQ = PRE_STEPS / MH_CHUNK_STEPS, int NT = BLOCK>
+__device__ __forceinline__ void mh_pre_variates(const SlotPhilox& ph, int S_, const PreVariates& v, int q0 = 0) {
   constexpr int MC = MH_CHUNK_STEPS;
   const int S = opaque_uniform(S_);
 #pragma unroll
   for (int q = 0; q < NQ; ++q) {
-    if (q * MC < S) {  // wave-uniform
+    if (q >= q0 && q * MC < S) {  // wave-uniform
       float tl[MC], tm[MC], lu[MC];
       mh_chunk_variates(ph, (uint32_t)q, tl, tm, lu);
       if (q * MC + MC <= S) {  // full chunk
 #pragma unroll
         for (int st = 0; st < MC; ++st) {
           const int k = q * MC + st;
-          v.t[k * BLOCK + v.lane] = make_float2(tl[st], tm[st]);
-          v.u[k * BLOCK + v.lane] = lu[st];
+          v.t[k * NT + v.lane] = make_float2(tl[st], tm[st]);
+          v.u[k * NT + v.lane] = lu[st];
         }
       } else {
 #pragma unroll
         for (int st = 0; st < MC; ++st) {
           const int k = q * MC + st;
-          v.t[k * BLOCK + v.lane] = make_float2(tl[st], tm[st]);
-          v.u[k * BLOCK + v.lane] = k < S ? lu[st] : __builtin_inff();
+          v.t[k * NT + v.lane] = make_float2(tl[st], tm[st]);
+          v.u[k * NT + v.lane] = k < S ? lu[st] : __builtin_inff();
         }
       }
     }
   }
 }
 
-template <int NQ = PRE_STEPS / MH_CHUNK_STEPS, int D, int K, bool CL>
+template <int NQ = PRE_STEPS / MH_CHUNK_STEPS, int NT = BLOCK, int D, int K, bool CL>
 __device__ __forceinline__ void mh_run_pre(Cust<D, K, CL>& cu, const PreVariates& v, double s00, double s11, int S,
                                            const double* exp_tab) {
   constexpr int MC = MH_CHUNK_STEPS;
@@ -1546,8 +1553,8 @@ __device__ __forceinline__ void mh_run_pre(Cust<D, K, CL>& cu, const PreVariates
       float u[MC];
 #pragma unroll
       for (int st = 0; st < MC; ++st) {  // the chunk's LDS reads issued together, ahead of the chain
-        t[st] = v.t[(q * MC + st) * BLOCK + v.lane];
-        u[st] = v.u[(q * MC + st) * BLOCK + v.lane];
+        t[st] = v.t[(q * MC + st) * NT + v.lane];
+        u[st] = v.u[(q * MC + st) * NT + v.lane];
       }
 #pragma unroll
       for (int st = 0; st < MC; ++st) mh_step(cu, s00, s11, t[st].x, t[st].y, u[st], exp_tab);
@@ -2123,7 +2130,13 @@ hipError_t launch_sweep_t(const SweepArgs& a, hipStream_t st, hipEvent_t e0, hip
 // ---------------------------------------------------------------------------------------------
 // The chain's level-2 workgroup of persist_kernel (one per chain, grid column nb_local).
 // register arrays (block/unit partials of the chain) do not raise the customer path's pressure.
-template <int D, int K, bool P2P>
+// SPLIT (persist_kernel_split): every third block (b % 3 == 1) arrives as three records, the prefix
+// r0 + r1 in the block's own slot and its rows r2, r3 in the extension behind the chain's nb block
+// slots ([nb + 2 (b / 3) + {0, 1}][stat]).  Lane b's second slot (free: nb <= NT) polls r2, the
+// second slot of a neighbouring lane of the same wavefront (b + 1, or b - 1 where b is the
+// wavefront's last lane; neither is a split block) polls r3, and lane b forms (v0 + r2) + r3 — the
+// block layout's ((r0 + r1) + r2) + r3 to the bit.
+template <int D, int K, bool P2P, bool SPLIT = false>
 __device__ __forceinline__ void persist_level2(const SweepArgs& a, int64_t s_first, int64_t n_sweeps, int c, uint32_t k0,
                                             uint32_t k1, int64_t wgi, int64_t it_stamp, double* pool) {
   constexpr int NT = BLOCK;
@@ -2142,7 +2155,10 @@ __device__ __forceinline__ void persist_level2(const SweepArgs& a, int64_t s_fir
   const Geometry& g = a.g;
   const int tid0 = threadIdx.x;
   (void)wgi;
-  double* parts0 = a.pblock + (int64_t)c * g.nb_local * NS;  // [block][stat]
+  static_assert(!(SPLIT && P2P), "the split layout is world size 1 only");
+  // (the record count is spelled out where it is used, not held in a variable: held, it changed the
+  // block kernel's register allocation — c4's 8-rank shard measured 2% slower)
+  double* parts0 = a.pblock + (int64_t)c * (SPLIT ? split_records(g.nb_local) : g.nb_local) * NS;  // [block][stat] (+ SPLIT: the extension)
   if (tid0 == 0) s_abort = 0;
   if constexpr (P2P) {
     if (tid0 < g.world_size) s_peers[tid0] = a.peers[tid0];
@@ -2191,10 +2207,27 @@ __device__ __forceinline__ void persist_level2(const SweepArgs& a, int64_t s_fir
     //    The persistent kernel's partials are [block][stat]: one base address per block and the
     //    statistics at immediate offsets (no per-statistic 64-bit addresses held across the poll).
     double v0[NS], v1[NS];
-    const int b0 = tid, b1 = tid + NT;
-    const bool hb0 = b0 < g.nb_local, hb1 = b1 < g.nb_local;
+    // SPLIT: eb = the split block whose extra record this lane's second slot polls (row 2 if it is
+    // the lane's own block, else row 3), src = the lane holding row 3 of this lane's own split block
+    int eb = -1, er = 0, src = tid & 63;
+    if constexpr (SPLIT) {
+      const int bm = tid - 1, bp = tid + 1;
+      if (tid % 3 == 1 && tid < g.nb_local) {
+        eb = tid;
+        src = (tid & 63) != 63 ? src + 1 : src - 1;
+      } else if (bm >= 0 && bm % 3 == 1 && (bm & 63) != 63 && bm < g.nb_local) {
+        eb = bm;
+        er = 1;
+      } else if (bp % 3 == 1 && (bp & 63) == 63 && bp < g.nb_local) {
+        eb = bp;
+        er = 1;
+      }
+    }
+    const bool own_split = SPLIT && eb == tid;
+    const int b0 = tid, b1 = SPLIT ? eb : tid + NT;
+    const bool hb0 = b0 < g.nb_local, hb1 = SPLIT ? eb >= 0 : b1 < g.nb_local;
     double* pb0 = parts + (int64_t)b0 * NS;
-    double* pb1 = parts + (int64_t)b1 * NS;
+    double* pb1 = parts + (int64_t)(SPLIT ? g.nb_local + 2 * (eb / 3) + er : b1) * NS;
     // polled unconditionally (no branch per load): lanes without a block / unit read block 0 /
     // their own first mail slot and discard it
     const double* qb0 = hb0 ? pb0 : parts;
@@ -2284,7 +2317,14 @@ __device__ __forceinline__ void persist_level2(const SweepArgs& a, int64_t s_fir
     CLV_P_STAMP(a.stamps, wgi, 2, stp);
     // 3. the fused path's fixed-order sum (hyper_body: lane u sums units u, u + NT, ... in order)
     double acc[NS];
-    if constexpr (!P2P) {
+    if constexpr (SPLIT) {
+#pragma unroll
+      for (int j = 0; j < NS; ++j) {  // (every lane shuffles; the second slots themselves are not summed)
+        const double r3 = __shfl(v1[j], src, 64);
+        acc[j] = 0.0;
+        if (hb0) acc[j] += own_split ? (v0[j] + v1[j]) + r3 : v0[j];
+      }
+    } else if constexpr (!P2P) {
 #pragma unroll
       for (int j = 0; j < NS; ++j) {
         acc[j] = 0.0;
@@ -2395,7 +2435,7 @@ __device__ __forceinline__ void persist_level2(const SweepArgs& a, int64_t s_fir
     //    the publish waits for them all).
     const int rt = tid - 64;  // (< 0: wavefront 0)
     if (rt >= 0) {
-      const int nrec = g.nb_local * NS;
+      const int nrec = (SPLIT ? split_records(g.nb_local) : g.nb_local) * NS;  // (SPLIT: the extension too)
       for (int e = rt; e < nrec; e += NT - 64) st_wt(parts + e, slot_empty());
       if ((it > 0 || pin) && rt < HS) st_wt(a.hyp2 + ((int64_t)(s & 1) * g.n_chains + c) * HS + rt, slot_empty());
     }
@@ -2639,6 +2679,251 @@ __global__ __launch_bounds__(BLOCK, 2) void persist_kernel(SweepArgs a, int64_t 
         if constexpr (D == 3) {
           if (pre) zeta_lds[tid] = eta_normal(k0, k1, cu.gi, s + 1, exp_tab);
         }
+      }
+    }
+    CLV_P_STAMP(a.stamps, wgi, 6, stp);
+  }
+  if (cu.active) {  // the carried state, once per launch (adopted by the host if nothing aborted)
+    const int64_t ci = (int64_t)c * g.n + cu.i;
+    a.lam_out[ci] = cu.lam;
+    a.mu_out[ci] = cu.mu;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// The same persistent sweep in the "split" layout (bivariate, world size 1, S <= PRE_STEPS,
+// nb <= SPLIT_MAX_NB; capi.hip chooses).  One 512-thread workgroup per CU: wavefronts 0-5 are
+// customer wavefronts, 6-7 helpers.  A chain's 4 nb wave rows (64 customers each) are dealt to its
+// workgroups six at a time, in order: workgroup p hosts rows 6p .. 6p + 5, i.e. customers
+// 384 p + tid.  Blocks stay the logical unit of the sums (256 consecutive customers, partial
+// ((r0 + r1) + r2) + r3 with every row reduced by wave_reduce_gen):
+//   p even: rows 0-3 = block 3p/2 whole; rows 4-5 = the first half of block 3p/2 + 1 -> r0 + r1
+//           into that block's slot
+//   p odd:  rows 0-1 = rows 2, 3 of block (3p - 1)/2 -> two records in the extension of pblock;
+//           rows 2-5 = block (3p + 1)/2 whole
+// so the blocks b % 3 == 1 are split 2 + 2 over two neighbouring workgroups and the level-2
+// workgroup completes them (persist_level2, SPLIT) — no wait between customer workgroups.  Rows
+// beyond the chain's last customer are inactive lanes and store their 0.0 like any padded lane.
+// Helpers: wavefront w sits on SIMD w % 4, so SIMDs 0 and 1 hold two customer wavefronts (0, 4 and
+// 1, 5) and SIMDs 2 and 3 one each plus a helper.  While the customers run sweep s's MH chain,
+// helper 6 (7) draws the first HC chunks of sweep s + 1's variates for wavefronts 0 and 4 (1 and
+// 5) into registers — the same SlotPhilox(k0, k1, gi, s + 1) of the customer's own global index,
+// so the same bits — and stores them into the pool after the reduction's barrier (before it the
+// customers still read sweep s's columns); the customers draw their remaining chunks and read the
+// pool after the next (beta, Sigma) barrier.  Helpers arrive at exactly the customers' barriers:
+// the prologue's, the (beta, Sigma) barrier (absent in a launch's first sweep unless a deferred
+// draw is pending; its s_abort exit included) and the reduction's.
+// ---------------------------------------------------------------------------------------------
+#ifndef CLV_SPLIT_HELP_CHUNKS
+#define CLV_SPLIT_HELP_CHUNKS 2  // of the PRE_STEPS / MH_CHUNK_STEPS = 5 chunks of a helped wavefront
+#endif
+constexpr int SPLIT_NC = SPLIT_CW * 64;  // customer threads of a workgroup = columns of its variate pool
+constexpr int SPLIT_PRE_LDS_BYTES = PRE_STEPS * SPLIT_NC * 12;
+
+template <int D, int K, int HC>
+__global__ __launch_bounds__(SPLIT_NT, 1) void persist_kernel_split(SweepArgs a, int64_t s_first, int64_t n_sweeps) {
+  static_assert(D == 2, "the split layout is bivariate");
+  constexpr int NXY = K * D;
+  constexpr int NYY = D * (D + 1) / 2;
+  constexpr int NS = NXY + NYY + 1;
+  constexpr int MC = MH_CHUNK_STEPS;
+  constexpr int NQ = PRE_STEPS / MC;
+  static_assert(HC >= 0 && HC <= NQ, "helper share");
+  __shared__ double red[SPLIT_CW][NS];
+  __shared__ __attribute__((aligned(16))) double exp_tab[FAST_TAB_N];
+  __shared__ double Hs[HS];
+  __shared__ uint32_t s_abort;
+  __shared__ __attribute__((aligned(16))) char pool[SPLIT_PRE_LDS_BYTES];
+  const Geometry& g = a.g;
+  const int nwg = split_wgs(g.nb_local);
+  int c = blockIdx.y, p = blockIdx.x;
+  if (a.wg_map) {  // capi.hip persist_split_layout: linear workgroup -> (chain << 16 | workgroup of the chain)
+    const int32_t m = a.wg_map[blockIdx.y * gridDim.x + blockIdx.x];
+    c = m >> 16;
+    p = m & 0xFFFF;
+  }
+  const int tid = threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int64_t wgi = (int64_t)c * (nwg + 1) + p;
+  const int64_t it_stamp = n_sweeps >= 2 ? n_sweeps - 2 : 0;  // diagnostic build: one sweep's timeline
+  (void)wgi;
+  (void)it_stamp;
+  uint32_t k0, k1;
+  chain_key(a.r.seed, (int64_t)a.r.chain_first + c, &k0, &k1);
+  double* parts = a.pblock + (int64_t)c * split_records(g.nb_local) * NS;  // [block][stat], then the extension
+  if (tid == 0) s_abort = 0;
+
+  if (p == nwg) {  // the chain's level-2 workgroup: its first 256 threads, as in the block layout
+    if (tid >= BLOCK) return;
+    persist_level2<D, K, false, true>(a, s_first, n_sweeps, c, k0, k1, wgi, it_stamp, (double*)pool);
+    return;
+  }
+
+  const PreVariates pv{(float2*)pool, (float*)(pool + PRE_STEPS * SPLIT_NC * 8), tid};
+  fast_tab_fill(exp_tab, tid, SPLIT_NT, false);
+  if (tid < HS) Hs[tid] = a.hyper[(int64_t)c * HS + tid];  // sweep s_first: from before this launch
+  const bool first_wait = a.pend_in != nullptr;  // a launch's first sweep waits only for a deferred draw
+
+  if (wave >= SPLIT_CW) {
+    // ================= helper wavefronts =================
+    const int h = wave - SPLIT_CW;  // helps customer wavefronts h and h + 4 (the two sharing SIMD h)
+    uint32_t gi[2];
+    bool on[2];
+    int col[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      col[t] = (h + 4 * t) * 64 + (tid & 63);
+      const int64_t i = (int64_t)p * SPLIT_NC + col[t];
+      on[t] = i < g.n;
+      gi[t] = (uint32_t)(g.shard_begin + i);
+    }
+    __syncthreads();  // the prologue's barrier (tables, Hs)
+    for (int64_t it = 0; it < n_sweeps; ++it) {
+      if (it > 0 || first_wait) {  // the (beta, Sigma) barrier of sweep s_first + it
+        __syncthreads();
+        if (s_abort) return;
+      }
+      const bool ahead = HC > 0 && it + 1 < n_sweeps;
+      const int S = opaque_uniform(loop_args<CLV_PERSIST_FRESH_ARGS != 0>(a).g.S);  // (re-read: not held in SGPRs)
+      float tl[2][HC > 0 ? HC : 1][MC], tm[2][HC > 0 ? HC : 1][MC], lu[2][HC > 0 ? HC : 1][MC];
+      if (ahead) {
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+          if (on[t]) {
+            const SlotPhilox ph(k0, k1, gi[t], (uint32_t)(s_first + it + 1));
+#pragma unroll
+            for (int q = 0; q < HC; ++q)
+              if (q * MC < S) mh_chunk_variates(ph, (uint32_t)q, tl[t][q], tm[t][q], lu[t][q]);  // wave-uniform
+          }
+        }
+      }
+      __syncthreads();  // the reduction's barrier: every customer wavefront has read sweep s's columns
+      if (ahead) {
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+          if (on[t]) {
+#pragma unroll
+            for (int q = 0; q < HC; ++q) {
+              if (q * MC < S) {
+#pragma unroll
+                for (int st = 0; st < MC; ++st) {
+                  const int k = q * MC + st;
+                  pv.t[k * SPLIT_NC + col[t]] = make_float2(tl[t][q][st], tm[t][q][st]);
+                  pv.u[k * SPLIT_NC + col[t]] = k < S ? lu[t][q][st] : __builtin_inff();  // as mh_pre_variates pads
+                }
+              }
+            }
+          }
+        }
+      }
+    }
+    return;
+  }
+
+  // ================= customer wavefronts =================
+  CLV_P_STAMP(a.stamps, wgi, 7, tid == 0);  // (diagnostic build) this workgroup's first instruction
+  Cust<D, K> cu;
+  {
+    const int64_t i = (int64_t)p * SPLIT_NC + tid;
+    cu.active = i < g.n;
+    cu.i = cu.active ? i : (g.n > 0 ? g.n - 1 : 0);
+  }
+  cust_load(cu, a, c);  // once per launch: CBS row, covariates, state stay in registers
+  __syncthreads();
+  if (cu.active) {
+    cust_ztau<D, K, false>(cu, a, s_first, k0, k1, nullptr, exp_tab);
+    mh_pre_variates<NQ, SPLIT_NC>(SlotPhilox(k0, k1, cu.gi, (uint32_t)s_first), g.S, pv);  // the first sweep: all chunks
+  }
+  CLV_P_STAMP(a.stamps, wgi, 10, tid == 0);  // (diagnostic build) prologue done
+  const SweepArgs& a_launch = a;
+  for (int64_t it = 0; it < n_sweeps; ++it) {
+    const SweepArgs& a = loop_args<CLV_PERSIST_FRESH_ARGS != 0>(a_launch);  // as persist_kernel (bivariate)
+    const Geometry& g = a.g;
+    const double* hyp_c = a.hyp2 + (int64_t)c * HS;
+    const int64_t s = uniform64(s_first + it);
+    const bool stored = is_stored(s, g);
+    const bool stp = tid == 0 && it == it_stamp;
+    (void)stp;
+    CLV_P_STAMP(a.stamps, wgi, 0, stp);
+    if (it > 0 || first_wait) {  // wait for (beta, Sigma) of sweep s (wavefront 0 polls, one slot per lane)
+      if (tid < 64) {
+        const double* src = hyp_c + (int64_t)(s & 1) * g.n_chains * HS;
+        const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
+        for (uint32_t poll = 0;; ++poll) {
+          const double v = ld_wt(src + tid);
+          if (__all(slot_full(v))) {
+            Hs[tid] = v;
+            break;
+          }
+          const int ws = wait_state(a, t0, poll, hyper_wait_ticks(a));
+          if (ws != WAIT_GOING) {
+            if (ws == WAIT_EXPIRED) {
+              report_wait(a, WAIT_HYPER, s, c, slot_full(v), p, tid, dbits(v), poll, t0);
+              raise_abort(a);
+            }
+            if (tid == 0) s_abort = 1;
+            break;
+          }
+          __builtin_amdgcn_s_sleep(1);
+        }
+      }
+      __syncthreads();
+      if (s_abort) return;
+    }
+    CLV_P_STAMP(a.stamps, wgi, 1, stp);
+    StatGen<D, K> st{};
+    CustOut<D> out{};
+    __builtin_amdgcn_s_setprio(2);  // the critical phase first (helpers stay at priority 0)
+    if (cu.active) {
+      cust_coeffs<D, K, false>(cu, Hs, exp_tab);
+      CLV_P_STAMP(a.stamps, wgi, 2, stp);
+      mh_run_pre<NQ, SPLIT_NC>(cu, pv, Hs[H_S00], Hs[H_S11], g.S, exp_tab);
+      CLV_P_STAMP(a.stamps, wgi, 3, stp);
+      out = cust_finish<D, K, false>(cu, a, s, stored, Hs, k0, k1, nullptr, exp_tab, st, nullptr);
+    }
+    CLV_P_STAMP(a.stamps, wgi, 4, stp);
+    wave_reduce_gen<NS, SWEEP_REDUCE_CHUNK>(st, red);
+    __syncthreads();
+    {  // the workgroup's records (wavefront 0: its first block's, wavefront 1: its second's), the
+       // rows summed in the block layout's order
+      const int j = tid & 63;
+      const int r0 = SPLIT_CW * p;  // first wave row
+      if (j < NS && tid < 128) {
+        if ((p & 1) == 0) {
+          if (tid < 64) {
+            st_wt(parts + (int64_t)(r0 / 4) * NS + j, ((red[0][j] + red[1][j]) + red[2][j]) + red[3][j]);
+          } else {
+            const int b = r0 / 4 + 1;  // first half: the exact prefix of the block's sum
+            if (b < g.nb_local) st_wt(parts + (int64_t)b * NS + j, red[4][j] + red[5][j]);
+          }
+        } else {
+          if (tid < 64) {
+            const int b = (r0 - 2) / 4;  // second half: rows 2 and 3 as they are
+            double* ext = parts + (int64_t)(g.nb_local + 2 * (b / 3)) * NS;
+            st_wt(ext + j, red[0][j]);
+            st_wt(ext + NS + j, red[1][j]);
+          } else {
+            const int b = (r0 + 2) / 4;
+            if (b < g.nb_local) st_wt(parts + (int64_t)b * NS + j, ((red[2][j] + red[3][j]) + red[4][j]) + red[5][j]);
+          }
+        }
+      }
+    }
+    __builtin_amdgcn_s_setprio(0);  // drawing ahead for the next sweep: yield the SIMD
+    CLV_P_STAMP(a.stamps, wgi, 5, stp);
+    CLV_P_STAMP(a.stamps, wgi, 8, stp);
+    CLV_P_STAMP(a.stamps, wgi, 9, stp);
+#ifdef CLV_STAMPS
+    if (stp && a.stamps) a.stamps[1024 * 8 + wgi * 12 + 11] = blockIdx.y * gridDim.x + blockIdx.x;  // dispatch position
+#endif
+    if (cu.active) {
+      cust_store<D, K>(cu, out, a, c, s, stored, false);
+      if (it + 1 < n_sweeps) {
+        cust_ztau<D, K, false>(cu, a, s + 1, k0, k1, nullptr, exp_tab);
+        // the chunks this wavefront draws itself: all, but for the helped wavefronts (0, 1, 4, 5) the
+        // first HC (recomputed here: one scalar less held across the sweep)
+        const int q_own = (__builtin_amdgcn_readfirstlane(tid >> 6) & 3) < 2 ? HC : 0;
+        mh_pre_variates<NQ, SPLIT_NC>(SlotPhilox(k0, k1, cu.gi, (uint32_t)(s + 1)), g.S, pv, q_own);
       }
     }
     CLV_P_STAMP(a.stamps, wgi, 6, stp);
@@ -2923,6 +3208,35 @@ hipError_t launch_persist(const SweepArgs& a, int64_t s_first, int64_t n_sweeps,
   CLV_FOR_K(CLV_CASE, 3, false)
   CLV_FOR_K(CLV_CASE, 2, true)
   CLV_FOR_K(CLV_CASE, 3, true)
+#undef CLV_CASE
+  return hipErrorInvalidValue;
+}
+
+// The split layout (bivariate, world size 1): a.wg_map is persist_split_layout's map.
+hipError_t launch_persist_split(const SweepArgs& a, int64_t s_first, int64_t n_sweeps, hipStream_t st) {
+  const dim3 grid(split_wgs(a.g.nb_local) + 1, a.g.n_chains);  // + the chain's level-2 workgroup
+#define CLV_CASE(DD, KK, PP)                                                                                        \
+  if (a.g.D == DD && a.g.K == KK) {                                                                               \
+    hipLaunchKernelGGL((persist_kernel_split<DD, KK, CLV_SPLIT_HELP_CHUNKS>), grid, dim3(SPLIT_NT), 0, st, a, s_first, n_sweeps); \
+    return hipGetLastError();                                                                                     \
+  }
+  CLV_FOR_K(CLV_CASE, 2, false)
+#undef CLV_CASE
+  return hipErrorInvalidValue;
+}
+
+// Workgroups per CU and scratch bytes per lane of a split instance (the layout needs 1 and 0).
+hipError_t persist_split_resources(int D, int K, int* blocks_per_cu, size_t* scratch_bytes) {
+  hipFuncAttributes fa{};
+#define CLV_CASE(DD, KK, PP)                                                                                      \
+  if (D == DD && K == KK) {                                                                                       \
+    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, persist_kernel_split<DD, KK, CLV_SPLIT_HELP_CHUNKS>, SPLIT_NT, 0); \
+    if (e != hipSuccess) return e;                                                                                \
+    e = hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&persist_kernel_split<DD, KK, CLV_SPLIT_HELP_CHUNKS>)); \
+    *scratch_bytes = fa.localSizeBytes;                                                                           \
+    return e;                                                                                                     \
+  }
+  CLV_FOR_K(CLV_CASE, 2, false)
 #undef CLV_CASE
   return hipErrorInvalidValue;
 }

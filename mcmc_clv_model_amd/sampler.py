@@ -266,11 +266,15 @@ class HipSampler:
         return float(v.value)
 
     def launch_info(self) -> dict:
-        """How clv_run launches (clv_launch_info): persistent kernel or one launch per sweep."""
+        """How clv_run launches (clv_launch_info): persistent kernel or one launch per sweep.
+        ``workgroups`` counts logical workgroups (one per customer block, + the level-2 one per chain
+        when persistent); ``physical_workgroups`` what is dispatched and ``layout`` the persistent
+        grid's layout: None, "block", "split", or "block (split aborted)"."""
         out = (ctypes.c_int64 * 6)()
         check(self._L.clv_launch_info(self.h, out))
         return dict(persistent=bool(out[0]), persist_blocks_per_cu=int(out[1]), n_cu=int(out[2]),
-                    workgroups=int(out[3]))
+                    workgroups=int(out[3]), physical_workgroups=int(out[4]),
+                    layout={1: "block", 2: "split", -1: "block (split aborted)"}.get(int(out[5])))
 
     # ---- peer exchange (world size > 1 through the persistent kernel, include/clvmcmc.h)
     IPC_HANDLE_BYTES = 64

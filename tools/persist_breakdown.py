@@ -39,8 +39,12 @@ def main(workload="c2", sweeps=1500):
     nb = -(-s.n // 256)
     wg = np.zeros(s.chains * (nb + 1) * 12, np.uint64)
     assert s._L.clv_debug_wg_stamps(s.h, wg.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))) == 0
-    wg = wg.astype(np.int64).reshape(s.chains, nb + 1, 12)
-    print(f"{workload}: persistent={info['persistent']}, chains={s.chains}, N={s.n}, {nb} customer workgroups per chain")
+    # the stamps are indexed by dispatched workgroup: the split layout has ceil(2 nb / 3) customer
+    # workgroups of six customer wavefronts per chain (its records lead the buffer), the block layout nb
+    nb = info["physical_workgroups"] // s.chains - 1
+    wg = wg.astype(np.int64)[:s.chains * (nb + 1) * 12].reshape(s.chains, nb + 1, 12)
+    print(f"{workload}: persistent={info['persistent']}, layout={info['layout']}, chains={s.chains}, N={s.n}, "
+          f"{nb} customer workgroups per chain")
     us = 0.01
     for c in range(s.chains):
         cust, tail = wg[c, :nb], wg[c, nb]
@@ -54,7 +58,7 @@ def main(workload="c2", sweeps=1500):
         txt = "  ".join(f"{n} {np.median(v) * us:5.2f}/{v.max() * us:5.2f}" for n, v in cols.items())
         print(f"  chain {c} (median/max us): {txt}")
         # by placement: workgroups on shared CUs (linear dispatch position < P or >= n_cu) vs alone
-        T, ncu = info["workgroups"], info["n_cu"]
+        T, ncu = info["physical_workgroups"], info["n_cu"]
         pos = cust[:, 11]
         shared = (pos < T - ncu) | (pos >= ncu)
         for tag, m in (("shared", shared), ("alone ", ~shared)):
