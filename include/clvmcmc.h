@@ -177,12 +177,22 @@ int clv_clock_probe(clv_sampler* s, double us, double* ghz);
  * resident whole (clv_debug_split_choice) and the block layout would put two workgroups on a CU;
  * CLV_PERSIST_LAYOUT = block | split forces one (split only where it can run).  Same results to
  * the bit.
+ * The split layout has two instances.  Helpers: wavefronts 6 and 7 draw part of the next sweep's
+ * variates for the rows that share a SIMD.  Relay (n_mh_steps > the compile-time relay point
+ * CLV_SPLIT_RELAY_STEPS, 8 or 12; 0 B of scratch): wavefronts 6 and 7 instead take over rows 4 and 5
+ * after that many MH steps, through one LDS record and flag per row and sweep, and finish and
+ * reduce them.  CLV_SPLIT_RELAY = 0 | 1 forces the helpers / the relay (the relay only where it can
+ * run; anything else is CLV_EINVAL); unset, the relay runs where it can (8 steps
+ * measured faster than the helpers, 12 slower).  Same results to
+ * the bit.  clv_split_relay_steps: *out = the relay point of a handle running the relay instance,
+ * else 0 (clv_launch_info's array stays six words).
  * Persistent = one launch for all of a clv_run's sweeps with every customer block resident, chosen
  * at create when world_size == 1, Philox mode, every workgroup fits at once (with a residency
  * margin) and few enough CUs hold two of them for it to pay (clv_debug_persist_choice), unless
  * CLV_PERSISTENT is "0" ("1": wherever it fits).  Otherwise one launch of the sweep kernel per
  * sweep (fused level-2 tail), replayed from captured hipGraph chunks. */
 int clv_launch_info(const clv_sampler* s, int64_t* out);
+int clv_split_relay_steps(const clv_sampler* s, int32_t* out);
 /* Sharded runs without a host collective per sweep (world_size > 1, Philox mode): the persistent
  * kernel's level-2 workgroup of each chain writes this rank's unit partials of sweep s straight into
  * EVERY rank's mail buffer (device stores over xGMI into IPC-mapped peer memory), waits until its
@@ -338,10 +348,18 @@ int clv_debug_persist_choice(int32_t D, int32_t K, int32_t n_chains, int64_t gri
  * level-2 workgroup), wave rows hosted, then the workgroup's two hand-off records as (kind, block):
  * kind 1 = four rows summed into the block's slot, 2 = rows 0, 1 summed into the block's slot (the
  * prefix of a split block), 3 = rows 2, 3 of a split block as two extension records, -1 = none;
- * out[.][7] = the first extension record's index in the chain's record table (kind 3), else -1. */
+ * out[.][7] = the first extension record's index in the chain's record table (kind 3), else -1.
+ * clv_debug_split_relay_plan: the relay instance's division of a sweep's S (0..20) MH steps at relay
+ * point R (0, 8 or 12) between a relayed row's owner and its relay wavefront, as [begin, end):
+ * out[8] = steps run by the owner, by the relay wavefront, steps whose variates the owner draws, the
+ * relay wavefront draws.  S <= R (or R = 0) is not relayed: the owner has all of it.
+ * clv_debug_split_stamps (CLV_STAMPS build): out[workgroup][16], the relay wavefronts' flag-seen and
+ * row-done times of the stamped sweep (rows 4, 5), then HW_ID of wavefronts 0..7 (bits 5:4: SIMD). */
 int clv_debug_split_fits(int32_t n_chains, int32_t nb, int32_t blocks_per_cu, int32_t n_cu);
 int clv_debug_split_choice(int32_t n_chains, int32_t nb, int32_t blocks_per_cu, int32_t n_cu);
 int clv_debug_split_layout(int32_t n_chains, int32_t nb, int32_t* out);
+int clv_debug_split_relay_plan(int32_t S, int32_t R, int32_t* out);
+int clv_debug_split_stamps(clv_sampler* s, uint64_t* out);
 
 /* ---- In-process multi-device runs (SURVEY.md §8b devices=, §8e) ----
  * A group drives the n shards of one problem from one host thread: shards[r] = the sampler of rank

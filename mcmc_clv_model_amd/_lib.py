@@ -98,6 +98,7 @@ def lib() -> ctypes.CDLL:
         "clv_clock_ghz": (c_int32, [sp, POINTER(c_double)]),
         "clv_clock_probe": (c_int32, [sp, c_double, POINTER(c_double)]),
         "clv_launch_info": (c_int32, [sp, POINTER(c_int64)]),
+        "clv_split_relay_steps": (c_int32, [sp, POINTER(c_int32)]),
         "clv_p2p_info": (c_int32, [sp, POINTER(c_int64)]),
         "clv_p2p_export": (c_int32, [sp, c_void_p]),
         "clv_p2p_connect": (c_int32, [sp, c_void_p, POINTER(c_uint64)]),
@@ -123,6 +124,8 @@ def lib() -> ctypes.CDLL:
         "clv_debug_hyper_variates": (c_int32, [c_uint64, c_int32, c_uint32, c_double, c_int64, dp, dp]),
         "clv_debug_stamps": (c_int32, [sp, POINTER(c_uint64)]),
         "clv_debug_wg_stamps": (c_int32, [sp, POINTER(c_uint64)]),
+        "clv_debug_split_stamps": (c_int32, [sp, POINTER(c_uint64)]),
+        "clv_debug_split_relay_plan": (c_int32, [c_int32, c_int32, POINTER(c_int32)]),
         "clv_debug_exp": (c_int32, [dp, c_int64, dp]),
         "clv_debug_log": (c_int32, [dp, c_int64, dp]),
         "clv_debug_mh_step": (c_int32, [c_int64, POINTER(c_int32), POINTER(c_uint8), dp, dp, dp, dp, dp,

@@ -234,6 +234,7 @@ std::string take_wait_diag(clv_sampler* s) {
   const Geometry& g = s->g;
   const char* what = d[1] == WAIT_HYPER ? "(beta, Sigma) hand-off slot"
                      : d[1] == WAIT_BLOCKS ? "block partial"
+                     : d[1] == WAIT_RELAY ? "split layout's relay flag of workgroup"
                      : d[1] == WAIT_P2P_MAIL ? "peer unit partial (persistent)" : "peer unit partial (fused)";
   std::string m = std::string(" [wait record: sweep ") + std::to_string((long long)d[2]) + ", chain " +
                   std::to_string(d[3]) + ", rank " + std::to_string(d[4]) + ": " + what + " ";
@@ -243,6 +244,7 @@ std::string take_wait_diag(clv_sampler* s) {
          std::to_string(unit % g.units_per_rank) + ")";
   else
     m += (d[1] == WAIT_HYPER ? "of block " : "") + std::to_string(unit);
+  if (d[1] == WAIT_RELAY) m += " (statistic: the wave row, bits: the flag's tag)";
   char bits[32];
   std::snprintf(bits, sizeof(bits), "%016llx", d[7]);
   m += " statistic " + std::to_string((long long)d[6]) + " still empty (bits " + bits + ") after " +
@@ -352,6 +354,12 @@ bool clv::persist_grid_fits(int64_t grid_wgs, int blocks_per_cu, int n_cu) {
 // 8, trivariate K <= 4), peer c2-tiled <2,2> 0 B, c4 at 8 ranks <2,5> 56 B, <3,3> 48 B (the tests'
 // world-3 trivariate run).  (llvm-readelf --notes: .private_segment_fixed_size.)
 constexpr size_t PERSIST_SCRATCH_MAX = 64;
+// The split layout's relay instance with CLV_SPLIT_RELAY unset (the measurement
+// that decides it).
+#ifndef CLV_SPLIT_RELAY_DEFAULT
+#define CLV_SPLIT_RELAY_DEFAULT 1
+#endif
+constexpr bool SPLIT_RELAY_DEFAULT = CLV_SPLIT_RELAY_DEFAULT != 0;
 
 bool clv::persist_worth(int D, int K, int n_chains, int64_t grid_wgs, int n_cu) {
   (void)D, (void)K, (void)n_chains;
@@ -603,6 +611,23 @@ int clv_create(const clv_config* cfg, const clv_data* data, const clv_prior* pri
         s->split = true;
       else
         (void)hipGetLastError();
+      // The relay instance (wavefronts 6 and 7 finish rows 4 and 5 from MH step SPLIT_RELAY_STEPS on)
+      // where the sweep has more steps than that and the instance has 0 B of scratch and fits as the
+      // helper instance does; CLV_SPLIT_RELAY = 0 | 1 forces the helpers / the relay (tests, A/B;
+      // the relay still only where it can run).
+      const char* rel = std::getenv("CLV_SPLIT_RELAY");
+      const std::string rwant = rel ? rel : "";
+      if (rel && rwant != "0" && rwant != "1")
+        return cleanup_fail(fail(CLV_EINVAL, "CLV_SPLIT_RELAY must be 0 or 1"));
+      if (s->split && SPLIT_RELAY_STEPS > 0 && g.S > SPLIT_RELAY_STEPS && (rel ? rwant == "1" : SPLIT_RELAY_DEFAULT)) {
+        int rbpc = 0;
+        size_t rscratch = SIZE_MAX;
+        if (persist_split_resources(g.D, g.K, &rbpc, &rscratch, true) == hipSuccess && rscratch == 0 &&
+            persist_split_fits((int)C, (int)nb_local, rbpc, s->n_cu))
+          s->relay_steps = SPLIT_RELAY_STEPS;
+        else
+          (void)hipGetLastError();
+      }
     }
   }
   // World size > 1: the same persistent kernel exchanging unit partials with its peers over xGMI
@@ -698,7 +723,8 @@ int clv_create(const clv_config* cfg, const clv_data* data, const clv_prior* pri
   }
 #ifdef CLV_STAMPS
   {
-    std::vector<unsigned long long> st(1024 * 8 + 12 * (size_t)C * (std::max(nb_local, 1) + 1), 0ull);
+    // (+ 16 words per workgroup: the split layout's relay stamps and SIMD ids, clv_debug_split_stamps)
+    std::vector<unsigned long long> st(1024 * 8 + (12 + 16) * (size_t)C * (std::max(nb_local, 1) + 1), 0ull);
     for (int i = 0; i < 1024; ++i) st[i * 8 + 0] = st[i * 8 + 4] = ~0ull;
     CLV_HIPC(dalloc(&s->d_stamps, st.size()));
     CLV_HIPC(hipMemcpy(s->d_stamps, st.data(), st.size() * sizeof(unsigned long long), hipMemcpyHostToDevice));
@@ -941,6 +967,12 @@ int clv_launch_info(const clv_sampler* s, int64_t* out) {
   return CLV_OK;
 }
 
+int clv_split_relay_steps(const clv_sampler* s, int32_t* out) {
+  if (!s || !out) return fail(CLV_EINVAL, "null argument");
+  *out = s->split ? s->relay_steps : 0;
+  return CLV_OK;
+}
+
 int clv_p2p_info(const clv_sampler* s, int64_t* out) {
   if (!s || !out) return fail(CLV_EINVAL, "null argument");
   out[0] = (s->p2p_capable || s->fx_capable) ? 1 : 0;
@@ -1092,7 +1124,7 @@ int clv::persist_launch(clv_sampler* s, int64_t n_sweeps) {
   s->host_ns[2] = host_now_ns();
   if (s->split) {
     a.wg_map = s->d_wgmap_split;
-    CLV_HIP(launch_persist_split(a, s->sweeps_done + 1, n_sweeps, s->stream));
+    CLV_HIP(launch_persist_split(a, s->sweeps_done + 1, n_sweeps, s->stream, s->relay_steps > 0));
   } else {
     CLV_HIP(launch_persist(a, s->sweeps_done + 1, n_sweeps, s->stream, nullptr, nullptr));
   }
@@ -1147,6 +1179,7 @@ int clv::persist_wait(clv_sampler* s) {
     if (s->split) {  // its one-workgroup-per-CU grid was not resident whole (or a fault): the block
                      // layout, with its wider margin, for the rest of the handle's life
       s->split = false;
+      s->relay_steps = 0;
       s->split_reverted = true;
       diag += "; the split layout's launch aborted: this handle uses the block layout from now on";
     }
@@ -1562,6 +1595,15 @@ int clv_debug_wg_stamps(clv_sampler* s, uint64_t* out) {
   return CLV_OK;
 }
 
+int clv_debug_split_stamps(clv_sampler* s, uint64_t* out) {
+  if (!s || !out) return fail(CLV_EINVAL, "null argument");
+  if (!s->d_stamps) return fail(CLV_ESTATE, "library not built with CLV_STAMPS (make STAMPS=1)");
+  CLV_HIP(hipStreamSynchronize(s->stream));
+  const size_t wgs = (size_t)s->g.n_chains * (s->g.nb_local + 1);
+  CLV_HIP(hipMemcpy(out, s->d_stamps + 1024 * 8 + 12 * wgs, sizeof(uint64_t) * 16 * wgs, hipMemcpyDeviceToHost));
+  return CLV_OK;
+}
+
 int clv_debug_host_times(const clv_sampler* s, int64_t* out) {
   if (!s || !out) return fail(CLV_EINVAL, "bad arguments");
   for (int k = 0; k < 8; ++k) out[k] = s->host_ns[k];
@@ -1713,6 +1755,17 @@ int clv_debug_split_fits(int32_t n_chains, int32_t nb, int32_t blocks_per_cu, in
 
 int clv_debug_split_choice(int32_t n_chains, int32_t nb, int32_t blocks_per_cu, int32_t n_cu) {
   return persist_split_fits(n_chains, nb, blocks_per_cu, n_cu) && persist_split_pays(n_chains, nb, n_cu) ? 1 : 0;
+}
+
+int clv_debug_split_relay_plan(int32_t S, int32_t R, int32_t* out) {
+  if (!out || S < 0 || S > PRE_STEPS || !(R == 0 || R == 8 || R == 12)) return fail(CLV_EINVAL, "bad arguments");
+  const SplitRelayPlan pl = split_relay_plan(S, R);
+  // the steps each wavefront runs, then the steps whose variates each draws (the same by construction:
+  // the kernel takes both from this one plan)
+  const int32_t o[8] = {pl.own_begin, pl.own_end, pl.relay_begin, pl.relay_end,
+                        pl.own_begin, pl.own_end, pl.relay_begin, pl.relay_end};
+  std::copy(o, o + 8, out);
+  return CLV_OK;
 }
 
 int clv_debug_split_layout(int32_t n_chains, int32_t nb, int32_t* out) {

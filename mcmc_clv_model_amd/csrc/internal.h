@@ -143,6 +143,7 @@ struct clv_sampler {
   bool persistent = false;          // clv_run uses persist_kernel (all workgroups resident)
   int persist_bpc = 0, n_cu = 0;    // persist_kernel occupancy (workgroups per CU), CUs
   bool split = false;               // the persistent launch uses the split layout (persist_kernel_split)
+  int relay_steps = 0;              // split layout: the relay instance's hand-over step (0: helper instance)
   bool split_reverted = false;      // a split launch aborted: block layout for the handle's lifetime
   int32_t* d_wgmap_split = nullptr; // split grid: linear workgroup -> (chain << 16 | chain's workgroup)
   // world size > 1: persistent kernel with the peer (xGMI) exchange

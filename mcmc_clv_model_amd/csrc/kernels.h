@@ -31,7 +31,23 @@ enum : int { LAYOUT_NONE = 0, LAYOUT_BLOCK = 1, LAYOUT_SPLIT = 2 };
 __host__ __device__ inline int split_wgs(int nb) { return (2 * nb + 2) / 3; }
 // Hand-off records per chain: the nb block slots, then rows 2 and 3 of every split block (b % 3 == 1).
 __host__ __device__ inline int split_records(int nb) { return nb + 2 * ((nb + 1) / 3); }
-enum : int { WAIT_HYPER = 1, WAIT_BLOCKS = 2, WAIT_P2P_MAIL = 3, WAIT_FX_MAIL = 4 };
+enum : int { WAIT_HYPER = 1, WAIT_BLOCKS = 2, WAIT_P2P_MAIL = 3, WAIT_FX_MAIL = 4, WAIT_RELAY = 5 };
+// Relay instance of the split layout: wavefronts 6 and 7 take over rows 4 and 5 after their first
+// CLV_SPLIT_RELAY_STEPS MH steps (a multiple of the variate chunk of 4 steps; 0: not compiled).
+#ifndef CLV_SPLIT_RELAY_STEPS
+#define CLV_SPLIT_RELAY_STEPS 8  // measured: 8 beats the helpers, 12 does not
+#endif
+constexpr int SPLIT_RELAY_STEPS = CLV_SPLIT_RELAY_STEPS;
+static_assert(SPLIT_RELAY_STEPS == 0 || SPLIT_RELAY_STEPS == 8 || SPLIT_RELAY_STEPS == 12, "relay point: 8 or 12 steps");
+// Which wavefront of a relayed row runs which of the sweep's S MH steps, [begin, end) each: the
+// owner (wavefront 4 or 5) and the relay wavefront (6 or 7).  Each draws exactly the variates of the
+// steps it runs.  A sweep of S <= R steps (or R = 0) is not relayed: the owner runs all of it.
+struct SplitRelayPlan {
+  int own_begin, own_end, relay_begin, relay_end;
+};
+__host__ __device__ constexpr SplitRelayPlan split_relay_plan(int S, int R) {
+  return SplitRelayPlan{0, (R > 0 && S > R) ? R : S, (R > 0 && S > R) ? R : S, S};
+}
 
 // Doubles of peer-mail slots before the progress words.
 __host__ __device__ inline int64_t mail_slots(int world, int chains, int stride, int units_per_rank) {
@@ -172,8 +188,10 @@ hipError_t launch_sweep(const SweepArgs& a, bool replay, hipStream_t st, hipEven
 hipError_t launch_group(const GroupArgs& a, hipStream_t st);
 hipError_t launch_persist(const SweepArgs& a, int64_t s_first, int64_t n_sweeps, hipStream_t st,
                           hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
-hipError_t launch_persist_split(const SweepArgs& a, int64_t s_first, int64_t n_sweeps, hipStream_t st);
-hipError_t persist_split_resources(int D, int K, int* blocks_per_cu, size_t* scratch_bytes);
+// relay: the relay instance (SPLIT_RELAY_STEPS > 0 and a.g.S above it), else the helper instance
+hipError_t launch_persist_split(const SweepArgs& a, int64_t s_first, int64_t n_sweeps, hipStream_t st,
+                                bool relay = false);
+hipError_t persist_split_resources(int D, int K, int* blocks_per_cu, size_t* scratch_bytes, bool relay = false);
 hipError_t persist_occupancy(int D, int K, bool p2p, int* blocks_per_cu);
 hipError_t persist_scratch_bytes(int D, int K, bool p2p, size_t* bytes);  // spilled instances: > 0
 // The deferred level-2 draw alone (a.pend_in, no sweeps): one level-2 workgroup per chain.

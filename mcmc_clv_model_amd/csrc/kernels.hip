@@ -254,6 +254,54 @@ __device__ __forceinline__ void wave_reduce_gen(const Gen& gen, double (*red)[NS
     }
   }
 }
+// The same, into a given row of red (a wavefront reducing another wavefront's row: the split layout's
+// relay wavefronts); the lanes are summed in the same order whichever wavefront runs it.  (A copy, so
+// that the callers of wave_reduce_gen compile to the code they had.)
+template <int NS, int G, class Gen>
+__device__ __forceinline__ void wave_reduce_gen_row(const Gen& gen, double* row_out) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int base = 0; base < NS; base += G) {
+    constexpr int GG = G;
+    const int n = NS - base < GG ? NS - base : GG;  // compile-time after unrolling
+    const int h1 = (n + 1) / 2;
+    const int h2 = (h1 + 1) / 2;
+    double w1[(G + 1) / 2];
+#pragma unroll
+    for (int j = 0; j < (G + 1) / 2; ++j) {
+      if (j < h1) {
+        double a = gen(base + j);
+        double b = (j + h1 < n) ? gen(base + j + h1) : 0.0;
+        swap_halves(a, b);
+        w1[j] = a + b;
+      }
+    }
+    double w2[(G + 3) / 4];
+#pragma unroll
+    for (int j = 0; j < (G + 3) / 4; ++j) {
+      if (j < h2) {
+        double a = w1[j];
+        double b = (j + h2 < h1) ? w1[j + h2] : 0.0;
+        swap_rows(a, b);
+        double x = a + b;
+        x = add_row_ror<8>(x);
+        x = add_row_ror<4>(x);
+        x = add_row_ror<2>(x);
+        x = add_row_ror<1>(x);
+        w2[j] = x;
+      }
+    }
+    if ((lane & 15) == 0) {
+      const int row = lane >> 4;
+#pragma unroll
+      for (int j = 0; j < (G + 3) / 4; ++j) {
+        const int i1 = j + ((row & 1) ? h2 : 0);
+        const int idx = i1 + ((row >> 1) ? h1 : 0);
+        if (j < h2 && i1 < h1 && idx < n) row_out[base + idx] = w2[j];
+      }
+    }
+  }
+}
 
 template <int NS, int G, int NT = BLOCK, class Gen>
 __device__ __forceinline__ void block_reduce_gen(const Gen& gen, double (*red)[NS], double* out) {
@@ -331,7 +379,17 @@ __device__ __forceinline__ void wg_stamp(unsigned long long* st, int64_t wg, int
   do {                             \
     if ((on) && (st)) (st)[1024 * 8 + (wg) * 12 + (k)] = (k) == 8 ? __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11)) : (k) == 9 ? __builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (15 << 11)) : __builtin_amdgcn_s_memrealtime(); \
   } while (0)
+// split layout, after those records: 16 words per workgroup (clv_debug_split_stamps) — [0..3] the
+// relay wavefronts' flag-seen and row-done times of the stamped sweep (rows 4 and 5), [4..11] HW_ID
+// of wavefronts 0..7, once per launch (bits 5:4: the SIMD)
+#define CLV_R_STAMP(a, wg, k, on)                                                                                       \
+  do {                                                                                                                  \
+    if ((on) && (a).stamps && (threadIdx.x & 63) == 0)                                                                  \
+      (a).stamps[1024 * 8 + ((int64_t)(a).g.n_chains * ((a).g.nb_local + 1)) * 12 + (wg) * 16 + (k)] =                   \
+          (k) >= 4 ? __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11)) : __builtin_amdgcn_s_memrealtime();    \
+  } while (0)
 #else
+#define CLV_R_STAMP(a, wg, k, on) ((void)0)
 #define CLV_P_STAMP(st, wg, k, on) ((void)0)
 #define CLV_WG_STAMP(st, wg, k) ((void)0)
 #define CLV_STAMP(st, s, k, is_min) ((void)0)
@@ -1562,6 +1620,48 @@ __device__ __forceinline__ void mh_run_pre(Cust<D, K, CL>& cu, const PreVariates
   }
 }
 
+// The chunks [Q0, Q1) only of mh_pre_variates / mh_run_pre (the split layout's relay instance: a
+// row's owner and its relay wavefront each draw and run their own share of the sweep's steps; run
+// one range after the other, the steps and their variates are those of the whole sweep).
+template <int Q0, int Q1, int NT>
+__device__ __forceinline__ void mh_pre_variates_range(const SlotPhilox& ph, int S_, const PreVariates& v) {
+  constexpr int MC = MH_CHUNK_STEPS;
+  const int S = opaque_uniform(S_);
+#pragma unroll
+  for (int q = Q0; q < Q1; ++q) {
+    if (q * MC < S) {  // wave-uniform
+      float tl[MC], tm[MC], lu[MC];
+      mh_chunk_variates(ph, (uint32_t)q, tl, tm, lu);
+#pragma unroll
+      for (int st = 0; st < MC; ++st) {
+        const int k = q * MC + st;
+        v.t[k * NT + v.lane] = make_float2(tl[st], tm[st]);
+        v.u[k * NT + v.lane] = k < S ? lu[st] : __builtin_inff();  // as mh_pre_variates pads
+      }
+    }
+  }
+}
+template <int Q0, int Q1, int NT, int D, int K, bool CL>
+__device__ __forceinline__ void mh_run_pre_range(Cust<D, K, CL>& cu, const PreVariates& v, double s00, double s11, int S,
+                                                 const double* exp_tab) {
+  constexpr int MC = MH_CHUNK_STEPS;
+  S = opaque_uniform(S);
+#pragma unroll
+  for (int q = Q0; q < Q1; ++q) {
+    if (q * MC < S) {  // wave-uniform
+      float2 t[MC];
+      float u[MC];
+#pragma unroll
+      for (int st = 0; st < MC; ++st) {
+        t[st] = v.t[(q * MC + st) * NT + v.lane];
+        u[st] = v.u[(q * MC + st) * NT + v.lane];
+      }
+#pragma unroll
+      for (int st = 0; st < MC; ++st) mh_step(cu, s00, s11, t[st].x, t[st].y, u[st], exp_tab);
+    }
+  }
+}
+
 // Phase C1: state update (bi:337-338), draw_eta (tri:306-333), the likelihood term of stored
 // sweeps (bi:423-427) and the customer's sufficient statistics into acc.
 template <int D>
@@ -2704,8 +2804,9 @@ __global__ __launch_bounds__(BLOCK, 2) void persist_kernel(SweepArgs a, int64_t 
 // so the blocks b % 3 == 1 are split 2 + 2 over two neighbouring workgroups and the level-2
 // workgroup completes them (persist_level2, SPLIT) — no wait between customer workgroups.  Rows
 // beyond the chain's last customer are inactive lanes and store their 0.0 like any padded lane.
-// Helpers: wavefront w sits on SIMD w % 4, so SIMDs 0 and 1 hold two customer wavefronts (0, 4 and
-// 1, 5) and SIMDs 2 and 3 one each plus a helper.  While the customers run sweep s's MH chain,
+// Helpers (R = 0; R > 0 is the relay instance, split_relay_sweeps above): wavefront w sits on SIMD
+// w % 4 up to a rotation per workgroup (stamped in round 8: w and w + 4 always share a SIMD), so two
+// SIMDs hold two customer wavefronts (0, 4 and 1, 5) and two one each plus a helper.  While the customers run sweep s's MH chain,
 // helper 6 (7) draws the first HC chunks of sweep s + 1's variates for wavefronts 0 and 4 (1 and
 // 5) into registers — the same SlotPhilox(k0, k1, gi, s + 1) of the customer's own global index,
 // so the same bits — and stores them into the pool after the reduction's barrier (before it the
@@ -2720,7 +2821,287 @@ __global__ __launch_bounds__(BLOCK, 2) void persist_kernel(SweepArgs a, int64_t 
 constexpr int SPLIT_NC = SPLIT_CW * 64;  // customer threads of a workgroup = columns of its variate pool
 constexpr int SPLIT_PRE_LDS_BYTES = PRE_STEPS * SPLIT_NC * 12;
 
-template <int D, int K, int HC>
+// The customer workgroups of the relay instance (R > 0 MH steps, a multiple of the chunk; launched
+// only for S > R).  Rows 4 and 5 share their SIMDs with rows 0 and 1, so their state-dependent phase
+// is handed over half way: the owner (wavefront 4 / 5) holds the CBS row and the state, does z / tau,
+// the coefficients and steps 0 .. R-1, writes the lane's record (the six LPFast coefficients, ll, lm,
+// cur; xm and 1 - z for a stored sweep's likelihood term) to LDS and raises the row's flag, tagged
+// with the sweep's number in the launch; wavefront 6 / 7 (lane l for the owner's lane l) polls the
+// flag, runs steps R .. S-1, cust_finish and the row's reduction into red[4] / red[5], and writes
+// lambda, mu and their logs back for the owner to read after the reduction's barrier.  That flag is
+// the only wait added; the barriers are the helper instance's.  Every wavefront draws the variates
+// of exactly the steps it runs (split_relay_plan) into pool columns only it reads, in the hand-off
+// window after the reduction's barrier (the prologue for the launch's first sweep).  The relayed
+// row's chain is the longest serial path of the workgroup: both its wavefronts run it at priority 3.
+// LDS order within a sweep: record and flag after the (beta, Sigma) barrier, the values written back
+// before the reduction's barrier and read after it, so neither is overwritten while still unread.
+constexpr int RELAY_REC = 11;  // doubles of a lane's hand-off record
+
+template <int D, int K, int R>
+__device__ __forceinline__ void split_relay_sweeps(const SweepArgs& a_launch, int64_t s_first, int64_t n_sweeps, int c,
+                                                   int p, uint32_t k0, uint32_t k1, int64_t wgi, int64_t it_stamp,
+                                                   double* parts, char* pool, double (*red)[K * D + D * (D + 1) / 2 + 1],
+                                                   const double* exp_tab, double* Hs, uint32_t* s_abort) {
+  constexpr int NS = K * D + D * (D + 1) / 2 + 1;
+  constexpr int MC = MH_CHUNK_STEPS;
+  constexpr int NQ = PRE_STEPS / MC;
+  static_assert(R > 0 && R % MC == 0 && R < PRE_STEPS, "relay point: whole chunks, inside the pool");
+  // the chunks each wavefront runs and draws, from the one plan (any S above R cuts at the same step:
+  // the owner's chunks are whole, the relay wavefront's last one may be partial)
+  constexpr SplitRelayPlan PLAN = split_relay_plan(PRE_STEPS, R);
+  static_assert(PLAN.own_begin == 0 && PLAN.own_end == PLAN.relay_begin && PLAN.own_end % MC == 0 && PLAN.relay_end == PRE_STEPS,
+                "the relay plan cuts between chunks");
+  static_assert(split_relay_plan(R + 1, R).own_end == PLAN.own_end, "one cut for every relayed S");
+  constexpr int QR = PLAN.relay_begin / MC;  // first chunk of the relay wavefront
+  __shared__ double relay_rec[RELAY_REC][128];
+  __shared__ double relay_ret[4][128];  // lambda, mu, log lambda, log mu
+  __shared__ uint32_t relay_flag[2];
+  __shared__ uint32_t relay_abort;
+  (void)wgi;
+  (void)it_stamp;
+  const int tid = threadIdx.x;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const bool first_wait = a_launch.pend_in != nullptr;
+  if (tid < 2) relay_flag[tid] = 0;
+  if (tid == 2) relay_abort = 0;
+
+  if (wave >= SPLIT_CW) {
+    // ================= relay wavefronts =================
+    const int rw = wave - SPLIT_CW;  // row 4 + rw
+    const int rl = tid - SPLIT_CW * 64;
+    const PreVariates pv{(float2*)pool, (float*)(pool + PRE_STEPS * SPLIT_NC * 8), tid - 128};  // the row's columns
+    Cust<D, K> cu;
+    {
+      const Geometry& g = a_launch.g;
+      const int64_t i = (int64_t)p * SPLIT_NC + (tid - 128);
+      cu.active = i < g.n;
+      cu.i = cu.active ? i : (g.n > 0 ? g.n - 1 : 0);
+      cu.xr_[0] = 1.0;
+#pragma unroll
+      for (int k = 1; k < K; ++k) cu.xr_[k] = a_launch.cov[(int64_t)(k - 1) * g.n + cu.i];  // once per launch
+      cu.gi = (uint32_t)(g.shard_begin + cu.i);
+      cu.xm = 0.0;
+      cu.lc.omz = 0.0;
+      if (cu.active) mh_pre_variates_range<QR, NQ, SPLIT_NC>(SlotPhilox(k0, k1, cu.gi, (uint32_t)s_first), g.S, pv);
+    }
+    __syncthreads();  // the prologue's barrier (tables, Hs, flags)
+    for (int64_t it = 0; it < n_sweeps; ++it) {
+      const SweepArgs& a = loop_args<CLV_PERSIST_FRESH_ARGS != 0>(a_launch);
+      const Geometry& g = a.g;
+      if (it > 0 || first_wait) {  // the (beta, Sigma) barrier of sweep s_first + it
+        __syncthreads();
+        if (*s_abort) return;
+      }
+      const int64_t s = uniform64(s_first + it);
+      const bool stored = is_stored(s, g);
+      const uint32_t tag = (uint32_t)it + 1u;
+      bool seen = true;
+      {  // the row's flag (bounded like every wait here; an expired or abandoned wait ends the launch
+         // for the whole workgroup after the reduction's barrier)
+        const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
+        for (uint32_t poll = 0;; ++poll) {
+          const uint32_t f = (uint32_t)__builtin_amdgcn_readfirstlane(
+              (int)__hip_atomic_load(&relay_flag[rw], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
+          if (f == tag) break;
+          const int ws = wait_state(a, t0, poll, a.wait_ticks);
+          if (ws != WAIT_GOING) {
+            if (ws == WAIT_EXPIRED) {
+              report_wait(a, WAIT_RELAY, s, c, false, p, 4 + rw, f, poll, t0);
+              raise_abort(a);
+            }
+            if ((tid & 63) == 0) relay_abort = 1;
+            seen = false;
+            break;
+          }
+          __builtin_amdgcn_s_sleep(1);
+        }
+      }
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+      CLV_R_STAMP(a, wgi, 2 * rw, it == it_stamp);  // (diagnostic build) flag seen
+      StatGen<D, K> st{};
+      __builtin_amdgcn_s_setprio(3);
+      if (seen && cu.active) {
+        cu.fc.A = relay_rec[0][rl];
+        cu.fc.B = relay_rec[1][rl];
+        cu.fc.C = relay_rec[2][rl];
+        cu.fc.Dl = relay_rec[3][rl];
+        cu.fc.El = relay_rec[4][rl];
+        cu.fc.w = relay_rec[5][rl];
+        cu.ll = relay_rec[6][rl];
+        cu.lm = relay_rec[7][rl];
+        cu.cur = relay_rec[8][rl];
+        cu.lc.w = cu.fc.w;
+        if (stored) {
+          cu.xm = relay_rec[9][rl];
+          cu.lc.omz = relay_rec[10][rl];
+        }
+        mh_run_pre_range<QR, NQ, SPLIT_NC>(cu, pv, Hs[H_S00], Hs[H_S11], g.S, exp_tab);
+        const CustOut<D> out = cust_finish<D, K, false>(cu, a, s, stored, Hs, k0, k1, nullptr, exp_tab, st, nullptr);
+        relay_ret[0][rl] = out.lam;
+        relay_ret[1][rl] = out.mu;
+        relay_ret[2][rl] = cu.ll;
+        relay_ret[3][rl] = cu.lm;
+      }
+      wave_reduce_gen_row<NS, SWEEP_REDUCE_CHUNK>(st, red[4 + rw]);  // the owner's lane order
+      CLV_R_STAMP(a, wgi, 2 * rw + 1, it == it_stamp);  // (diagnostic build) row done
+      __syncthreads();  // the reduction's barrier
+      __builtin_amdgcn_s_setprio(0);
+      if (relay_abort) return;
+      if (cu.active && it + 1 < n_sweeps)
+        mh_pre_variates_range<QR, NQ, SPLIT_NC>(SlotPhilox(k0, k1, cu.gi, (uint32_t)(s + 1)), g.S, pv);
+    }
+    return;
+  }
+
+  // ================= customer wavefronts (4 and 5: owners of the relayed rows) =================
+  const bool relayed = wave >= 4;
+  const int rl = tid - 4 * 64;  // (relayed rows) the lane's record
+  const PreVariates pv{(float2*)pool, (float*)(pool + PRE_STEPS * SPLIT_NC * 8), tid};
+  CLV_P_STAMP(a_launch.stamps, wgi, 7, tid == 0);  // (diagnostic build) this workgroup's first instruction
+  Cust<D, K> cu;
+  {
+    const int64_t i = (int64_t)p * SPLIT_NC + tid;
+    cu.active = i < a_launch.g.n;
+    cu.i = cu.active ? i : (a_launch.g.n > 0 ? a_launch.g.n - 1 : 0);
+  }
+  cust_load(cu, a_launch, c);  // once per launch: CBS row, covariates, state stay in registers
+  __syncthreads();
+  if (cu.active) {
+    cust_ztau<D, K, false>(cu, a_launch, s_first, k0, k1, nullptr, exp_tab);
+    const SlotPhilox ph(k0, k1, cu.gi, (uint32_t)s_first);
+    mh_pre_variates_range<0, QR, SPLIT_NC>(ph, a_launch.g.S, pv);
+    if (!relayed) mh_pre_variates_range<QR, NQ, SPLIT_NC>(ph, a_launch.g.S, pv);
+  }
+  CLV_P_STAMP(a_launch.stamps, wgi, 10, tid == 0);  // (diagnostic build) prologue done
+  for (int64_t it = 0; it < n_sweeps; ++it) {
+    const SweepArgs& a = loop_args<CLV_PERSIST_FRESH_ARGS != 0>(a_launch);
+    const Geometry& g = a.g;
+    const double* hyp_c = a.hyp2 + (int64_t)c * HS;
+    const int64_t s = uniform64(s_first + it);
+    const bool stored = is_stored(s, g);
+    const bool stp = tid == 0 && it == it_stamp;
+    (void)stp;
+    CLV_P_STAMP(a.stamps, wgi, 0, stp);
+    if (it > 0 || first_wait) {  // wait for (beta, Sigma) of sweep s (wavefront 0 polls, one slot per lane)
+      if (tid < 64) {
+        const double* src = hyp_c + (int64_t)(s & 1) * g.n_chains * HS;
+        const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
+        for (uint32_t poll = 0;; ++poll) {
+          const double v = ld_wt(src + tid);
+          if (__all(slot_full(v))) {
+            Hs[tid] = v;
+            break;
+          }
+          const int ws = wait_state(a, t0, poll, hyper_wait_ticks(a));
+          if (ws != WAIT_GOING) {
+            if (ws == WAIT_EXPIRED) {
+              report_wait(a, WAIT_HYPER, s, c, slot_full(v), p, tid, dbits(v), poll, t0);
+              raise_abort(a);
+            }
+            if (tid == 0) *s_abort = 1;
+            break;
+          }
+          __builtin_amdgcn_s_sleep(1);
+        }
+      }
+      __syncthreads();
+      if (*s_abort) return;
+    }
+    CLV_P_STAMP(a.stamps, wgi, 1, stp);
+    StatGen<D, K> st{};
+    CustOut<D> out{};
+    if (relayed) {
+      __builtin_amdgcn_s_setprio(3);  // the relayed row's chain: the workgroup's longest serial path
+      if (cu.active) {
+        cust_coeffs<D, K, false>(cu, Hs, exp_tab);
+        mh_run_pre_range<0, QR, SPLIT_NC>(cu, pv, Hs[H_S00], Hs[H_S11], g.S, exp_tab);
+        relay_rec[0][rl] = cu.fc.A;
+        relay_rec[1][rl] = cu.fc.B;
+        relay_rec[2][rl] = cu.fc.C;
+        relay_rec[3][rl] = cu.fc.Dl;
+        relay_rec[4][rl] = cu.fc.El;
+        relay_rec[5][rl] = cu.fc.w;
+        relay_rec[6][rl] = cu.ll;
+        relay_rec[7][rl] = cu.lm;
+        relay_rec[8][rl] = cu.cur;
+        if (stored) {
+          relay_rec[9][rl] = cu.xm;
+          relay_rec[10][rl] = cu.lc.omz;
+        }
+      }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+      if ((tid & 63) == 0)  // (a vacant row too: its relay wavefront waits for every sweep's flag)
+        __hip_atomic_store(&relay_flag[wave - 4], (uint32_t)it + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    } else {
+      __builtin_amdgcn_s_setprio(2);  // the critical phase first (drawing ahead stays at 0)
+      if (cu.active) {
+        cust_coeffs<D, K, false>(cu, Hs, exp_tab);
+        CLV_P_STAMP(a.stamps, wgi, 2, stp);
+        mh_run_pre_range<0, QR, SPLIT_NC>(cu, pv, Hs[H_S00], Hs[H_S11], g.S, exp_tab);
+        mh_run_pre_range<QR, NQ, SPLIT_NC>(cu, pv, Hs[H_S00], Hs[H_S11], g.S, exp_tab);
+        CLV_P_STAMP(a.stamps, wgi, 3, stp);
+        out = cust_finish<D, K, false>(cu, a, s, stored, Hs, k0, k1, nullptr, exp_tab, st, nullptr);
+      }
+      CLV_P_STAMP(a.stamps, wgi, 4, stp);
+      wave_reduce_gen<NS, SWEEP_REDUCE_CHUNK>(st, red);
+    }
+    __syncthreads();
+    if (relay_abort) return;
+    {  // the workgroup's records, as the helper instance writes them
+      const int j = tid & 63;
+      const int r0 = SPLIT_CW * p;  // first wave row
+      if (j < NS && tid < 128) {
+        if ((p & 1) == 0) {
+          if (tid < 64) {
+            st_wt(parts + (int64_t)(r0 / 4) * NS + j, ((red[0][j] + red[1][j]) + red[2][j]) + red[3][j]);
+          } else {
+            const int b = r0 / 4 + 1;  // first half: the exact prefix of the block's sum
+            if (b < g.nb_local) st_wt(parts + (int64_t)b * NS + j, red[4][j] + red[5][j]);
+          }
+        } else {
+          if (tid < 64) {
+            const int b = (r0 - 2) / 4;  // second half: rows 2 and 3 as they are
+            double* ext = parts + (int64_t)(g.nb_local + 2 * (b / 3)) * NS;
+            st_wt(ext + j, red[0][j]);
+            st_wt(ext + NS + j, red[1][j]);
+          } else {
+            const int b = (r0 + 2) / 4;
+            if (b < g.nb_local) st_wt(parts + (int64_t)b * NS + j, ((red[2][j] + red[3][j]) + red[4][j]) + red[5][j]);
+          }
+        }
+      }
+    }
+    __builtin_amdgcn_s_setprio(0);  // drawing ahead for the next sweep: yield the SIMD
+    CLV_P_STAMP(a.stamps, wgi, 5, stp);
+    CLV_P_STAMP(a.stamps, wgi, 8, stp);
+    CLV_P_STAMP(a.stamps, wgi, 9, stp);
+#ifdef CLV_STAMPS
+    if (stp && a.stamps) a.stamps[1024 * 8 + wgi * 12 + 11] = blockIdx.y * gridDim.x + blockIdx.x;  // dispatch position
+#endif
+    if (cu.active) {
+      if (relayed) {  // the row's new state, as cust_finish left it in the relay wavefront
+        cu.lam = relay_ret[0][rl];
+        cu.mu = relay_ret[1][rl];
+        out = CustOut<D>{cu.lam, cu.mu, 1.0, relay_ret[2][rl], relay_ret[3][rl], 0.0};  // (logs: read by stored sweeps only)
+      }
+      cust_store<D, K>(cu, out, a, c, s, stored, false);
+      if (it + 1 < n_sweeps) {
+        cust_ztau<D, K, false>(cu, a, s + 1, k0, k1, nullptr, exp_tab);
+        const SlotPhilox ph(k0, k1, cu.gi, (uint32_t)(s + 1));
+        mh_pre_variates_range<0, QR, SPLIT_NC>(ph, g.S, pv);
+        if (!relayed) mh_pre_variates_range<QR, NQ, SPLIT_NC>(ph, g.S, pv);
+      }
+    }
+    CLV_P_STAMP(a.stamps, wgi, 6, stp);
+  }
+  if (cu.active) {  // the carried state, once per launch (adopted by the host if nothing aborted)
+    const int64_t ci = (int64_t)c * a_launch.g.n + cu.i;
+    a_launch.lam_out[ci] = cu.lam;
+    a_launch.mu_out[ci] = cu.mu;
+  }
+}
+
+template <int D, int K, int HC, int R = 0>
 __global__ __launch_bounds__(SPLIT_NT, 1) void persist_kernel_split(SweepArgs a, int64_t s_first, int64_t n_sweeps) {
   static_assert(D == 2, "the split layout is bivariate");
   constexpr int NXY = K * D;
@@ -2763,6 +3144,11 @@ __global__ __launch_bounds__(SPLIT_NT, 1) void persist_kernel_split(SweepArgs a,
   fast_tab_fill(exp_tab, tid, SPLIT_NT, false);
   if (tid < HS) Hs[tid] = a.hyper[(int64_t)c * HS + tid];  // sweep s_first: from before this launch
   const bool first_wait = a.pend_in != nullptr;  // a launch's first sweep waits only for a deferred draw
+  CLV_R_STAMP(a, wgi, 4 + wave, true);  // (diagnostic build) the wavefront's SIMD
+  if constexpr (R > 0) {  // the relay instance: wavefronts 6 and 7 finish rows 4 and 5
+    split_relay_sweeps<D, K, R>(a, s_first, n_sweeps, c, p, k0, k1, wgi, it_stamp, parts, pool, red, exp_tab, Hs, &s_abort);
+    return;
+  }
 
   if (wave >= SPLIT_CW) {
     // ================= helper wavefronts =================
@@ -3213,9 +3599,14 @@ hipError_t launch_persist(const SweepArgs& a, int64_t s_first, int64_t n_sweeps,
 }
 
 // The split layout (bivariate, world size 1): a.wg_map is persist_split_layout's map.
-hipError_t launch_persist_split(const SweepArgs& a, int64_t s_first, int64_t n_sweeps, hipStream_t st) {
+hipError_t launch_persist_split(const SweepArgs& a, int64_t s_first, int64_t n_sweeps, hipStream_t st, bool relay) {
   const dim3 grid(split_wgs(a.g.nb_local) + 1, a.g.n_chains);  // + the chain's level-2 workgroup
+  if (relay && !(SPLIT_RELAY_STEPS > 0 && a.g.S > SPLIT_RELAY_STEPS)) return hipErrorInvalidValue;
 #define CLV_CASE(DD, KK, PP)                                                                                        \
+  if (a.g.D == DD && a.g.K == KK && relay) {                                                                      \
+    hipLaunchKernelGGL((persist_kernel_split<DD, KK, CLV_SPLIT_HELP_CHUNKS, SPLIT_RELAY_STEPS>), grid, dim3(SPLIT_NT), 0, st, a, s_first, n_sweeps); \
+    return hipGetLastError();                                                                                     \
+  }                                                                                                               \
   if (a.g.D == DD && a.g.K == KK) {                                                                               \
     hipLaunchKernelGGL((persist_kernel_split<DD, KK, CLV_SPLIT_HELP_CHUNKS>), grid, dim3(SPLIT_NT), 0, st, a, s_first, n_sweeps); \
     return hipGetLastError();                                                                                     \
@@ -3226,9 +3617,17 @@ hipError_t launch_persist_split(const SweepArgs& a, int64_t s_first, int64_t n_s
 }
 
 // Workgroups per CU and scratch bytes per lane of a split instance (the layout needs 1 and 0).
-hipError_t persist_split_resources(int D, int K, int* blocks_per_cu, size_t* scratch_bytes) {
+hipError_t persist_split_resources(int D, int K, int* blocks_per_cu, size_t* scratch_bytes, bool relay) {
   hipFuncAttributes fa{};
+  if (relay && SPLIT_RELAY_STEPS <= 0) return hipErrorInvalidValue;
 #define CLV_CASE(DD, KK, PP)                                                                                      \
+  if (D == DD && K == KK && relay) {                                                                              \
+    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, persist_kernel_split<DD, KK, CLV_SPLIT_HELP_CHUNKS, SPLIT_RELAY_STEPS>, SPLIT_NT, 0); \
+    if (e != hipSuccess) return e;                                                                                \
+    e = hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&persist_kernel_split<DD, KK, CLV_SPLIT_HELP_CHUNKS, SPLIT_RELAY_STEPS>)); \
+    *scratch_bytes = fa.localSizeBytes;                                                                           \
+    return e;                                                                                                     \
+  }                                                                                                               \
   if (D == DD && K == KK) {                                                                                       \
     hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, persist_kernel_split<DD, KK, CLV_SPLIT_HELP_CHUNKS>, SPLIT_NT, 0); \
     if (e != hipSuccess) return e;                                                                                \

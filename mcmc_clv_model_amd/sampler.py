@@ -269,12 +269,17 @@ class HipSampler:
         """How clv_run launches (clv_launch_info): persistent kernel or one launch per sweep.
         ``workgroups`` counts logical workgroups (one per customer block, + the level-2 one per chain
         when persistent); ``physical_workgroups`` what is dispatched and ``layout`` the persistent
-        grid's layout: None, "block", "split", or "block (split aborted)"."""
+        grid's layout: None, "block", "split", or "block (split aborted)".  ``relay_steps``
+        (clv_split_relay_steps): the MH step at which the split layout's relay instance hands rows
+        4 and 5 to wavefronts 6 and 7, 0 when the helper instance (or another layout) runs."""
         out = (ctypes.c_int64 * 6)()
         check(self._L.clv_launch_info(self.h, out))
+        relay = ctypes.c_int32(0)
+        check(self._L.clv_split_relay_steps(self.h, ctypes.byref(relay)))
         return dict(persistent=bool(out[0]), persist_blocks_per_cu=int(out[1]), n_cu=int(out[2]),
                     workgroups=int(out[3]), physical_workgroups=int(out[4]),
-                    layout={1: "block", 2: "split", -1: "block (split aborted)"}.get(int(out[5])))
+                    layout={1: "block", 2: "split", -1: "block (split aborted)"}.get(int(out[5])),
+                    relay_steps=int(relay.value))
 
     # ---- peer exchange (world size > 1 through the persistent kernel, include/clvmcmc.h)
     IPC_HANDLE_BYTES = 64

@@ -46,6 +46,22 @@ def main(workload="c2", sweeps=1500):
     print(f"{workload}: persistent={info['persistent']}, layout={info['layout']}, chains={s.chains}, N={s.n}, "
           f"{nb} customer workgroups per chain")
     us = 0.01
+    sp = None
+    if info["layout"] == "split":
+        # the split layout's own record: relay stamps (rows 4, 5: flag seen, row done) and the HW_ID
+        # of every wavefront of a customer workgroup (bits 5:4: the SIMD it sits on)
+        nbl = -(-s.n // 256)
+        raw = np.zeros(s.chains * (nbl + 1) * 16, np.uint64)
+        assert s._L.clv_debug_split_stamps(s.h, raw.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))) == 0
+        sp = raw.astype(np.int64)[:s.chains * (nb + 1) * 16].reshape(s.chains, nb + 1, 16)
+        simd = (sp[:, :nb, 4:12] >> 4) & 3
+        print(f"  relay_steps={info['relay_steps']}; wavefront -> SIMD over {simd.shape[0] * simd.shape[1]} customer workgroups "
+              "(count of workgroups per SIMD 0..3):")
+        for w in range(8):
+            cnt = np.bincount(simd[:, :, w].ravel(), minlength=4)
+            print(f"    wavefront {w}: {cnt.tolist()}" + ("" if cnt[w % 4] == cnt.sum() else "   <- not w % 4 everywhere"))
+        pair = lambda a, b: int((simd[:, :, a] != simd[:, :, b]).sum())  # noqa: E731
+        print(f"    rows 4/6 on different SIMDs in {pair(4, 6)}, rows 5/7 in {pair(5, 7)} of {simd.shape[0] * simd.shape[1]} workgroups")
     for c in range(s.chains):
         cust, tail = wg[c, :nb], wg[c, nb]
         R = tail[5]
@@ -69,6 +85,13 @@ def main(workload="c2", sweeps=1500):
                       nextdone=cust[m, 6] - R)
             print(f"    {tag} x{int(m.sum()):3d} (median/max us): " +
                   "  ".join(f"{n} {np.median(v) * us:5.2f}/{v.max() * us:5.2f}" for n, v in ph.items()))
+        if sp is not None and info["relay_steps"] > 0:
+            rs = sp[c, :nb, :4]
+            on = rs[:, 0] > 0
+            if on.any():
+                rel = dict(flag4=rs[on, 0] - R, done4=rs[on, 1] - R, flag5=rs[on, 2] - R, done5=rs[on, 3] - R)
+                print("    relay wavefronts, from the publish (median/max us): " +
+                      "  ".join(f"{n} {np.median(v) * us:5.2f}/{v.max() * us:5.2f}" for n, v in rel.items()))
         print(f"    last partial issued {(cust[:, 5].max() - R) * us:6.2f}  tail: variates {(tail[1] - tail[0]) * us:5.2f}"
               f"  partials seen {(tail[2] - R) * us:6.2f}  draw {(tail[3] - tail[2]) * us:5.2f} (reduce {(tail[6] - tail[2]) * us:4.2f}"
               f" algebra {(tail[7] - tail[6]) * us:4.2f} finalize {(tail[3] - tail[7]) * us:4.2f})"
