@@ -363,7 +363,77 @@ GRID_CASES = {
     "g_tri9_u16": _grid_case(3, 9, _N41, 2, 16, dict(default=False), 3107, (41, 16, 3, 3), {"last unit": (2 * 16 * BLOCK, _N41)}),
 }
 GRID_RUNS = [(n, m) for n, c in GRID_CASES.items() for m in c["modes"]]
-ALL_CASES = {**CASES, **INSTANCE_CASES, **GRID_CASES}
+
+
+# ---------------------------------------------------------------------------------------------
+# the split layout of the persistent sweep (persist_kernel_split; tests/test_gpu_split_model.py)
+# ---------------------------------------------------------------------------------------------
+ROW = 64               # customers per wave row; a block is 4 rows, a split workgroup hosts 6
+SPLIT_MAX_NB = 256     # one level-2 lane per block: the split layout's largest chain
+SPLIT_S = 14           # above both supported relay points (8, 12), a partial last chunk under either
+
+
+def split_wgs(nb):
+    """Customer workgroups per chain of the split layout: a chain's 4 nb wave rows dealt six at a time
+    (the plan rule restated; the level-2 workgroup comes on top)."""
+    return -(-4 * nb // 6)
+
+
+def _split_instance_case(K):
+    """One case per compiled bivariate split instance (helper and relay).  N = 769: 4 blocks in 3
+    workgroups — block 1 split with live lanes in both halves (its extension records are customers
+    384..511); workgroup 1 with all six rows live, its relayed rows customers 640..767; workgroup 2 with
+    one live lane, in block 3, and no block 4.  The state read between the launches forces the deferred
+    level-2 draw through the flush kernel and gives a launch whose first sweep waits on a pending draw."""
+    return dict(D=2, covs=[f"c{k}" for k in range(1, K)], data=("tiled", 769, K - 1), S=SPLIT_S, chains=2,
+                chain_first=K % 2, seed=3300 + K, burnin=0, mcmc=3, thin=1,
+                drive=[("run", 1), ("state",), ("run", 2)])
+
+
+SPLIT_INSTANCE_CASES = {f"split_bi{K}": _split_instance_case(K) for K in range(1, 10)}
+# customer ranges [lo, hi) the instance cases' power checks leave out (as GRID_CASES' drop)
+SPLIT_INSTANCE_DROP = {"block 1's extension records": (BLOCK + 2 * ROW, 2 * BLOCK),
+                       "workgroup 1's relayed rows": (10 * ROW, 12 * ROW)}
+
+
+def _rows(b, first, n_rows=1):
+    """Customers of rows [first, first + n_rows) of block b."""
+    return (b * BLOCK + first * ROW, b * BLOCK + (first + n_rows) * ROW)
+
+
+def _split_grid_case(K, n, layout, env, drop, seed, data="tiled", covs=None, chains=1, S=SPLIT_S):
+    return dict(D=2, covs=[f"c{k}" for k in range(1, K)] if covs is None else covs,
+                data=(data, n, K - 1 if covs is None else 0), S=S, chains=chains, chain_first=0, seed=seed,
+                burnin=0, mcmc=2, thin=1, drive=[("run", 2)], layout=layout, env=env, drop=drop)
+
+
+# layout: "split" / "block": what the handle must report; "choice": the default environment, where it must
+# be what clv_debug_split_choice gives for the device's CU count.  env: the environment of the run.
+_N129, _N256, _N257, _NC2 = 128 * BLOCK + 1, 255 * BLOCK + 1, 256 * BLOCK + 1, 23570
+SPLIT_GRID_CASES = {
+    # nb = 129: level-2 lanes in three wavefronts; block 127 (the only b % 3 == 1 at a wavefront's last
+    # lane below 256) pairs with lane 126; a one-customer last block.  130 block workgroups do not
+    # double up on 256 CUs, so the layout is forced.
+    "sg_bi2_129": _split_grid_case(2, _N129, "split", {"CLV_PERSISTENT": "1", "CLV_PERSIST_LAYOUT": "split"},
+                                   {"block 127 row 2": _rows(127, 2), "block 127 row 3": _rows(127, 3),
+                                    "block 64 row 3": _rows(64, 3), "block 124 row 3": _rows(124, 3),
+                                    "last block": (128 * BLOCK, _N129)}, 3401),
+    # nb = SPLIT_MAX_NB: every level-2 lane holds a block, 171 + 1 physical workgroups, 256 + 170 records
+    "sg_bi1_256": _split_grid_case(1, _N256, "choice", {},
+                                   {"block 253 rows 2-3": _rows(253, 2, 2), "block 255 (one customer)": (255 * BLOCK, _N256),
+                                    "block 0": (0, BLOCK)}, 3402),
+    # nb = 257: the forced split layout is declined; lane 0 of the block layout's level-2 workgroup holds
+    # blocks 0 and 256; customer 65,536 is the first large index
+    "sg_bi1_257": _split_grid_case(1, _N257, "block", {"CLV_PERSIST_LAYOUT": "split"},
+                                   {"block 0": (0, BLOCK), "block 256 (one customer)": (256 * BLOCK, _N257),
+                                    "block 255": (255 * BLOCK, 256 * BLOCK)}, 3403),
+    # the benchmark's own grid (c2): 4 x 63 workgroups on a 4-CU margin, chain-major
+    "sg_c2": _split_grid_case(2, _NC2, "choice", {},
+                              {"chain-last block": (92 * BLOCK, _NC2), "block 91 rows 2-3": _rows(91, 2, 2),
+                               "block 64 row 3": _rows(64, 3)}, 42, data="full", covs=["first_sales_scaled"],
+                              chains=4, S=20),
+}
+ALL_CASES = {**CASES, **INSTANCE_CASES, **GRID_CASES, **SPLIT_INSTANCE_CASES, **SPLIT_GRID_CASES}
 
 
 def case_frame(case):

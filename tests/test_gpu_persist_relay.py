@@ -9,7 +9,9 @@ wrong:
   n = 257   row 4 holds one live lane and row 5 none
   n = 384   one workgroup with rows 4 and 5 full
   n = 385   a second workgroup whose relay rows are vacant (their flags are still raised and awaited)
-  n = 640   two workgroups, the second with live relayed rows
+  n = 640   two workgroups; the second's rows 0-3 are live, its relay rows (customers 640..767) vacant
+  n = 769   three workgroups, the second with live relayed rows (customers 640..767), full sink: its
+            stored level-1 draws are compared
   n = 1537  several workgroups, vacant wavefronts in the last (4 chains from chain 3, K = 5, summary)
 
 K = 1, 2, 5; both sinks; S = 1, R - 1, R (not relayed: relay_steps reports 0), R + 1, 13, 20 with R read
@@ -36,6 +38,8 @@ CASES = [
     (640, 1, 0, 1, "1", "full"),
     (640, 2, 0, 5, "20", "full"),
     (640, 1, 0, 2, "13", "summary"),
+    (769, 2, 0, 2, "R+1", "full"),
+    (769, 1, 0, 1, "20", "full"),
     (1537, 4, 3, 5, "20", "summary"),
 ]
 

@@ -112,10 +112,11 @@ def _device_variates(L, seed, chain, sweep, n, S):
 class Device:
     """What one run of a case left on the device, indexed by sweep."""
 
-    def __init__(self, L, case, mp, persistent, blocks_per_unit=0, geometry=None):
+    def __init__(self, L, case, mp, persistent, blocks_per_unit=0, geometry=None, on_info=None):
         """``persistent``: the launch_info flag asserted (None: whatever the build chose, kept in
         self.persistent); ``geometry``: (blocks, blocks per unit, units per rank, global units) asserted
-        against the handle before the run."""
+        against the handle before the run; ``on_info``: called with launch_info() and "before" / "after"
+        ahead of the first launch and again after the last."""
         from mcmc_clv_model_amd.sampler import HipSampler, build_problem
         self.case, self.mp = case, mp
         self.C, self.T = case["chains"], M.n_sweeps_of(case)
@@ -136,12 +137,16 @@ class Device:
                 _, nd, stride = s.partials()
                 assert stride == mp.K * mp.D + mp.D * (mp.D + 1) // 2 + 1 and nd == self.C * stride * upr
                 assert upr == units == -(-nb // bpu)  # world size 1: every unit is this rank's
+            if on_info is not None:
+                on_info(s.launch_info(), "before")
             for act in case["drive"]:
                 if act[0] == "run":
                     s.run(act[1])
                 else:
                     self.states[s.sweeps_done] = s.get_state()
             assert s.sweeps_done == self.T
+            if on_info is not None:
+                on_info(s.launch_info(), "after")
             self.l1, self.l2, self.ll = s.read_draws()
         # the device's variates of every (chain, sweep), one sweep beyond the run and, for chain 0,
         # of the next chain key (the power checks' wrong inputs)

@@ -114,11 +114,13 @@ def test_level2_lane_pairing(nb):
 def test_eligibility(L):
     ok = lambda C, nb, n_cu=256, bpc=1: bool(L.clv_debug_split_choice(C, nb, bpc, n_cu))  # noqa: E731
     fits = lambda C, nb, n_cu=256, bpc=1: bool(L.clv_debug_split_fits(C, nb, bpc, n_cu))  # noqa: E731
-    assert ok(4, 93) and fits(4, 93)              # c2 / c3: 4 x (62 + 1) = 252 of 256 CUs, margin 4
+    assert ok(4, 93) and fits(4, 93)              # c2 (bivariate; the trivariate c3, on the same customers,
+                                                  # never takes this layout): 4 x (62 + 1) = 252 of 256 CUs, margin 4
     assert not ok(4, 94) and not fits(4, 94)      # 4 x (63 + 1) = 256
     assert not ok(1, 496) and not fits(1, 496)    # one level-2 lane per block: nb <= 256
     assert not ok(4, 257) and not fits(1, 257)
     assert not ok(4, 40) and fits(4, 40)          # the block layout does not double up: 164 <= 256
+    assert ok(1, 129) is False and fits(1, 129)   # nor do 130: the model test of nb = 129 has to force the layout
     assert fits(1, 256) and ok(1, 256)            # 172 CUs; its 257 block workgroups double up on 256
     assert ok(1, 256, 200) and not fits(1, 256, 173) and fits(1, 256, 174)  # margin max(1, n_cu / 64)
     assert not fits(4, 93, 256, 0) and not fits(0, 93) and not fits(4, 0)

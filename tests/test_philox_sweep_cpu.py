@@ -12,7 +12,8 @@ here it is pinned to the REFERENCE, never to the kernel:
 * at every shape the GPU module uses, the share of (chain, sweep, customer) lanes whose decision
   margin is below the comparison tolerance stays within the 0.1% cap, and the level-2 tolerance
   covers ten times the measured sensitivity to the variates' and Y's documented uncertainty — for
-  CASES, INSTANCE_CASES (every compiled (D, K)) and GRID_CASES (up to 153,345 customers) alike;
+  CASES, INSTANCE_CASES (every compiled (D, K)), GRID_CASES (up to 153,345 customers) and the split
+  layout's SPLIT_INSTANCE_CASES / SPLIT_GRID_CASES (tests/test_gpu_split_model.py) alike;
 * the coverage events the GPU module asserts per instance case (INSTANCE_COVERAGE) are exactly those
   the model's free run of the case produces;
 * at the grid cases' sizes numpy's mean of the likelihood terms and the exactly rounded one differ by
@@ -310,7 +311,7 @@ def test_instance_coverage_table_is_what_the_model_produces(free_runs, name):
     assert {k for k, v in n.items() if v > 0} == set(M.INSTANCE_COVERAGE[name])
 
 
-@pytest.mark.parametrize("name", list(M.GRID_CASES))
+@pytest.mark.parametrize("name", list(M.GRID_CASES) + list(M.SPLIT_GRID_CASES))
 def test_loglik_mean_does_not_depend_on_the_summation_order(free_runs, name):
     """The stored log-likelihood is a mean over up to 153,345 terms, summed on the device per block, per
     unit and over the units.  numpy's pairwise mean of the model's terms, which the GPU module compares
