@@ -466,6 +466,56 @@ int clv_lifetime_value_sampler(clv_sampler* s, const double* monetary, double de
  * batch: a test knob, the results do not depend on it. */
 int clv_ltv_info(int64_t* out);
 
+/* ---- Model comparison: pointwise log-likelihood, WAIC and PSIS-LOO (csrc/ic.hip) ----
+ * The pointwise log-likelihood of customer i under stacked draw d is the Pareto/NBD individual
+ * likelihood given (lambda, mu), marginal over z and tau, in the form that cannot overflow; with
+ * ml = lambda + mu:
+ *   l = ((x log(lambda) - log(ml)) - ml t_x) + log(mu + lambda exp(-(ml (T_cal - t_x))))
+ * and, with log_s given (width 5 only; omega2 > 0), one observation of log_s ~ N(log eta, omega2):
+ *       + (-log(2 pi omega2) / 2 - (log_s - log eta)^2 / (2 omega2)).
+ * log_s NULL on a width-5 array compares the transaction part only.
+ * Per customer over the S = n_draws values (out [n][CLV_N_IC_STATS]):
+ *   lppd = logsumexp(l) - log S, p_waic = var(l) (ddof 0), elpd_waic = lppd - p_waic;
+ *   PSIS (Vehtari, Gelman & Gabry 2017, as ArviZ): log ratios r = -l, x = r - max r,
+ *   M = ceil(min(S / 5, 3 sqrt(S / reff))), cutoff = max((M + 1)-th largest x, log(DBL_MIN)), tail =
+ *   every x > cutoff (tail_len of them, at most M); a tail of 5 or more is fitted with Zhang &
+ *   Stephens' generalised Pareto estimator (pareto_k, shrunk towards 0.5 by a prior worth 10
+ *   values) and replaced by the fit's quantiles, every log weight capped at 0 and normalised;
+ *   a shorter tail or a non-finite fit keeps the raw weights and reports pareto_k = +infinity;
+ *   elpd_loo = logsumexp(log weight + l), p_loo = lppd - elpd_loo.
+ * A customer with a non-finite l has NaN in all its columns.  Every sum has a fixed order (ic.hip):
+ * the results do not depend on the launch geometry or the customer batch; no atomics.
+ * CLV_EINVAL before any device call: a null pointer, n_draws < 8 or > 2^20, n < 1, width not 4 or
+ * 5, log_s with width 4, omega2 not in (0, inf) with log_s, reff not in (0, inf) or so small that M
+ * exceeds 4096. */
+enum {
+  CLV_IC_LPPD = 0, CLV_IC_P_WAIC, CLV_IC_ELPD_WAIC, CLV_IC_ELPD_LOO, CLV_IC_P_LOO, CLV_IC_PARETO_K,
+  CLV_IC_TAIL_LEN, CLV_N_IC_STATS
+};
+/* out [n_draws][n]. */
+int clv_pointwise_loglik(int32_t device, const double* level1, int64_t n_draws, int64_t n, int32_t width,
+                         const int32_t* x, const double* t_x, const double* T_cal,
+                         const double* log_s /* NULL: no spend term */, double omega2, double* out);
+/* The statistics of any caller-supplied matrix loglik [n_draws][n]. */
+int clv_psis_loo(int32_t device, const double* loglik, int64_t n_draws, int64_t n, double reff, double* out);
+/* clv_pointwise_loglik and clv_psis_loo fused (the same bits): the matrix stays on the device. */
+int clv_information_criteria(int32_t device, const double* level1, int64_t n_draws, int64_t n, int32_t width,
+                             const int32_t* x, const double* t_x, const double* T_cal, const double* log_s,
+                             double omega2, double reff, double* out);
+/* From the draws a CLV_SINK_FULL sampler holds in HBM and the data it was created with (spend != 0:
+ * its log_s; CLV_ESTATE as clv_predict_sampler). */
+int clv_information_criteria_sampler(clv_sampler* s, int32_t spend, double omega2, double reff, double* out);
+/* The limits of csrc/ic.hip: out[0] customers per workgroup of the pass (256), out[1] draws per LDS
+ * tile of its transpose, out[2] keys per sort batch, out[3] the fewest and out[4] the most stacked
+ * draws, out[5] the longest tail, out[6] the shortest tail that is fitted. */
+int clv_ic_info(int64_t* out);
+/* clv_information_criteria with batch_keys (> 0: keys per sort batch, whole 256-customer blocks, at
+ * least one) and grid (> 0: the most workgroups per launch) overridden: the tests' knobs, the
+ * results do not depend on them. */
+int clv_debug_information_criteria(int32_t device, const double* level1, int64_t n_draws, int64_t n, int32_t width,
+                                   const int32_t* x, const double* t_x, const double* T_cal, const double* log_s,
+                                   double omega2, double reff, int64_t batch_keys, int32_t grid, double* out);
+
 /* ---- Convergence diagnostics on device (csrc/diag.hip) ----
  * The reference checks convergence with ArviZ on its level-2 draws (bivariate/analysis_abe.py:
  * 651-706: az.summary, az.plot_autocorr).  Here a series is m chains x n draws (n >= 8) of one

@@ -16,15 +16,21 @@ mle.ParetoNBDFitter, a drop-in for what the reference uses of lifetimes', with p
 and mape_aggregate (analysis_bi_helpers.py:29).  What Abe (2015) derives from the draws, which the
 reference stops short of: every customer's posterior lifetime value, the customer equity and the
 elasticity of CLV to the covariates (lifetime_value, customer_equity, lifetime_value_elasticities).
+Which model the data prefer: the pointwise log-likelihood, WAIC and PSIS-LOO with the Pareto k
+diagnostic per customer, and a paired comparison with a standard error (pointwise_log_likelihood,
+information_criteria, psis_loo, compare_models) — az.waic / az.loo / az.compare, which the reference
+prepares for and never calls.
 
 The per-sweep work runs in hand-written HIP kernels for gfx950 (csrc/), bound through the C
 ABI in include/clvmcmc.h.  There is no CPU fallback.
 """
-from .analysis import (chain_total_loglik, compute_table4, customer_equity, draw_future_transactions,
-                       draw_future_transactions_rfm_m, extract_correlation, level1_diagnostics,
+from .analysis import (chain_total_loglik, compare_models, compute_table4, customer_equity,
+                       draw_future_transactions, draw_future_transactions_rfm_m, extract_correlation,
+                       information_criteria, level1_diagnostics,
                        level1_rank_diagnostics, level2_autocorr, level2_diagnostics, level2_rank_diagnostics,
-                       level2_summary, lifetime_value, lifetime_value_elasticities, post_mean_lambdas,
-                       post_mean_mus, posterior_weekly_tracking, summarize_level2, summary_rhat)
+                       level2_summary, lifetime_value, lifetime_value_elasticities, pointwise_log_likelihood,
+                       post_mean_lambdas, post_mean_mus, posterior_weekly_tracking, psis_loo, summarize_level2,
+                       summary_rhat)
 from .bivariate import mcmc_draw_parameters
 from .mle import ParetoNBDFitter, mape_aggregate, pnbd_weekly_tracking
 from .trivariate import mcmc_draw_parameters_rfm_m
@@ -35,5 +41,6 @@ __all__ = ["mcmc_draw_parameters", "mcmc_draw_parameters_rfm_m", "draw_future_tr
            "level2_autocorr", "summarize_level2", "extract_correlation", "summary_rhat",
            "level1_rank_diagnostics", "level2_rank_diagnostics", "level2_summary", "ParetoNBDFitter",
            "pnbd_weekly_tracking", "mape_aggregate", "lifetime_value", "customer_equity",
-           "lifetime_value_elasticities"]
+           "lifetime_value_elasticities", "pointwise_log_likelihood", "information_criteria", "psis_loo",
+           "compare_models"]
 __version__ = "0.1.0"

@@ -150,6 +150,15 @@ def lib() -> ctypes.CDLL:
                                          c_double, dp, dp]),
         "clv_lifetime_value_sampler": (c_int32, [sp, dp, c_double, c_double, c_double, c_double, dp, dp]),
         "clv_ltv_info": (c_int32, [POINTER(c_int64)]),
+        "clv_pointwise_loglik": (c_int32, [c_int32, dp, c_int64, c_int64, c_int32, POINTER(c_int32), dp, dp, dp,
+                                           c_double, dp]),
+        "clv_psis_loo": (c_int32, [c_int32, dp, c_int64, c_int64, c_double, dp]),
+        "clv_information_criteria": (c_int32, [c_int32, dp, c_int64, c_int64, c_int32, POINTER(c_int32), dp, dp, dp,
+                                               c_double, c_double, dp]),
+        "clv_information_criteria_sampler": (c_int32, [sp, c_int32, c_double, c_double, dp]),
+        "clv_ic_info": (c_int32, [POINTER(c_int64)]),
+        "clv_debug_information_criteria": (c_int32, [c_int32, dp, c_int64, c_int64, c_int32, POINTER(c_int32), dp,
+                                                     dp, dp, c_double, c_double, c_int64, c_int32, dp]),
         "clv_diagnostics": (c_int32, [c_int32, dp, c_int32, c_int64, c_int64, c_int32, c_uint32, dp]),
         "clv_diagnostics_sampler": (c_int32, [sp, c_uint32, dp, dp]),
         "clv_autocorr": (c_int32, [c_int32, dp, c_int32, c_int64, c_int64, c_int32, dp]),
@@ -212,6 +221,23 @@ def ltv_info() -> dict:
     check(lib().clv_ltv_info(out))
     return dict(block=int(out[0]), tile_draws=int(out[1]), batch_keys=int(out[2]), max_draws=int(out[3]),
                 sd_tile_draws=int(out[4]))
+
+
+# Columns of clv_information_criteria() / clv_psis_loo() (include/clvmcmc.h CLV_IC_*).
+IC_STATS = ("lppd", "p_waic", "elpd_waic", "elpd_loo", "p_loo", "pareto_k", "tail_len")
+# The limits of csrc/ic.hip (clv_ic_info reports the library's own; tests/test_ic_cpu.py compares):
+# customers per workgroup of the pass, draws per LDS tile of its transpose, keys per sort batch, the
+# fewest and the most stacked draws, the longest tail, the shortest tail that is fitted.
+IC_BLOCK, IC_TILE_DRAWS, IC_BATCH_KEYS, IC_MIN_DRAWS, IC_MAX_DRAWS, IC_MAX_TAIL, IC_MIN_FIT = (
+    256, 16, 1 << 27, 8, 1 << 20, 4096, 5)
+
+
+def ic_info() -> dict:
+    """The limits of csrc/ic.hip (clv_ic_info)."""
+    out = (c_int64 * 7)()
+    check(lib().clv_ic_info(out))
+    return dict(block=int(out[0]), tile_draws=int(out[1]), batch_keys=int(out[2]), min_draws=int(out[3]),
+                max_draws=int(out[4]), max_tail=int(out[5]), min_fit=int(out[6]))
 
 
 def exported_symbols():

@@ -21,6 +21,9 @@ Reference functions mirrored (same names, arguments, defaults and return layout)
 * ``lifetime_value``, ``customer_equity``, ``lifetime_value_elasticities`` — what Abe (2015) derives
   from the level-1 draws and the reference leaves out: every customer's posterior lifetime value,
   the value of the customer base and the elasticity of CLV to the covariates (``csrc/ltv.hip``).
+* ``pointwise_log_likelihood``, ``information_criteria``, ``psis_loo``, ``compare_models`` — what
+  ``az.waic`` / ``az.loo`` / ``az.compare`` would give on the draws the reference wraps in
+  ``az.from_dict`` and never compares: WAIC and PSIS-LOO per customer (``csrc/ic.hip``).
 
 The per-customer / per-draw work runs in ``csrc/analysis.hip`` through the C ABI (``clv_predict``,
 ``clv_track``, ``clv_level1_summary``, ``clv_chain_total_loglik``); the host only reshapes and
@@ -44,7 +47,8 @@ __all__ = ["draw_future_transactions", "draw_future_transactions_rfm_m", "post_m
            "chain_total_loglik", "compute_table4", "level1_summary", "posterior_weekly_tracking",
            "level1_diagnostics", "level2_diagnostics", "level2_autocorr", "summarize_level2", "extract_correlation",
            "summary_rhat", "level1_rank_diagnostics", "level2_rank_diagnostics", "level2_summary",
-           "lifetime_value", "customer_equity", "lifetime_value_elasticities"]
+           "lifetime_value", "customer_equity", "lifetime_value_elasticities",
+           "pointwise_log_likelihood", "information_criteria", "psis_loo", "compare_models"]
 
 
 def _stacked_level1(level1_chains) -> np.ndarray:
@@ -340,6 +344,201 @@ def lifetime_value_elasticities(draws: Dict[str, Any], covariates, *, discount_r
             index.append((name, comp))
     idx = pd.MultiIndex.from_arrays([[i[0] for i in index], [i[1] for i in index]], names=["covariate", "component"])
     return pd.DataFrame(rows, columns=["mean", "p025", "p975"], index=idx)
+
+
+# ---- model comparison: WAIC and PSIS-LOO (csrc/ic.hip) -----------------------------------------
+def ic_params(spend=False, omega2=None, reff=1.0, log_s=None) -> dict:
+    """spend / omega2 / reff of the information criteria, validated (ValueError) on the host; the
+    default omega2 of the spend term is var(log_s, ddof 1), the sampler's own."""
+    spend = bool(spend)
+    r = float(reff)
+    if not (np.isfinite(r) and r > 0.0):
+        raise ValueError(f"reff must be finite and > 0 (got {reff!r})")
+    w2 = 0.0
+    if spend:
+        if omega2 is None:
+            if log_s is None or len(log_s) < 2:
+                raise ValueError("spend=True needs omega2 or at least two customers' log_s for its default")
+            omega2 = np.var(log_s, ddof=1)
+        w2 = float(omega2)
+        if not (np.isfinite(w2) and w2 > 0.0):
+            raise ValueError(f"omega2 must be finite and > 0 (got {omega2!r})")
+    elif omega2 is not None:
+        raise ValueError("omega2 belongs to the spend term (spend=True)")
+    return dict(spend=spend, omega2=w2, reff=r)
+
+
+def _ic_shape(nd: int, n: int, w: int, spend: bool, reff: float) -> None:
+    if nd < _lib.IC_MIN_DRAWS or nd > _lib.IC_MAX_DRAWS:
+        raise ValueError(f"{nd} stacked draws: the information criteria take {_lib.IC_MIN_DRAWS} to "
+                         f"{_lib.IC_MAX_DRAWS}")
+    if n < 1:
+        raise ValueError("no customer")
+    if spend and w != 5:
+        raise ValueError("spend=True needs the trivariate model's draws (the eta column)")
+    if np.ceil(min(nd / 5.0, 3.0 * np.sqrt(nd / reff))) > _lib.IC_MAX_TAIL:
+        raise ValueError(f"reff = {reff!r} gives a tail of more than {_lib.IC_MAX_TAIL} draws")
+
+
+def _ic_data(cbs, n: int, spend: bool):
+    """x (int32), t_x, T_cal and (spend) log_s of the CBS as contiguous arrays of n entries."""
+    x = np.ascontiguousarray(cbs["x"].to_numpy(), dtype=np.int32)
+    t_x = np.ascontiguousarray(cbs["t_x"].to_numpy(float))
+    T_cal = np.ascontiguousarray(cbs["T_cal"].to_numpy(float))
+    if not (x.shape[0] == t_x.shape[0] == T_cal.shape[0] == n):
+        raise ValueError("cbs and draws disagree on the number of customers")
+    log_s = None
+    if spend:
+        if "log_s" not in cbs:
+            raise ValueError("spend=True needs a log_s column in cbs")
+        log_s = np.ascontiguousarray(cbs["log_s"].to_numpy(float))
+    return x, t_x, T_cal, log_s
+
+
+def fixed_order_sum(v) -> float:
+    """Sum of a per-customer column in the project's fixed order (csrc/pnbd.hip): zero-padded
+    256-customer blocks by the tree (offsets 128 ... 1), then lane t adds the block partials t,
+    t + 256, ... in turn and the lanes go through the same tree."""
+    def tree(a):
+        off = _lib.BLOCK // 2
+        while off:
+            a[:, :off] += a[:, off:2 * off]
+            off >>= 1
+        return a[:, 0]
+    v = np.asarray(v, np.float64)
+    nb = -(-len(v) // _lib.BLOCK)
+    part = tree(np.pad(v, (0, nb * _lib.BLOCK - len(v))).reshape(nb, _lib.BLOCK))
+    rows = np.pad(part, (0, -(-nb // _lib.BLOCK) * _lib.BLOCK - nb)).reshape(-1, _lib.BLOCK)
+    acc = np.zeros(_lib.BLOCK)
+    for row in rows:
+        acc = acc + row
+    return float(tree(acc[None])[0])
+
+
+def bad_k_threshold(n_samples: int) -> float:
+    """The Pareto k above which PSIS-LOO is not to be trusted: min(1 - 1 / log10(S), 0.7)."""
+    return min(1.0 - 1.0 / np.log10(n_samples), 0.7)
+
+
+def ic_frames(stats: np.ndarray, n_samples: int) -> dict:
+    """The per-customer columns [n][len(_lib.IC_STATS)] as {"pointwise", "waic", "loo"}: the totals
+    are formed here in float64 with :func:`fixed_order_sum` — elpd the sum of the per-customer
+    values, se = sqrt(N var(., ddof 0)) (deviations from the mean, squares, the same sum), p the sum
+    of the penalties, n_bad_k the customers with pareto_k above :func:`bad_k_threshold`, warning =
+    any such customer (loo) or any p_waic > 0.4 (waic, as az.waic).  A NaN customer (a non-finite
+    log-likelihood) makes the totals NaN."""
+    pw = pd.DataFrame(stats, columns=list(_lib.IC_STATS))
+    n = stats.shape[0]
+
+    def total(col):
+        v = pw[col].to_numpy()
+        mean = fixed_order_sum(v) / n
+        dev = v - mean
+        return fixed_order_sum(v), float(np.sqrt(n * (fixed_order_sum(dev * dev) / n)))
+    k = pw["pareto_k"].to_numpy()
+    n_bad = int(np.count_nonzero(k > bad_k_threshold(n_samples)))
+    rows = {}
+    for name, ecol, pcol in (("waic", "elpd_waic", "p_waic"), ("loo", "elpd_loo", "p_loo")):
+        elpd, se = total(ecol)
+        warn = bool(n_bad > 0) if name == "loo" else bool(np.any(pw["p_waic"].to_numpy() > 0.4))
+        rows[name] = pd.DataFrame([dict(elpd=elpd, se=se, p=fixed_order_sum(pw[pcol].to_numpy()),
+                                        n_samples=int(n_samples), n_data_points=int(n),
+                                        n_bad_k=n_bad if name == "loo" else 0, warning=warn)])
+    return dict(pointwise=pw, waic=rows["waic"], loo=rows["loo"])
+
+
+def _i32p(a: np.ndarray):
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+
+
+def pointwise_log_likelihood(draws: Dict[str, Any], cbs: pd.DataFrame, *, spend: bool = False, omega2=None,
+                             device: int = -1) -> np.ndarray:
+    """The log-likelihood of every customer under every stacked draw, on the GPU (``csrc/ic.hip``,
+    ``clv_pointwise_loglik``): float64 (n_draws_total, n_customers), chains stacked in order.  It is
+    marginal over z and tau — the Pareto/NBD individual likelihood given the draw's (lambda, mu) —
+    unlike the reference's ``log_likelihood`` and ``chain_total_loglik``, which condition on them.
+    ``spend=True`` (trivariate draws) adds one observation of ``log_s ~ N(log eta, omega2)``;
+    ``omega2`` defaults to ``var(cbs["log_s"], ddof=1)``, the sampler's.  ``spend=False`` on
+    trivariate draws gives the transaction part alone, comparable with a bivariate fit."""
+    a = _stacked_level1(draws.get("level_1"))
+    nd, n, w = a.shape
+    x, t_x, T_cal, log_s = _ic_data(cbs, n, spend)
+    par = ic_params(spend, omega2, 1.0, log_s)
+    _ic_shape(nd, n, w, par["spend"], 1.0)
+    L = _L()
+    out = np.empty((nd, n), np.float64)
+    check(L.clv_pointwise_loglik(int(device), dptr(a), nd, n, w, _i32p(x), dptr(t_x), dptr(T_cal), dptr(log_s),
+                                 par["omega2"], dptr(out)))
+    return out
+
+
+def information_criteria(draws: Dict[str, Any], cbs: pd.DataFrame, *, spend: bool = False, omega2=None,
+                         reff: float = 1.0, device: int = -1) -> Dict[str, Any]:
+    """WAIC and Pareto-smoothed importance-sampling leave-one-out (Vehtari, Gelman & Gabry 2017) of a
+    fit, per customer and in total, on the GPU (``csrc/ic.hip``, ``clv_information_criteria``): what
+    ``az.waic`` and ``az.loo`` give on :func:`pointwise_log_likelihood`, without that matrix leaving
+    the device.  ``reff`` is the relative efficiency of the draws (ESS / S; the rank diagnostics
+    give ESS), which sets the tail length ``M = ceil(min(S / 5, 3 sqrt(S / reff)))``.
+
+    Returns ``{"pointwise": DataFrame, one row per customer, columns _lib.IC_STATS (lppd, p_waic,
+    elpd_waic, elpd_loo, p_loo, pareto_k — +inf where the tail had fewer than 5 distinct values or
+    the fit failed and the raw weights were kept —, tail_len), "waic", "loo": one-row DataFrames
+    elpd, se, p, n_samples, n_data_points, n_bad_k, warning}`` (:func:`ic_frames`); compare fits of
+    the same customers with :func:`compare_models`.  Arguments are checked before any device is
+    touched."""
+    a = _stacked_level1(draws.get("level_1"))
+    nd, n, w = a.shape
+    x, t_x, T_cal, log_s = _ic_data(cbs, n, spend)
+    par = ic_params(spend, omega2, reff, log_s)
+    _ic_shape(nd, n, w, par["spend"], par["reff"])
+    L = _L()
+    out = np.empty((n, len(_lib.IC_STATS)), np.float64)
+    check(L.clv_information_criteria(int(device), dptr(a), nd, n, w, _i32p(x), dptr(t_x), dptr(T_cal), dptr(log_s),
+                                     par["omega2"], par["reff"], dptr(out)))
+    return ic_frames(out, nd)
+
+
+def psis_loo(log_lik, *, reff: float = 1.0, device: int = -1) -> Dict[str, Any]:
+    """:func:`information_criteria` of any pointwise log-likelihood matrix (n_draws, n_observations)
+    (``clv_psis_loo``)."""
+    ll = np.ascontiguousarray(np.asarray(log_lik, dtype=np.float64))
+    if ll.ndim != 2:
+        raise ValueError("log_lik must be (n_draws, n_observations)")
+    par = ic_params(False, None, reff)
+    _ic_shape(ll.shape[0], ll.shape[1], 4, False, par["reff"])
+    L = _L()
+    out = np.empty((ll.shape[1], len(_lib.IC_STATS)), np.float64)
+    check(L.clv_psis_loo(int(device), dptr(ll), ll.shape[0], ll.shape[1], par["reff"], dptr(out)))
+    return ic_frames(out, ll.shape[0])
+
+
+def compare_models(models: Dict[str, Dict[str, Any]], criterion: str = "loo") -> pd.DataFrame:
+    """Rank fits of the same customers by ``criterion`` ("loo" or "waic"), as ``az.compare`` does:
+    one row per model, best first, with rank, elpd, p, ``elpd_diff`` = the best model's elpd minus
+    this one's, ``dse = sqrt(N var(elpd_i - elpd_best,i, ddof 0))`` — the standard error of that
+    difference from the paired per-customer values — se, n_bad_k and warning.  Host numpy on the
+    frames of :func:`information_criteria`; ValueError on unequal customer counts."""
+    if criterion not in ("loo", "waic"):
+        raise ValueError(f"criterion must be 'loo' or 'waic' (got {criterion!r})")
+    if not models:
+        raise ValueError("no model to compare")
+    col = "elpd_" + criterion
+    point = {k: m["pointwise"][col].to_numpy() for k, m in models.items()}
+    sizes = {len(v) for v in point.values()}
+    if len(sizes) != 1:
+        raise ValueError(f"the models were fitted to different numbers of customers: {sorted(sizes)}")
+    n = sizes.pop()
+    order = sorted(models, key=lambda k: -float(models[k][criterion]["elpd"].iloc[0]))
+    best = order[0]
+    rows = []
+    for r, k in enumerate(order):
+        tot = models[k][criterion].iloc[0]
+        diff = point[best] - point[k]
+        rows.append(dict(rank=r, elpd=float(tot["elpd"]), p=float(tot["p"]),
+                         elpd_diff=float(models[best][criterion]["elpd"].iloc[0]) - float(tot["elpd"]),
+                         dse=float(np.sqrt(n * np.var(diff))), se=float(tot["se"]), n_bad_k=int(tot["n_bad_k"]),
+                         warning=bool(tot["warning"])))
+    return pd.DataFrame(rows, index=pd.Index(order, name="model"))
 
 
 # ---- convergence diagnostics (csrc/diag.hip) -------------------------------------------------

@@ -27,6 +27,10 @@ line and return layout (bivariate/mcmc.py:437-504); the sweeps run on the GPU
   ``periods_per_year``, ``horizon``, ``monetary``, ``omega2``), adds ``out["lifetime_value"]``: the
   posterior customer lifetime value per customer and the customer equity per draw, computed on the
   GPU from the draws still in HBM (``csrc/ltv.hip``; ``draw_sink="full"`` only).  None changes nothing.
+* ``information_criteria``: True, or a dict of ``analysis.information_criteria``'s keywords (``spend``,
+  ``omega2``, ``reff``), adds ``out["information_criteria"]``: WAIC and PSIS-LOO per customer and in
+  total, from the draws still in HBM (``csrc/ic.hip``; ``draw_sink="full"`` only); compare two fits
+  with ``analysis.compare_models``.  None changes nothing.
 """
 from __future__ import annotations
 
@@ -43,7 +47,8 @@ def mcmc_draw_parameters(cal_cbs, covariates: Optional[Sequence[str]] = None, mc
                          trace: int = 100, n_mh_steps: int = 20, *, draw_sink: str = "full",
                          rng: str = "philox", device: int = -1, replay_tape=None,
                          replay_sweeps: Optional[int] = None, devices: Optional[Sequence[int]] = None,
-                         shard: str = "auto", exchange: str = "auto", diagnostics=False, lifetime_value=None):
+                         shard: str = "auto", exchange: str = "auto", diagnostics=False, lifetime_value=None,
+                         information_criteria=None):
     """Run the Abe (2009) Gibbs/MH sampler on calibration CBS (bivariate/mcmc.py:437).
 
     Returns dict(level_1=[(n_draws, N, 4) per chain: lambda, mu, tau, z],
@@ -61,4 +66,5 @@ def mcmc_draw_parameters(cal_cbs, covariates: Optional[Sequence[str]] = None, mc
     return fit(p, mcmc=mcmc, burnin=burnin, thin=thin, chains=chains, seed=seed, trace=trace,
                n_mh_steps=n_mh_steps, draw_sink=draw_sink, rng=rng, device=device,
                replay_tape=replay_tape, replay_sweeps=replay_sweeps, devices=devices, shard=shard,
-               exchange=exchange, diagnostics=diagnostics, lifetime_value=lifetime_value)
+               exchange=exchange, diagnostics=diagnostics, lifetime_value=lifetime_value,
+               information_criteria=information_criteria)

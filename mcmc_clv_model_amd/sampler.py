@@ -458,6 +458,18 @@ class HipSampler:
                                                  par["periods_per_year"], dptr(cust), dptr(per_draw)))
         return A.ltv_frames(cust, per_draw, par)
 
+    def information_criteria(self, *, spend: bool = False, omega2=None, reff: float = 1.0) -> dict:
+        """clv_information_criteria_sampler: analysis.information_criteria (WAIC and PSIS-LOO per
+        customer and in total) of the draws this sampler holds in HBM, with the data it was created
+        with, without the host round trip; the same bits as the host-array route."""
+        from . import analysis as A
+        par = A.ic_params(spend, omega2, reff, self.p.log_s)
+        A._ic_shape(self.chains * self.n_draws, self.n, self.D + 2, par["spend"], par["reff"])
+        out = np.empty((self.n, len(_lib.IC_STATS)), np.float64)
+        check(self._L.clv_information_criteria_sampler(self.h, 1 if par["spend"] else 0, par["omega2"], par["reff"],
+                                                       dptr(out)))
+        return A.ic_frames(out, self.chains * self.n_draws)
+
     def chain_total_loglik(self) -> float:
         out = ctypes.c_double()
         check(self._L.clv_chain_total_loglik_sampler(self.h, ctypes.byref(out)))
@@ -571,7 +583,7 @@ def _assemble(D: int, chains: int, l1, l2, ll, sums, k: int, n_draws: int, draw_
 def fit(p: Problem, *, mcmc: int, burnin: int, thin: int, chains: int, seed, trace: int, n_mh_steps: int,
         draw_sink: str = "full", rng: str = "philox", device: int = -1, replay_tape=None,
         replay_sweeps: Optional[int] = None, devices: Optional[Sequence[int]] = None, shard: str = "auto",
-        exchange: str = "auto", diagnostics=False, lifetime_value=None) -> dict:
+        exchange: str = "auto", diagnostics=False, lifetime_value=None, information_criteria=None) -> dict:
     """Run all chains of one problem in one batched launch sequence and return the reference's
     output layout (bi:499-504).  ``devices`` (two or more): the run is spread over those devices
     in this process (:func:`fit_multi`).  ``diagnostics``: also out["diagnostics"] = {"level_1",
@@ -581,7 +593,10 @@ def fit(p: Problem, *, mcmc: int, burnin: int, thin: int, chains: int, seed, tra
     (analysis.level1_rank_diagnostics / level2_rank_diagnostics / level2_summary).
     ``lifetime_value``: True or a dict of analysis.lifetime_value's keywords adds
     out["lifetime_value"] (customer lifetime value per customer, customer equity per draw; full
-    sink only), routed as the diagnostics are."""
+    sink only), routed as the diagnostics are.
+    ``information_criteria``: True or a dict of analysis.information_criteria's keywords (spend,
+    omega2, reff) adds out["information_criteria"] (WAIC and PSIS-LOO; full sink only), routed the
+    same way."""
     if chains < 1:
         raise ValueError("chains must be >= 1")
     if thin < 1:
@@ -591,6 +606,7 @@ def fit(p: Problem, *, mcmc: int, burnin: int, thin: int, chains: int, seed, tra
     if diagnostics and draw_sink != "full":
         raise ValueError("diagnostics=True needs draw_sink='full' (analysis.summary_rhat serves a summary run)")
     ltv_kw = lifetime_value_kwargs(lifetime_value, draw_sink)
+    ic_kw = information_criteria_kwargs(information_criteria, draw_sink, p.D)
     if devices is not None:
         devices = [int(d) for d in devices]
         if not devices:
@@ -600,7 +616,8 @@ def fit(p: Problem, *, mcmc: int, burnin: int, thin: int, chains: int, seed, tra
                 raise ValueError("devices= runs need rng='philox' (the replay tape is a single-device test mode)")
             out = fit_multi(p, mcmc=mcmc, burnin=burnin, thin=thin, chains=chains, seed=seed, trace=trace,
                             n_mh_steps=n_mh_steps, draw_sink=draw_sink, devices=devices, shard=shard,
-                            exchange=exchange, lifetime_value=lifetime_value)
+                            exchange=exchange, lifetime_value=lifetime_value,
+                            information_criteria=information_criteria)
             if diagnostics:
                 from . import analysis as A
                 out["diagnostics"] = dict(level_1=A.level1_diagnostics(out, device=devices[0]),
@@ -632,6 +649,8 @@ def fit(p: Problem, *, mcmc: int, burnin: int, thin: int, chains: int, seed, tra
             out["diagnostics"] = s.diagnostics(rank=diagnostics == "rank")
         if ltv_kw is not None:
             out["lifetime_value"] = s.lifetime_value(**ltv_kw)
+        if ic_kw is not None:
+            out["information_criteria"] = s.information_criteria(**ic_kw)
         return out
     finally:
         s.close()
@@ -660,6 +679,31 @@ def lifetime_value_kwargs(lifetime_value, draw_sink: str):
     return kw
 
 
+def information_criteria_kwargs(information_criteria, draw_sink: str, D: int):
+    """The ``information_criteria=`` keyword of the fit functions as analysis.information_criteria's
+    keywords (None: not asked for), validated before the run starts."""
+    if information_criteria is None or information_criteria is False:
+        return None
+    if information_criteria is True:
+        kw = {}
+    elif isinstance(information_criteria, dict):
+        kw = dict(information_criteria)
+    else:
+        raise ValueError("information_criteria must be None, True or a dict of keywords "
+                         f"(got {information_criteria!r})")
+    if draw_sink != "full":
+        raise ValueError("information_criteria needs draw_sink='full' (it is computed from the level-1 draws)")
+    from . import analysis as A
+    allowed = ("spend", "omega2", "reff")
+    bad = sorted(set(kw) - set(allowed))
+    if bad:
+        raise ValueError(f"information_criteria takes the keywords {allowed} (got {bad})")
+    if kw.get("spend") and D != 3:
+        raise ValueError("spend=True needs the trivariate model (D = 3)")
+    A.ic_params(kw.get("spend", False), kw.get("omega2", 1.0 if kw.get("spend") else None), kw.get("reff", 1.0))
+    return kw
+
+
 def multi_plan(chains: int, n_dev: int, draw_sink: str, shard: str = "auto"):
     """How :func:`fit_multi` spreads a run over ``n_dev`` devices: ("chains", [(first chain,
     chains), ...] one group per device used) or ("customers", None).  "auto" takes chain groups
@@ -681,7 +725,7 @@ def multi_plan(chains: int, n_dev: int, draw_sink: str, shard: str = "auto"):
 
 def fit_multi(p: Problem, *, mcmc: int, burnin: int, thin: int, chains: int, seed, trace: int, n_mh_steps: int,
               draw_sink: str, devices: Sequence[int], shard: str = "auto", exchange: str = "auto",
-              lifetime_value=None) -> dict:
+              lifetime_value=None, information_criteria=None) -> dict:
     """One run over several devices of this process (SURVEY §8b ``devices=``), same output as the
     single-device run, bit for bit:
 
@@ -695,14 +739,24 @@ def fit_multi(p: Problem, *, mcmc: int, burnin: int, thin: int, chains: int, see
     * ``"auto"``: chains when they divide evenly over the devices (and the sink is not
       "summary+pct", whose percentiles pool all chains), else customers.
 
-    ``lifetime_value``: as :func:`fit`, computed from the returned arrays on ``devices[0]``."""
+    ``lifetime_value``, ``information_criteria``: as :func:`fit`, computed from the returned arrays
+    on ``devices[0]``."""
     import threading
     ltv_kw = lifetime_value_kwargs(lifetime_value, draw_sink)
+    ic_kw = information_criteria_kwargs(information_criteria, draw_sink, p.D)
 
     def finish(out):
         if ltv_kw is not None:
             from . import analysis as A
             out["lifetime_value"] = A.lifetime_value(out, device=int(devices[0]), **ltv_kw)
+        if ic_kw is not None:
+            from . import analysis as A
+            import pandas as pd
+            cbs = dict(x=p.x, t_x=p.t_x, T_cal=p.T_cal)
+            if p.log_s is not None:
+                cbs["log_s"] = p.log_s
+            out["information_criteria"] = A.information_criteria(out, pd.DataFrame(cbs), device=int(devices[0]),
+                                                                 **ic_kw)
         return out
 
     n_dev = len(devices)
