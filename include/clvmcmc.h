@@ -516,6 +516,67 @@ int clv_debug_information_criteria(int32_t device, const double* level1, int64_t
                                    const int32_t* x, const double* t_x, const double* T_cal, const double* log_s,
                                    double omega2, double reff, int64_t batch_keys, int32_t grid, double* out);
 
+/* ---- Scoring customers outside the fit (csrc/score.hip, kernels.hip score_kernel) ----
+ * Given (beta, Sigma) customers are conditionally independent, so a customer the fit never saw has
+ *   p(theta_i | y_i, fit) = integral p(theta_i | y_i, beta, Sigma) p(beta, Sigma | fit) d(beta, Sigma):
+ * the level-1 half of the sweep — draw_z, draw_tau (bi:193-227), the MH steps on (log lambda, log mu)
+ * (bi:268-339) and draw_eta (tri:306-333) — run against the fit's stored level-2 records instead of a
+ * live level-2 draw.  level2 is [n_chains][n_draws][D K + D (D + 1) / 2], a row being beta.T.ravel()
+ * then Sigma's upper triangle (bi:411-412, tri:549-554: what clv_read_draws returns).  For chain c
+ * and new customer i one shadow chain runs from init_*[c][i]: warmup inner sweeps against record 0
+ * (nothing recorded), then inner_sweeps against every record d in turn, the state after the last
+ * of them being draw d.  Inner sweep number t (1-based from sweep_first, warm-up counted) is the
+ * production Philox-mode level-1 sweep with n_mh_steps MH steps, key chain_key(seed + chain_first +
+ * c) and counter (customer_offset + i, t, slot, customer stream): the result is a function of
+ * (seed, chain, global customer index, t) alone, whatever the batch or the grid.  A call with
+ * init_* = an earlier call's state_*_out, warmup = 0 and sweep_first = that call's last t + 1
+ * continues it exactly.
+ * (beta, Sigma) is held fixed during a record's inner sweeps (a two-stage, "cut" analysis).  With
+ * all of a chain's records equal the scheme is exactly invariant for any inner_sweeps; when they
+ * vary, theta enters record d distributed for record d - 1, a bias that fades with inner_sweeps and
+ * with the narrowness of the level-2 posterior (measured: DESIGN.md §4h).
+ * Host pointers.  x [n] int32; t_x, T_cal [n]; cov [(K - 1)][n] (NULL for K = 1); log_s [n] and
+ * omega2 > 0 for D = 3 (log_s NULL for D = 2); init_lam, init_mu, state_lam_out, state_mu_out
+ * [n_chains][n] (the final state is always written).  sink = CLV_SINK_FULL: level1_out
+ * [n_chains][n_draws][n][D + 2] = (lambda, mu, tau, z, [eta]), the layout of clv_read_draws;
+ * CLV_SINK_SUMMARY: sums_out [n_chains][CLV_N_SUM_STATS][n], the CLV_SUM_* sums over the records in
+ * record order from zero (the log sums are logs of the recorded natural-scale draws; eta sums zero
+ * for D = 2) — nothing per record leaves the registers, so millions of customers x thousands of
+ * records fit.  The other output may be NULL.
+ * CLV_EINVAL before any device call: a null pointer, D not 2 or 3, K not 1 .. 9, n_chains or n_draws
+ * < 1, n <= 0, cov / log_s that do not match (D, K), omega2 not in (0, inf) for D = 3, n_mh_steps or
+ * warmup < 0, inner_sweeps < 1, a sink other than the two, the sink's output NULL, init not finite
+ * and positive, x < 0, t_x outside [0, T_cal], non-finite data or records, a record with a
+ * non-positive variance, customer_offset + n or the last inner-sweep number beyond 32 bits.
+ * CLV_ENOMEM (before anything is allocated) when the sink does not fit in device memory. */
+int clv_score_customers(int32_t device, int32_t D, int32_t K, int32_t n_chains, int64_t n_draws,
+                        const double* level2, int64_t n, const int32_t* x, const double* t_x,
+                        const double* T_cal, const double* cov, const double* log_s, double omega2,
+                        int32_t n_mh_steps, int32_t warmup, int32_t inner_sweeps, uint64_t seed,
+                        int32_t chain_first, int64_t customer_offset, int64_t sweep_first,
+                        const double* init_lam, const double* init_mu, int32_t sink, double* level1_out,
+                        double* sums_out, double* state_lam_out, double* state_mu_out);
+/* The same from the level-2 records a sampler holds in HBM after its run (any draw sink; CLV_ESTATE
+ * before every record is stored, and for a replay-mode sampler): D, K, n_chains, n_draws, omega2 and
+ * the chain keys' chain_first are the sampler's. */
+int clv_score_customers_sampler(clv_sampler* s, int64_t n, const int32_t* x, const double* t_x,
+                                const double* T_cal, const double* cov, const double* log_s,
+                                int32_t n_mh_steps, int32_t warmup, int32_t inner_sweeps, uint64_t seed,
+                                int64_t customer_offset, int64_t sweep_first, const double* init_lam,
+                                const double* init_mu, int32_t sink, double* level1_out, double* sums_out,
+                                double* state_lam_out, double* state_mu_out);
+/* out[0] customers per workgroup (256), out[1] CLV_N_SUM_STATS; of the instance the calling thread's
+ * last clv_score_customers* call launched (-1 before one): out[2] D, out[3] K, out[4] sink, out[5]
+ * VGPRs and out[6] scratch bytes per lane (hipFuncGetAttributes), out[7] the kernel's device time
+ * in ns (events around the launch). */
+int clv_score_info(int64_t* out);
+/* The prepare kernel alone (tests): out [n_rec][64], the hyper block the score kernel reads for each
+ * record of level2 [n_rec][D K + D (D + 1) / 2] — beta[k][d] at k D + d, Sigma 3 x 3 row-major at 27,
+ * inv(Sigma)[0:2, 0:2] = (P00, P01, P11) at 36 .. 38, the proposal scales Sigma00, Sigma11 at 39, 40,
+ * and for D = 3 Sigma22, post_var, sqrt(post_var), omega2, 1 / omega2, 1 / Sigma22 at 41 .. 46. */
+int clv_debug_score_hyper(int32_t device, int32_t D, int32_t K, int64_t n_rec, const double* level2,
+                          double omega2, double* out);
+
 /* ---- Convergence diagnostics on device (csrc/diag.hip) ----
  * The reference checks convergence with ArviZ on its level-2 draws (bivariate/analysis_abe.py:
  * 651-706: az.summary, az.plot_autocorr).  Here a series is m chains x n draws (n >= 8) of one

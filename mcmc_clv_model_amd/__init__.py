@@ -20,6 +20,12 @@ Which model the data prefer: the pointwise log-likelihood, WAIC and PSIS-LOO wit
 diagnostic per customer, and a paired comparison with a standard error (pointwise_log_likelihood,
 information_criteria, psis_loo, compare_models) — az.waic / az.loo / az.compare, which the reference
 prepares for and never calls.
+Customers who were not in the fit — the usual case: fit on a sample, score the whole base — get their
+own level-1 draws from the fit's level-2 draws (score_customers: the level-1 half of the sweep run
+against the stored (beta, Sigma) records, in the drop-ins' level_1 layout, so every function above
+works on them unchanged; sink="summary" keeps only per-customer sums, for millions of customers).
+(beta, Sigma) is held fixed while a record's inner sweeps run: when the records differ, a customer
+enters each record distributed for the one before, a bias that shrinks as inner_sweeps grows.
 
 The per-sweep work runs in hand-written HIP kernels for gfx950 (csrc/), bound through the C
 ABI in include/clvmcmc.h.  There is no CPU fallback.
@@ -29,8 +35,8 @@ from .analysis import (chain_total_loglik, compare_models, compute_table4, custo
                        information_criteria, level1_diagnostics,
                        level1_rank_diagnostics, level2_autocorr, level2_diagnostics, level2_rank_diagnostics,
                        level2_summary, lifetime_value, lifetime_value_elasticities, pointwise_log_likelihood,
-                       post_mean_lambdas, post_mean_mus, posterior_weekly_tracking, psis_loo, summarize_level2,
-                       summary_rhat)
+                       post_mean_lambdas, post_mean_mus, posterior_weekly_tracking, psis_loo, score_customers,
+                       summarize_level2, summary_rhat)
 from .bivariate import mcmc_draw_parameters
 from .mle import ParetoNBDFitter, mape_aggregate, pnbd_weekly_tracking
 from .trivariate import mcmc_draw_parameters_rfm_m
@@ -42,5 +48,5 @@ __all__ = ["mcmc_draw_parameters", "mcmc_draw_parameters_rfm_m", "draw_future_tr
            "level1_rank_diagnostics", "level2_rank_diagnostics", "level2_summary", "ParetoNBDFitter",
            "pnbd_weekly_tracking", "mape_aggregate", "lifetime_value", "customer_equity",
            "lifetime_value_elasticities", "pointwise_log_likelihood", "information_criteria", "psis_loo",
-           "compare_models"]
+           "compare_models", "score_customers"]
 __version__ = "0.1.0"

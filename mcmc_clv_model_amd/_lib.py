@@ -159,6 +159,13 @@ def lib() -> ctypes.CDLL:
         "clv_ic_info": (c_int32, [POINTER(c_int64)]),
         "clv_debug_information_criteria": (c_int32, [c_int32, dp, c_int64, c_int64, c_int32, POINTER(c_int32), dp,
                                                      dp, dp, c_double, c_double, c_int64, c_int32, dp]),
+        "clv_score_customers": (c_int32, [c_int32, c_int32, c_int32, c_int32, c_int64, dp, c_int64, POINTER(c_int32), dp,
+                                          dp, dp, dp, c_double, c_int32, c_int32, c_int32, c_uint64, c_int32, c_int64,
+                                          c_int64, dp, dp, c_int32, dp, dp, dp, dp]),
+        "clv_score_customers_sampler": (c_int32, [sp, c_int64, POINTER(c_int32), dp, dp, dp, dp, c_int32, c_int32,
+                                                  c_int32, c_uint64, c_int64, c_int64, dp, dp, c_int32, dp, dp, dp, dp]),
+        "clv_score_info": (c_int32, [POINTER(c_int64)]),
+        "clv_debug_score_hyper": (c_int32, [c_int32, c_int32, c_int32, c_int64, dp, c_double, dp]),
         "clv_diagnostics": (c_int32, [c_int32, dp, c_int32, c_int64, c_int64, c_int32, c_uint32, dp]),
         "clv_diagnostics_sampler": (c_int32, [sp, c_uint32, dp, dp]),
         "clv_autocorr": (c_int32, [c_int32, dp, c_int32, c_int64, c_int64, c_int32, dp]),
@@ -238,6 +245,16 @@ def ic_info() -> dict:
     check(lib().clv_ic_info(out))
     return dict(block=int(out[0]), tile_draws=int(out[1]), batch_keys=int(out[2]), min_draws=int(out[3]),
                 max_draws=int(out[4]), max_tail=int(out[5]), min_fit=int(out[6]))
+
+
+def score_info() -> dict:
+    """clv_score_info: customers per workgroup and the sum-stat count of csrc/score.hip, and of the
+    instance this thread's last score_customers call launched (-1 before one): D, K, sink, VGPRs and
+    scratch bytes per lane, the kernel's device time in ns."""
+    out = (c_int64 * 8)()
+    check(lib().clv_score_info(out))
+    keys = ("block", "n_sum_stats", "D", "K", "sink", "vgprs", "scratch_bytes", "kernel_ns")
+    return {k: int(v) for k, v in zip(keys, out)}
 
 
 def exported_symbols():

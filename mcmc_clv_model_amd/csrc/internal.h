@@ -51,6 +51,16 @@ void stream_clear_failed(DrawStreamState* st);  // after a full copy has repaire
 // [chain * draw][n][width], *n_draws = chains x stored draws; CLV_ESTATE without them.
 int sampler_l1(clv_sampler* s, const double** l1, int64_t* n_draws, int32_t* width);
 
+// Scoring customers outside the fit (kernels.hip; host side in score.hip).  launch_score_prepare:
+// level2 [n_rec][D K + D (D + 1) / 2] -> hyper [n_rec][HS] (cleared by the caller).  launch_score:
+// grid (ceil(a.g.n / BLOCK), a.g.n_chains), optional events around the kernel.  score_resources:
+// VGPRs and scratch bytes per lane of the (D, K, sink) instance.
+hipError_t launch_score_prepare(int D, int K, const double* level2, int64_t n_rec, double omega2, double* hyper,
+                                hipStream_t st);
+hipError_t launch_score(const SweepArgs& a, const ScoreArgs& e, bool summary, hipStream_t st,
+                        hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
+hipError_t score_resources(int D, int K, bool summary, int* vgprs, size_t* scratch_bytes);
+
 template <class T>
 hipError_t dalloc(T** p, size_t count) {
   *p = nullptr;

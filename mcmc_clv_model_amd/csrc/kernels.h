@@ -175,6 +175,21 @@ struct SweepArgs {
   unsigned long long* stamps; // diagnostic build only (CLV_STAMPS): [1024][8] s_memrealtime stamps
 };
 
+// Scoring customers outside the fit (kernels.hip score_kernel).  The kernel takes a SweepArgs too and
+// reads from it: g.D, g.K, g.S, g.n_chains, g.n (new customers), g.shard_begin (customer_offset),
+// r.seed, r.chain_first, x, tx, T, cov, log_s, and lam / mu as the start state [chain][n].
+struct ScoreArgs {
+  const double* hyper;       // [chain][n_draws][HS] hyper blocks (score_prepare_kernel)
+  int64_t n_draws;           // records per chain
+  int64_t s_first;           // inner-sweep number of the call's first sweep (>= 1)
+  int warmup;                // inner sweeps against record 0 before anything is recorded
+  int inner;                 // inner sweeps per record (>= 1); the last one is recorded
+  double* level1;            // full sink: [chain][n_draws][n][D+2]
+  double* sums;              // summary sink: [chain][CLV_N_SUM_STATS][n]
+  double* lam_out;           // [chain][n] final state
+  double* mu_out;
+};
+
 struct GroupArgs {
   Geometry g;
   const double* blockpart;

@@ -14,6 +14,7 @@
 #include <hip/hip_ext.h>
 
 #include "fastmath.h"
+#include "internal.h"
 #include "kernels.h"
 #include "philox.h"
 
@@ -3348,6 +3349,128 @@ __global__ void set_hyper_kernel(int n_chains, double* hyper, const double* bs, 
 }
 
 // ---------------------------------------------------------------------------------------------
+// Scoring customers outside the fit (score.hip): the level-1 half of the sweep run
+// against stored level-2 records.  No reduction, no hand-off between workgroups.
+// ---------------------------------------------------------------------------------------------
+// One lane per (chain, record): the stored row (beta.T.ravel(), Sigma's upper triangle; bi:411-412,
+// tri:549-554) -> the HS-double hyper block the fit's own MH would form from it (finalize_hyper with
+// set_hyper_kernel's NR).  The block's unwritten entries are zero (the caller clears the buffer).
+template <int D, int K, bool NR>
+__global__ __launch_bounds__(BLOCK) void score_prepare_kernel(const double* level2, int64_t n_rec, double omega2,
+                                                              double* hyper) {
+  const int64_t r = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (r >= n_rec) return;
+  const double* in = level2 + r * (D * K + D * (D + 1) / 2);
+  double beta[K * D], Sig[D][D];
+#pragma unroll
+  for (int k = 0; k < K; ++k)
+#pragma unroll
+    for (int d = 0; d < D; ++d) beta[k * D + d] = in[d * K + k];
+  int q = D * K;
+#pragma unroll
+  for (int p = 0; p < D; ++p)
+#pragma unroll
+    for (int t = p; t < D; ++t) Sig[p][t] = Sig[t][p] = in[q++];
+  finalize_hyper<D, K, false, NR>(beta, Sig, omega2, hyper + r * HS);
+}
+
+// One lane per (chain, customer).  The CBS row, the covariates and the whole state stay in
+// registers (K >= SWEEP_COV_LDS_MIN_K: the covariates in LDS, as the launch-per-sweep kernel keeps
+// them) over warm-up and every record; record d's hyper block is read from LDS (wave-uniform
+// addresses) while wavefront 0 holds record d + 1's in flight.  Inner sweep t is the production
+// Philox-mode level-1 sweep with the counter (customer, t, slot, STREAM_CUSTOMER): bi:193-227
+// (cust_ztau), bi:268-339 (cust_coeffs, mh_run) and, on the sweep that is recorded, tri:306-333
+// (cust_finish's eta draw — eta never feeds back into the state, and its variate is a function of
+// the counter alone, so the sweeps that are not recorded skip it and change nothing).
+// SUMMARY: the CLV_N_SUM_STATS sums stay in registers, accumulated in record order from zero; the
+// log sums are log_fast of the recorded natural-scale draw, so every sum is a function of what the
+// full sink would have stored.  Inactive lanes of the last block run a clamped row and store nothing.
+template <int D, int K, bool SUMMARY>
+__global__ __launch_bounds__(BLOCK) void score_kernel(SweepArgs a, ScoreArgs e) {
+  constexpr bool CL = CovLds<D, K>::value;
+  __shared__ __attribute__((aligned(16))) double exp_tab[D == 3 ? FAST_TAB_N3 : FAST_TAB_N];
+  __shared__ double cov_s[CL ? (K - 1) * BLOCK : 1];
+  __shared__ double Hs[2][HS];
+  const Geometry& g = a.g;
+  const int c = blockIdx.y, tid = threadIdx.x;
+  Cust<D, K, CL> cu;
+  cu.cl = cov_s + tid;
+  {
+    const int64_t i = (int64_t)blockIdx.x * BLOCK + tid;
+    cu.active = i < g.n;
+    cu.i = cu.active ? i : g.n - 1;
+  }
+  cust_load(cu, a, c);
+  fast_tab_fill(exp_tab, tid, BLOCK, D == 3);
+  const double* Hc = e.hyper + (int64_t)c * e.n_draws * HS;
+  if (tid < HS) Hs[0][tid] = Hc[tid];
+  __syncthreads();
+  uint32_t k0, k1;
+  chain_key(a.r.seed, (int64_t)a.r.chain_first + c, &k0, &k1);
+  double sum[SUMMARY ? CLV_N_SUM_STATS : 1];
+#pragma unroll
+  for (int k = 0; k < (SUMMARY ? CLV_N_SUM_STATS : 1); ++k) sum[k] = 0.0;
+  int64_t t = e.s_first;  // the inner-sweep number (Philox counter word), warm-up included
+  for (int64_t d = e.warmup > 0 ? -1 : 0; d < e.n_draws; ++d) {  // d = -1: warm-up against record 0
+    const int64_t rec = d < 0 ? 0 : d;
+    const double* H = Hs[rec & 1];
+    const bool fetch = d >= 0 && d + 1 < e.n_draws;  // record d + 1 travels while record d's sweeps run
+    double hv = 0.0;
+    if (fetch && tid < HS) hv = Hc[(d + 1) * HS + tid];
+    const int nsw = d < 0 ? e.warmup : e.inner;
+    const double s00 = H[H_S00], s11 = H[H_S11];
+    StatGen<D, K> st{};
+    CustOut<D> out{};
+    for (int k = 0; k < nsw; ++k, ++t) {
+      cust_ztau<D, K, false>(cu, a, t, k0, k1, nullptr, exp_tab);
+      cust_coeffs<D, K, false>(cu, H, exp_tab);
+      mh_run(cu, SlotPhilox(k0, k1, cu.gi, (uint32_t)t), s00, s11, g.S, exp_tab);
+      if (d >= 0 && k == nsw - 1) out = cust_finish<D, K, false>(cu, a, t, true, H, k0, k1, nullptr, exp_tab, st);
+      else exp_fast2(cu.ll, cu.lm, exp_tab, cu.lam, cu.mu);  // bi:337-338
+    }
+    if (d >= 0 && cu.active) {
+      if constexpr (SUMMARY) {
+        auto acc = [&](int k, double v) { sum[k] = sum[k] + v; };
+        acc(CLV_SUM_LAMBDA, out.lam);
+        acc(CLV_SUM_MU, out.mu);
+        acc(CLV_SUM_Z, cu.z ? 1.0 : 0.0);
+        acc(CLV_SUM_LOG_LAMBDA, log_fast(out.lam, exp_tab));
+        acc(CLV_SUM_LOG_MU, log_fast(out.mu, exp_tab));
+        acc(CLV_SUM_LAMBDA2, out.lam * out.lam);
+        acc(CLV_SUM_MU2, out.mu * out.mu);
+        if constexpr (D == 3) {
+          acc(CLV_SUM_ETA, out.eta);
+          acc(CLV_SUM_LOG_ETA, log_fast(out.eta, exp_tab));
+        }
+        acc(CLV_SUM_MU_CAPPED, fmin(out.mu, CLV_SUMMARY_MU_CAP));
+        acc(CLV_SUM_TAU, cu.tau);
+      } else {  // one (D + 2)-double row per lane, consecutive lanes consecutive rows (as cust_store)
+        double* w = e.level1 + ((((int64_t)c * e.n_draws + d) * g.n) + cu.i) * (D + 2);
+        w[0] = out.lam;
+        w[1] = out.mu;
+        w[2] = cu.tau;
+        w[3] = cu.z ? 1.0 : 0.0;
+        if constexpr (D == 3) w[4] = out.eta;
+      }
+    }
+    if (fetch) {  // wave-uniform.  Buffer (d + 1) & 1 was last read in record d - 1, before the previous barrier
+      if (tid < HS) Hs[(d + 1) & 1][tid] = hv;
+      __syncthreads();
+    }
+  }
+  if (cu.active) {
+    const int64_t ci = (int64_t)c * g.n + cu.i;
+    e.lam_out[ci] = cu.lam;
+    e.mu_out[ci] = cu.mu;
+    if constexpr (SUMMARY) {
+      double* sm = e.sums + (int64_t)c * CLV_N_SUM_STATS * g.n + cu.i;
+#pragma unroll
+      for (int k = 0; k < CLV_N_SUM_STATS; ++k) sm[(int64_t)k * g.n] = sum[k];
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // Debug / test kernels
 // ---------------------------------------------------------------------------------------------
 __global__ void debug_philox_kernel(uint32_t k0, uint32_t k1, const uint32_t* ctr, int64_t n, uint32_t* out) {
@@ -3754,6 +3877,57 @@ hipError_t launch_debug_mh(const int32_t* x, const uint8_t* z, const double* T, 
   hipLaunchKernelGGL(debug_mh_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, x, z, T, tau, m, prec,
                      cur_pt, t3, scale, log_u, n, out);
   return hipGetLastError();
+}
+
+hipError_t launch_score_prepare(int D, int K, const double* level2, int64_t n_rec, double omega2, double* hyper,
+                                hipStream_t st) {
+  const dim3 grid((unsigned)((n_rec + BLOCK - 1) / BLOCK));
+#define CLV_CASE(DD, KK, RR)                                                                                        \
+  if (D == DD && K == KK) {                                                                                         \
+    hipLaunchKernelGGL((score_prepare_kernel<DD, KK, CLV_L2_NR != 0>), grid, dim3(BLOCK), 0, st, level2, n_rec, omega2, \
+                       hyper);                                                                                      \
+    return hipGetLastError();                                                                                       \
+  }
+  CLV_FOR_K(CLV_CASE, 2, false)
+  CLV_FOR_K(CLV_CASE, 3, false)
+#undef CLV_CASE
+  return hipErrorInvalidValue;
+}
+
+// Grid (ceil(n / BLOCK), chains); e0 / e1 (optional): events around the kernel.
+hipError_t launch_score(const SweepArgs& a, const ScoreArgs& e, bool summary, hipStream_t st, hipEvent_t e0,
+                        hipEvent_t e1) {
+  const dim3 grid((unsigned)((a.g.n + BLOCK - 1) / BLOCK), a.g.n_chains);
+#define CLV_CASE(DD, KK, SS)                                                                                  \
+  if (a.g.D == DD && a.g.K == KK && summary == SS) {                                                          \
+    if (e0) hipExtLaunchKernelGGL((score_kernel<DD, KK, SS>), grid, dim3(BLOCK), 0, st, e0, e1, 0, a, e);      \
+    else hipLaunchKernelGGL((score_kernel<DD, KK, SS>), grid, dim3(BLOCK), 0, st, a, e);                       \
+    return hipGetLastError();                                                                                 \
+  }
+  CLV_FOR_K(CLV_CASE, 2, false)
+  CLV_FOR_K(CLV_CASE, 3, false)
+  CLV_FOR_K(CLV_CASE, 2, true)
+  CLV_FOR_K(CLV_CASE, 3, true)
+#undef CLV_CASE
+  return hipErrorInvalidValue;
+}
+
+// VGPRs and scratch bytes per lane of a score instance (hipFuncGetAttributes).
+hipError_t score_resources(int D, int K, bool summary, int* vgprs, size_t* scratch_bytes) {
+  hipFuncAttributes fa{};
+#define CLV_CASE(DD, KK, SS)                                                                                   \
+  if (D == DD && K == KK && summary == SS) {                                                                   \
+    const hipError_t err = hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&score_kernel<DD, KK, SS>)); \
+    *vgprs = fa.numRegs;                                                                                       \
+    *scratch_bytes = fa.localSizeBytes;                                                                        \
+    return err;                                                                                                \
+  }
+  CLV_FOR_K(CLV_CASE, 2, false)
+  CLV_FOR_K(CLV_CASE, 3, false)
+  CLV_FOR_K(CLV_CASE, 2, true)
+  CLV_FOR_K(CLV_CASE, 3, true)
+#undef CLV_CASE
+  return hipErrorInvalidValue;
 }
 
 }  // namespace clv

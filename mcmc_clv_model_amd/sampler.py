@@ -470,6 +470,30 @@ class HipSampler:
                                                        dptr(out)))
         return A.ic_frames(out, self.chains * self.n_draws)
 
+    def score_customers(self, cbs_new, covariates=None, *, inner_sweeps: int = 10, warmup: int = 50,
+                        n_mh_steps: int = 20, seed: Optional[int] = 0, sink: str = "full", init=None,
+                        customer_offset: int = 0, sweep_first: int = 1) -> dict:
+        """clv_score_customers_sampler: analysis.score_customers (customers outside the fit scored
+        from its level-2 draws) with the records this sampler holds in HBM after its run — D, K,
+        omega2 and the chain keys' chain_first are the sampler's; the same bits as the host-array
+        route on read_draws()'s level-2 records."""
+        from . import analysis as A
+        _, level2, _ = self.read_draws(level1=False)
+        C, nd, width = level2.shape
+        D, K, x, t_x, T_cal, cov, log_s = A.score_problem(cbs_new, covariates, width)
+        if (D, K) != (self.D, self.K):
+            raise ValueError(f"{K - 1} covariates do not match the sampler's model (D = {self.D}, K = {self.K})")
+        n = x.shape[0]
+        opts = A.score_options(inner_sweeps, warmup, n_mh_steps, sink, customer_offset, sweep_first, nd, n)
+        lam0, mu0 = A.score_init(level2, D, K, cov, n, init)
+        l1, sums = A.score_outputs(sink, C, nd, n, D)
+        lam, mu = np.empty((C, n)), np.empty((C, n))
+        A.score_check(self._L.clv_score_customers_sampler(
+            self.h, n, x.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), dptr(t_x), dptr(T_cal), dptr(cov), dptr(log_s),
+            opts["S"], opts["warmup"], opts["inner"], resolve_seed(seed), opts["offset"], opts["sweep_first"],
+            dptr(lam0), dptr(mu0), opts["sink"], dptr(l1), dptr(sums), dptr(lam), dptr(mu)))
+        return A.score_result(sink, level2, l1, sums, lam, mu, D, opts)
+
     def chain_total_loglik(self) -> float:
         out = ctypes.c_double()
         check(self._L.clv_chain_total_loglik_sampler(self.h, ctypes.byref(out)))
