@@ -577,6 +577,50 @@ int clv_score_info(int64_t* out);
 int clv_debug_score_hyper(int32_t device, int32_t D, int32_t K, int64_t n_rec, const double* level2,
                           double omega2, double* out);
 
+/* ---- Closed-form holdout predictive distribution and forecast scores (csrc/forecast.hip) ----
+ * The number of purchases X* of customer i (x, t_x, T_cal) in (T_cal, T_cal + T_star] given stacked
+ * draw d's (lambda, mu), marginal over z and tau (the conditioning of the pointwise likelihood
+ * above).  With ml = lambda + mu, D = T_cal - t_x, E = exp(-(ml D)), t = T_star, y = ml t,
+ * r = lambda / ml, w = mu / ml:
+ *   p_alive(d, i) = (ml E) / (mu + lambda E)
+ *   pmf_alive(k)  = exp(-y) (lambda t)^k / k!  +  w r^k P(k + 1, y)     (P: regularised lower incomplete gamma)
+ *   pmf(d, i, k)  = p_alive pmf_alive(k) + (1 - p_alive) [k = 0],  k = 0 ... k_max - 1
+ *   mean(d, i)    = p_alive (lambda / mu) (-expm1(-(mu t)))
+ * A customer's posterior predictive is the mean over the draws: the draws are added in the order
+ * d = 0, 1, ..., n_draws - 1, one plain float64 addition each, into an accumulator that starts at
+ * zero, and the sum is divided by n_draws once.  One lane owns a customer and nothing else adds to
+ * its accumulators: the order depends on n_draws only, not on the launch geometry or the customer
+ * batch; no atomics.  Columns of out [n][CLV_N_FC_STATS], F the cumulative sum of the mean pmf in k
+ * order: xstar_mean; p_alive; p_zero = pmf(0); q05, q50, q95 (the smallest k with F(k) >= p, k_max
+ * if F never reaches p); tail_mass = max(0, 1 - F(k_max - 1)); and, NaN without x_star,
+ * log_score = log pmf(x*), pit_lo = F(x* - 1), pit_hi = F(x*), rps = sum_k (F(k) - [k >= x*])^2.
+ * out_pmf (or NULL) takes the mean pmf [n][k_max]; out has the same bits with and without it.
+ * A draw whose lambda or mu is not in (0, inf), or whose lambda + mu overflows, marks the customer:
+ * NaN in every column and in its pmf row.
+ * CLV_EINVAL before any device call: a null pointer, n_draws < 1 or > 2^31 - 1, n < 1 or > 2^31 - 1,
+ * width not 4 or 5, T_star not in (0, inf), k_max not in [1, 4096], an x_star[i] outside [0, k_max). */
+enum {
+  CLV_FC_XSTAR_MEAN = 0, CLV_FC_P_ALIVE, CLV_FC_P_ZERO, CLV_FC_Q05, CLV_FC_Q50, CLV_FC_Q95, CLV_FC_TAIL_MASS,
+  CLV_FC_LOG_SCORE, CLV_FC_PIT_LO, CLV_FC_PIT_HI, CLV_FC_RPS, CLV_N_FC_STATS
+};
+int clv_forecast(int32_t device, const double* level1, int64_t n_draws, int64_t n, int32_t width, const int32_t* x,
+                 const double* t_x, const double* T_cal, double T_star, int32_t k_max,
+                 const int32_t* x_star /* NULL or [n] */, double* out, double* out_pmf /* NULL or [n][k_max] */);
+/* From the draws a CLV_SINK_FULL sampler holds in HBM and the data it was created with (CLV_ESTATE
+ * as clv_predict_sampler); x_star, out and out_pmf on the host. */
+int clv_forecast_sampler(clv_sampler* s, double T_star, int32_t k_max, const int32_t* x_star, double* out,
+                         double* out_pmf);
+/* The limits of csrc/forecast.hip: out[0] customers per workgroup (256), out[1] the largest k_max
+ * (4096), out[2] the most stacked draws, out[3] the cap on the terms of the series that starts the
+ * recurrence at k_max - 1, out[4] the accumulator doubles of one customer batch by default. */
+int clv_forecast_info(int64_t* out);
+/* clv_forecast with batch_customers (> 0: customers per accumulator batch, rounded up to whole
+ * 256-customer blocks) and grid (> 0: the most workgroups per launch) overridden: the tests' knobs,
+ * the results do not depend on them. */
+int clv_debug_forecast(int32_t device, const double* level1, int64_t n_draws, int64_t n, int32_t width,
+                       const int32_t* x, const double* t_x, const double* T_cal, double T_star, int32_t k_max,
+                       const int32_t* x_star, int64_t batch_customers, int32_t grid, double* out, double* out_pmf);
+
 /* ---- Convergence diagnostics on device (csrc/diag.hip) ----
  * The reference checks convergence with ArviZ on its level-2 draws (bivariate/analysis_abe.py:
  * 651-706: az.summary, az.plot_autocorr).  Here a series is m chains x n draws (n >= 8) of one

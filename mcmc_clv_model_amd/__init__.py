@@ -26,13 +26,16 @@ against the stored (beta, Sigma) records, in the drop-ins' level_1 layout, so ev
 works on them unchanged; sink="summary" keeps only per-customer sums, for millions of customers).
 (beta, Sigma) is held fixed while a record's inner sweeps run: when the records differ, a customer
 enters each record distributed for the one before, a bias that shrinks as inner_sweeps grows.
+The holdout forecast in closed form: every customer's posterior predictive distribution of the
+number of holdout purchases, marginal over z and tau, with its mean, P(alive), quantiles, log score,
+PIT and ranked probability score (forecast, forecast_pit, compare_forecasts, forecast_table).
 
 The per-sweep work runs in hand-written HIP kernels for gfx950 (csrc/), bound through the C
 ABI in include/clvmcmc.h.  There is no CPU fallback.
 """
-from .analysis import (chain_total_loglik, compare_models, compute_table4, customer_equity,
+from .analysis import (chain_total_loglik, compare_forecasts, compare_models, compute_table4, customer_equity,
                        draw_future_transactions, draw_future_transactions_rfm_m, extract_correlation,
-                       information_criteria, level1_diagnostics,
+                       forecast, forecast_pit, forecast_table, information_criteria, level1_diagnostics,
                        level1_rank_diagnostics, level2_autocorr, level2_diagnostics, level2_rank_diagnostics,
                        level2_summary, lifetime_value, lifetime_value_elasticities, pointwise_log_likelihood,
                        post_mean_lambdas, post_mean_mus, posterior_weekly_tracking, psis_loo, score_customers,
@@ -48,5 +51,6 @@ __all__ = ["mcmc_draw_parameters", "mcmc_draw_parameters_rfm_m", "draw_future_tr
            "level1_rank_diagnostics", "level2_rank_diagnostics", "level2_summary", "ParetoNBDFitter",
            "pnbd_weekly_tracking", "mape_aggregate", "lifetime_value", "customer_equity",
            "lifetime_value_elasticities", "pointwise_log_likelihood", "information_criteria", "psis_loo",
-           "compare_models", "score_customers"]
+           "compare_models", "score_customers", "forecast", "forecast_pit", "compare_forecasts",
+           "forecast_table"]
 __version__ = "0.1.0"

@@ -166,6 +166,12 @@ def lib() -> ctypes.CDLL:
                                                   c_int32, c_uint64, c_int64, c_int64, dp, dp, c_int32, dp, dp, dp, dp]),
         "clv_score_info": (c_int32, [POINTER(c_int64)]),
         "clv_debug_score_hyper": (c_int32, [c_int32, c_int32, c_int32, c_int64, dp, c_double, dp]),
+        "clv_forecast": (c_int32, [c_int32, dp, c_int64, c_int64, c_int32, POINTER(c_int32), dp, dp, c_double, c_int32,
+                                   POINTER(c_int32), dp, dp]),
+        "clv_forecast_sampler": (c_int32, [sp, c_double, c_int32, POINTER(c_int32), dp, dp]),
+        "clv_forecast_info": (c_int32, [POINTER(c_int64)]),
+        "clv_debug_forecast": (c_int32, [c_int32, dp, c_int64, c_int64, c_int32, POINTER(c_int32), dp, dp, c_double,
+                                         c_int32, POINTER(c_int32), c_int64, c_int32, dp, dp]),
         "clv_diagnostics": (c_int32, [c_int32, dp, c_int32, c_int64, c_int64, c_int32, c_uint32, dp]),
         "clv_diagnostics_sampler": (c_int32, [sp, c_uint32, dp, dp]),
         "clv_autocorr": (c_int32, [c_int32, dp, c_int32, c_int64, c_int64, c_int32, dp]),
@@ -255,6 +261,23 @@ def score_info() -> dict:
     check(lib().clv_score_info(out))
     keys = ("block", "n_sum_stats", "D", "K", "sink", "vgprs", "scratch_bytes", "kernel_ns")
     return {k: int(v) for k, v in zip(keys, out)}
+
+
+# Columns of clv_forecast() (include/clvmcmc.h CLV_FC_*); the last four are NaN without x_star.
+FC_STATS = ("xstar_mean", "p_alive", "p_zero", "q05", "q50", "q95", "tail_mass", "log_score", "pit_lo", "pit_hi",
+            "rps")
+# The limits of csrc/forecast.hip (clv_forecast_info reports the library's own; tests/test_forecast_cpu.py
+# compares): customers per workgroup, the largest k_max, the most stacked draws, the cap on the terms
+# of the series that starts the recurrence, the accumulator doubles of one customer batch.
+FC_BLOCK, FC_MAX_K, FC_MAX_DRAWS, FC_SERIES_CAP, FC_BATCH_DOUBLES = 256, 4096, (1 << 31) - 1, 4096, 1 << 25
+
+
+def forecast_info() -> dict:
+    """The limits of csrc/forecast.hip (clv_forecast_info)."""
+    out = (c_int64 * 5)()
+    check(lib().clv_forecast_info(out))
+    return dict(block=int(out[0]), max_k=int(out[1]), max_draws=int(out[2]), series_cap=int(out[3]),
+                batch_doubles=int(out[4]))
 
 
 def exported_symbols():

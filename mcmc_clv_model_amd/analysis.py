@@ -26,6 +26,10 @@ Reference functions mirrored (same names, arguments, defaults and return layout)
   ``az.from_dict`` and never compares: WAIC and PSIS-LOO per customer (``csrc/ic.hip``).
 * ``score_customers`` — level-1 draws for customers outside the fit, from its level-2 draws
   (``csrc/score.hip``): bi:193-227, 268-339 and tri:306-333 run against stored (beta, Sigma) records.
+* ``forecast``, ``forecast_pit``, ``compare_forecasts``, ``forecast_table`` — the holdout forecast the
+  reference builds its draws for, in closed form (``csrc/forecast.hip``): every customer's predictive
+  distribution of the holdout count, its out-of-sample scores, Table 2's disaggregate rows and
+  Figure 3's conditional expectations from the posterior mean instead of a plug-in.
 
 The per-customer / per-draw work runs in ``csrc/analysis.hip`` through the C ABI (``clv_predict``,
 ``clv_track``, ``clv_level1_summary``, ``clv_chain_total_loglik``); the host only reshapes and
@@ -50,7 +54,8 @@ __all__ = ["draw_future_transactions", "draw_future_transactions_rfm_m", "post_m
            "level1_diagnostics", "level2_diagnostics", "level2_autocorr", "summarize_level2", "extract_correlation",
            "summary_rhat", "level1_rank_diagnostics", "level2_rank_diagnostics", "level2_summary",
            "lifetime_value", "customer_equity", "lifetime_value_elasticities",
-           "pointwise_log_likelihood", "information_criteria", "psis_loo", "compare_models", "score_customers"]
+           "pointwise_log_likelihood", "information_criteria", "psis_loo", "compare_models", "score_customers",
+           "forecast", "forecast_pit", "compare_forecasts", "forecast_table"]
 
 
 def _stacked_level1(level1_chains) -> np.ndarray:
@@ -729,6 +734,164 @@ def compare_models(models: Dict[str, Dict[str, Any]], criterion: str = "loo") ->
                          dse=float(np.sqrt(n * np.var(diff))), se=float(tot["se"]), n_bad_k=int(tot["n_bad_k"]),
                          warning=bool(tot["warning"])))
     return pd.DataFrame(rows, index=pd.Index(order, name="model"))
+
+
+# ---- the closed-form holdout forecast and its scores (csrc/forecast.hip) ---------------------
+def forecast_params(T_star=39.0, x_star=None, k_max=None, pmf=False, cbs=None, n: Optional[int] = None) -> dict:
+    """T_star / x_star / k_max of :func:`forecast`, validated (ValueError) on the host.  ``x_star`` may
+    name a column of ``cbs``; ``k_max=None`` gives ``64 ceil((max(63, max x*) + 1) / 64)``."""
+    t = float(T_star)
+    if not (np.isfinite(t) and t > 0.0):
+        raise ValueError(f"T_star must be finite and > 0 (got {T_star!r})")
+    xs = None
+    if x_star is not None:
+        if isinstance(x_star, str):
+            if cbs is None or x_star not in cbs:
+                raise ValueError(f"x_star names the column {x_star!r}, which cbs does not have")
+            x_star = cbs[x_star].to_numpy()
+        v = np.asarray(x_star)
+        if v.ndim != 1 or (n is not None and v.shape[0] != n):
+            raise ValueError("x_star must hold one count per customer")
+        if v.size and (not np.all(np.isfinite(v)) or np.any(v < 0) or np.any(v != np.floor(v))):
+            raise ValueError("x_star must hold non-negative whole numbers")
+        if v.size and v.max() >= _lib.FC_MAX_K:
+            raise ValueError(f"x_star reaches {int(v.max())}: the forecast covers counts below {_lib.FC_MAX_K}")
+        xs = np.ascontiguousarray(v, dtype=np.int32)
+    if k_max is None:
+        top = 63 if xs is None or xs.size == 0 else max(63, int(xs.max()))
+        k_max = 64 * -(-(top + 1) // 64)
+    if int(k_max) != k_max or not 1 <= int(k_max) <= _lib.FC_MAX_K:
+        raise ValueError(f"k_max must be a whole number in [1, {_lib.FC_MAX_K}] (got {k_max!r})")
+    k_max = int(k_max)
+    if xs is not None and xs.size and int(xs.max()) >= k_max:
+        raise ValueError(f"x_star reaches {int(xs.max())}, outside [0, k_max = {k_max})")
+    return dict(T_star=t, x_star=xs, k_max=k_max, pmf=bool(pmf))
+
+
+def forecast_frames(stats: np.ndarray, pmf: Optional[np.ndarray], n_samples: int, has_x_star: bool) -> dict:
+    """The per-customer columns [n][len(_lib.FC_STATS)] as {"pointwise", "scores", "frequency",
+    "pmf"}.  ``scores`` (one row, sums by :func:`fixed_order_sum`): log_score = the sum of the
+    customers' log scores, se = sqrt(N var(., ddof 0)), rps = the mean ranked probability score,
+    coverage_90 = the share of customers with q05 <= x* <= q95, n_samples, n_data_points; the score
+    columns are NaN without x_star.  ``frequency`` (with the pmf only): the expected number of
+    customers with k purchases, k = 0 ... k_max - 1, and a last entry ">=k_max" from the tail
+    masses."""
+    pw = pd.DataFrame(stats, columns=list(_lib.FC_STATS))
+    n = stats.shape[0]
+    row = dict(log_score=np.nan, se=np.nan, rps=np.nan, coverage_90=np.nan)
+    if has_x_star:
+        ls = pw["log_score"].to_numpy()
+        tot = fixed_order_sum(ls)
+        dev = ls - tot / n
+        # q05 <= x* is F(x*) >= 0.05, x* <= q95 is F(x* - 1) < 0.95
+        lo = np.where(pw["pit_hi"].to_numpy() >= 0.05, 1.0, 0.0)
+        hi = np.where(pw["pit_lo"].to_numpy() < 0.95, 1.0, 0.0)
+        row = dict(log_score=tot, se=float(np.sqrt(n * (fixed_order_sum(dev * dev) / n))),
+                   rps=fixed_order_sum(pw["rps"].to_numpy()) / n, coverage_90=fixed_order_sum(lo * hi) / n)
+    row.update(n_samples=int(n_samples), n_data_points=int(n))
+    freq = None
+    if pmf is not None:
+        vals = [fixed_order_sum(pmf[:, k]) for k in range(pmf.shape[1])]
+        vals.append(fixed_order_sum(pw["tail_mass"].to_numpy()))
+        freq = pd.Series(vals, index=pd.Index(list(range(pmf.shape[1])) + [f">={pmf.shape[1]}"], name="x_star"),
+                         name="expected_customers")
+    return dict(pointwise=pw, scores=pd.DataFrame([row]), frequency=freq, pmf=pmf)
+
+
+def forecast(draws: Dict[str, Any], cbs: pd.DataFrame, T_star: float = 39.0, *, x_star=None, k_max=None,
+             pmf: bool = False, device: int = -1) -> Dict[str, Any]:
+    """The posterior predictive distribution of every customer's number of purchases in the
+    ``T_star`` periods after calibration, in closed form, on the GPU (``csrc/forecast.hip``,
+    ``clv_forecast``): given a draw's (lambda, mu) the count is marginal over z and tau — a customer
+    alive at T_cal may still drop out during the holdout, unlike in
+    :func:`draw_future_transactions`, which restates the reference's simulation (there a customer
+    whose sampled z is 1 buys for the whole of T_star) — and the distribution is the mean over the
+    draws, not a sample.  ``x_star`` (an array, or the name of a CBS column) adds the scores of the
+    realised counts; ``k_max`` is the number of counts covered (default
+    ``64 ceil((max(63, max x*) + 1) / 64)``, at most 4096); ``pmf=True`` also returns the
+    (n_customers, k_max) distribution.
+
+    Returns ``{"pointwise": DataFrame, one row per customer, columns _lib.FC_STATS (xstar_mean,
+    p_alive, p_zero, q05, q50, q95, tail_mass; log_score, pit_lo, pit_hi, rps with x_star),
+    "scores", "frequency", "pmf"}`` (:func:`forecast_frames`; "frequency" needs the pmf and is None
+    without it).  Arguments are checked before any device is touched."""
+    a = _stacked_level1(draws.get("level_1"))
+    nd, n, w = a.shape
+    x, t_x, T_cal, _ = _ic_data(cbs, n, False)
+    par = forecast_params(T_star, x_star, k_max, pmf, cbs, n)
+    L = _L()
+    out = np.empty((n, len(_lib.FC_STATS)), np.float64)
+    dist = np.empty((n, par["k_max"]), np.float64) if par["pmf"] else None
+    xs = par["x_star"]
+    check(L.clv_forecast(int(device), dptr(a), nd, n, w, _i32p(x), dptr(t_x), dptr(T_cal), par["T_star"],
+                         par["k_max"], None if xs is None else _i32p(xs), dptr(out), dptr(dist)))
+    return forecast_frames(out, dist, nd, xs is not None)
+
+
+def forecast_pit(fc: Dict[str, Any], bins: int = 10, seed: int = 0) -> pd.Series:
+    """The randomised probability integral transform histogram of a scored :func:`forecast`:
+    u_i = pit_lo + v_i (pit_hi - pit_lo) with v_i uniform (numpy's default_rng(seed)), counted in
+    ``bins`` equal bins of [0, 1].  A calibrated forecast gives a flat histogram.  Host numpy."""
+    pw = fc["pointwise"]
+    lo, hi = pw["pit_lo"].to_numpy(), pw["pit_hi"].to_numpy()
+    if int(bins) < 1:
+        raise ValueError("bins must be >= 1")
+    if np.isnan(lo).any() or np.isnan(hi).any():
+        raise ValueError("the forecast carries no PIT values (it was made without x_star, or a customer is NaN)")
+    u = lo + np.random.default_rng(seed).random(len(lo)) * (hi - lo)
+    counts, edges = np.histogram(np.clip(u, 0.0, 1.0), bins=int(bins), range=(0.0, 1.0))
+    return pd.Series(counts, index=pd.Index(edges[:-1], name="pit_bin_left"), name="customers")
+
+
+def compare_forecasts(forecasts: Dict[str, Dict[str, Any]]) -> pd.DataFrame:
+    """Rank forecasts of the same customers' holdout counts by their total log score, best first:
+    rank, log_score, ``diff`` = the best forecast's log score minus this one's,
+    ``dse = sqrt(N var(log_score_i - log_score_best,i, ddof 0))`` from the paired per-customer
+    values, se and rps (:func:`compare_models` for the out-of-sample score)."""
+    if not forecasts:
+        raise ValueError("no forecast to compare")
+    point = {k: f["pointwise"]["log_score"].to_numpy() for k, f in forecasts.items()}
+    sizes = {len(v) for v in point.values()}
+    if len(sizes) != 1:
+        raise ValueError(f"the forecasts cover different numbers of customers: {sorted(sizes)}")
+    if any(np.isnan(v).all() for v in point.values()):
+        raise ValueError("a forecast carries no log score (it was made without x_star)")
+    n = sizes.pop()
+    total = {k: float(f["scores"]["log_score"].iloc[0]) for k, f in forecasts.items()}
+    order = sorted(forecasts, key=lambda k: -total[k])
+    best = order[0]
+    rows = []
+    for r, k in enumerate(order):
+        sc = forecasts[k]["scores"].iloc[0]
+        diff = point[best] - point[k]
+        rows.append(dict(rank=r, log_score=total[k], diff=total[best] - total[k],
+                         dse=float(np.sqrt(n * np.var(diff))), se=float(sc["se"]), rps=float(sc["rps"])))
+    return pd.DataFrame(rows, index=pd.Index(order, name="model"))
+
+
+def forecast_table(fc: Dict[str, Any], cbs: pd.DataFrame, pool_from: int = 7) -> Dict[str, Any]:
+    """Table 2's disaggregate rows and Figure 3's data from the posterior mean forecast
+    (``xstar_mean``) and the realised ``cbs["x_star"]``: ``{"metrics": one-row DataFrame correlation
+    (Pearson) and mse, "by_frequency": DataFrame indexed by calibration x (0 ... pool_from - 1 and
+    "7+" pooled) with n, actual = mean x_star, predicted = mean xstar_mean}``
+    (analysis_abe.py compute_metrics and its conditional-expectation figure).  Host numpy."""
+    if "x_star" not in cbs or "x" not in cbs:
+        raise ValueError("cbs needs the columns x and x_star")
+    pred = fc["pointwise"]["xstar_mean"].to_numpy()
+    act = cbs["x_star"].to_numpy(float)
+    x = cbs["x"].to_numpy()
+    if not (len(pred) == len(act) == len(x)):
+        raise ValueError("cbs and the forecast disagree on the number of customers")
+    corr = float(np.corrcoef(act, pred)[0, 1]) if len(act) > 1 else float("nan")
+    metrics = pd.DataFrame([dict(correlation=corr, mse=float(np.mean((act - pred) ** 2)))])
+    rows, labels = [], []
+    for k in range(int(pool_from) + 1):
+        sel = x >= pool_from if k == pool_from else x == k
+        if not sel.any():
+            continue
+        labels.append(f"{pool_from}+" if k == pool_from else str(k))
+        rows.append(dict(n=int(sel.sum()), actual=float(act[sel].mean()), predicted=float(pred[sel].mean())))
+    return dict(metrics=metrics, by_frequency=pd.DataFrame(rows, index=pd.Index(labels, name="x")))
 
 
 # ---- convergence diagnostics (csrc/diag.hip) -------------------------------------------------

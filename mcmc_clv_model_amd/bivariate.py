@@ -31,13 +31,17 @@ line and return layout (bivariate/mcmc.py:437-504); the sweeps run on the GPU
   ``omega2``, ``reff``), adds ``out["information_criteria"]``: WAIC and PSIS-LOO per customer and in
   total, from the draws still in HBM (``csrc/ic.hip``; ``draw_sink="full"`` only); compare two fits
   with ``analysis.compare_models``.  None changes nothing.
+* ``forecast``: True, or a dict of ``analysis.forecast``'s keywords (``T_star``, ``x_star`` — an array or
+  the name of a column of ``cal_cbs`` —, ``k_max``, ``pmf``), adds ``out["forecast"]``: the closed-form
+  predictive distribution of every customer's holdout purchases and, with ``x_star``, its scores, from
+  the draws still in HBM (``csrc/forecast.hip``; ``draw_sink="full"`` only).  None changes nothing.
 """
 from __future__ import annotations
 
 from typing import Optional, Sequence
 
 from .analysis import draw_future_transactions  # bi:506-546 (posterior predictive, csrc/analysis.hip)
-from .sampler import build_problem, fit
+from .sampler import build_problem, fit, forecast_kwargs
 
 __all__ = ["mcmc_draw_parameters", "draw_future_transactions"]
 
@@ -48,7 +52,7 @@ def mcmc_draw_parameters(cal_cbs, covariates: Optional[Sequence[str]] = None, mc
                          rng: str = "philox", device: int = -1, replay_tape=None,
                          replay_sweeps: Optional[int] = None, devices: Optional[Sequence[int]] = None,
                          shard: str = "auto", exchange: str = "auto", diagnostics=False, lifetime_value=None,
-                         information_criteria=None):
+                         information_criteria=None, forecast=None):
     """Run the Abe (2009) Gibbs/MH sampler on calibration CBS (bivariate/mcmc.py:437).
 
     Returns dict(level_1=[(n_draws, N, 4) per chain: lambda, mu, tau, z],
@@ -67,4 +71,5 @@ def mcmc_draw_parameters(cal_cbs, covariates: Optional[Sequence[str]] = None, mc
                n_mh_steps=n_mh_steps, draw_sink=draw_sink, rng=rng, device=device,
                replay_tape=replay_tape, replay_sweeps=replay_sweeps, devices=devices, shard=shard,
                exchange=exchange, diagnostics=diagnostics, lifetime_value=lifetime_value,
-               information_criteria=information_criteria)
+               information_criteria=information_criteria,
+               forecast=forecast_kwargs(forecast, draw_sink, cal_cbs))

@@ -494,6 +494,21 @@ class HipSampler:
             dptr(lam0), dptr(mu0), opts["sink"], dptr(l1), dptr(sums), dptr(lam), dptr(mu)))
         return A.score_result(sink, level2, l1, sums, lam, mu, D, opts)
 
+    def forecast(self, T_star: float = 39.0, *, x_star=None, k_max=None, pmf: bool = False) -> dict:
+        """clv_forecast_sampler: analysis.forecast (the closed-form holdout predictive distribution
+        and its scores) of the draws this sampler holds in HBM, with the data it was created with,
+        without the host round trip; the same bits as the host-array route.  ``x_star``: an array of
+        the realised holdout counts (a column name needs a CBS: analysis.forecast)."""
+        from . import analysis as A
+        par = A.forecast_params(T_star, x_star, k_max, pmf, None, self.n)
+        out = np.empty((self.n, len(_lib.FC_STATS)), np.float64)
+        dist = np.empty((self.n, par["k_max"]), np.float64) if par["pmf"] else None
+        xs = par["x_star"]
+        check(self._L.clv_forecast_sampler(self.h, par["T_star"], par["k_max"],
+                                           None if xs is None else xs.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                           dptr(out), dptr(dist)))
+        return A.forecast_frames(out, dist, self.chains * self.n_draws, xs is not None)
+
     def chain_total_loglik(self) -> float:
         out = ctypes.c_double()
         check(self._L.clv_chain_total_loglik_sampler(self.h, ctypes.byref(out)))
@@ -607,7 +622,8 @@ def _assemble(D: int, chains: int, l1, l2, ll, sums, k: int, n_draws: int, draw_
 def fit(p: Problem, *, mcmc: int, burnin: int, thin: int, chains: int, seed, trace: int, n_mh_steps: int,
         draw_sink: str = "full", rng: str = "philox", device: int = -1, replay_tape=None,
         replay_sweeps: Optional[int] = None, devices: Optional[Sequence[int]] = None, shard: str = "auto",
-        exchange: str = "auto", diagnostics=False, lifetime_value=None, information_criteria=None) -> dict:
+        exchange: str = "auto", diagnostics=False, lifetime_value=None, information_criteria=None,
+        forecast=None) -> dict:
     """Run all chains of one problem in one batched launch sequence and return the reference's
     output layout (bi:499-504).  ``devices`` (two or more): the run is spread over those devices
     in this process (:func:`fit_multi`).  ``diagnostics``: also out["diagnostics"] = {"level_1",
@@ -620,7 +636,10 @@ def fit(p: Problem, *, mcmc: int, burnin: int, thin: int, chains: int, seed, tra
     sink only), routed as the diagnostics are.
     ``information_criteria``: True or a dict of analysis.information_criteria's keywords (spend,
     omega2, reff) adds out["information_criteria"] (WAIC and PSIS-LOO; full sink only), routed the
-    same way."""
+    same way.
+    ``forecast``: True or a dict of analysis.forecast's keywords (T_star, x_star as an array, k_max,
+    pmf) adds out["forecast"] (the closed-form holdout predictive distribution; full sink only),
+    routed the same way."""
     if chains < 1:
         raise ValueError("chains must be >= 1")
     if thin < 1:
@@ -631,6 +650,7 @@ def fit(p: Problem, *, mcmc: int, burnin: int, thin: int, chains: int, seed, tra
         raise ValueError("diagnostics=True needs draw_sink='full' (analysis.summary_rhat serves a summary run)")
     ltv_kw = lifetime_value_kwargs(lifetime_value, draw_sink)
     ic_kw = information_criteria_kwargs(information_criteria, draw_sink, p.D)
+    fc_kw = forecast_kwargs(forecast, draw_sink, n=p.N)
     if devices is not None:
         devices = [int(d) for d in devices]
         if not devices:
@@ -641,7 +661,7 @@ def fit(p: Problem, *, mcmc: int, burnin: int, thin: int, chains: int, seed, tra
             out = fit_multi(p, mcmc=mcmc, burnin=burnin, thin=thin, chains=chains, seed=seed, trace=trace,
                             n_mh_steps=n_mh_steps, draw_sink=draw_sink, devices=devices, shard=shard,
                             exchange=exchange, lifetime_value=lifetime_value,
-                            information_criteria=information_criteria)
+                            information_criteria=information_criteria, forecast=forecast)
             if diagnostics:
                 from . import analysis as A
                 out["diagnostics"] = dict(level_1=A.level1_diagnostics(out, device=devices[0]),
@@ -675,6 +695,8 @@ def fit(p: Problem, *, mcmc: int, burnin: int, thin: int, chains: int, seed, tra
             out["lifetime_value"] = s.lifetime_value(**ltv_kw)
         if ic_kw is not None:
             out["information_criteria"] = s.information_criteria(**ic_kw)
+        if fc_kw is not None:
+            out["forecast"] = s.forecast(**fc_kw)
         return out
     finally:
         s.close()
@@ -728,6 +750,31 @@ def information_criteria_kwargs(information_criteria, draw_sink: str, D: int):
     return kw
 
 
+def forecast_kwargs(forecast, draw_sink: str, cbs=None, n=None):
+    """The ``forecast=`` keyword of the fit functions as analysis.forecast's keywords (None: not asked
+    for), validated before the run starts; an ``x_star`` given as a column name is taken from
+    ``cbs`` (the drop-ins have one)."""
+    if forecast is None or forecast is False:
+        return None
+    if forecast is True:
+        kw = {}
+    elif isinstance(forecast, dict):
+        kw = dict(forecast)
+    else:
+        raise ValueError(f"forecast must be None, True or a dict of keywords (got {forecast!r})")
+    if draw_sink != "full":
+        raise ValueError("forecast needs draw_sink='full' (it is computed from the level-1 draws)")
+    from . import analysis as A
+    allowed = ("T_star", "x_star", "k_max", "pmf")
+    bad = sorted(set(kw) - set(allowed))
+    if bad:
+        raise ValueError(f"forecast takes the keywords {allowed} (got {bad})")
+    par = A.forecast_params(kw.get("T_star", 39.0), kw.get("x_star"), kw.get("k_max"), kw.get("pmf", False), cbs, n)
+    if "x_star" in kw and kw["x_star"] is not None:
+        kw["x_star"] = par["x_star"]
+    return kw
+
+
 def multi_plan(chains: int, n_dev: int, draw_sink: str, shard: str = "auto"):
     """How :func:`fit_multi` spreads a run over ``n_dev`` devices: ("chains", [(first chain,
     chains), ...] one group per device used) or ("customers", None).  "auto" takes chain groups
@@ -749,7 +796,7 @@ def multi_plan(chains: int, n_dev: int, draw_sink: str, shard: str = "auto"):
 
 def fit_multi(p: Problem, *, mcmc: int, burnin: int, thin: int, chains: int, seed, trace: int, n_mh_steps: int,
               draw_sink: str, devices: Sequence[int], shard: str = "auto", exchange: str = "auto",
-              lifetime_value=None, information_criteria=None) -> dict:
+              lifetime_value=None, information_criteria=None, forecast=None) -> dict:
     """One run over several devices of this process (SURVEY §8b ``devices=``), same output as the
     single-device run, bit for bit:
 
@@ -763,11 +810,12 @@ def fit_multi(p: Problem, *, mcmc: int, burnin: int, thin: int, chains: int, see
     * ``"auto"``: chains when they divide evenly over the devices (and the sink is not
       "summary+pct", whose percentiles pool all chains), else customers.
 
-    ``lifetime_value``, ``information_criteria``: as :func:`fit`, computed from the returned arrays
+    ``lifetime_value``, ``information_criteria``, ``forecast``: as :func:`fit`, computed from the returned arrays
     on ``devices[0]``."""
     import threading
     ltv_kw = lifetime_value_kwargs(lifetime_value, draw_sink)
     ic_kw = information_criteria_kwargs(information_criteria, draw_sink, p.D)
+    fc_kw = forecast_kwargs(forecast, draw_sink, n=p.N)
 
     def finish(out):
         if ltv_kw is not None:
@@ -781,6 +829,11 @@ def fit_multi(p: Problem, *, mcmc: int, burnin: int, thin: int, chains: int, see
                 cbs["log_s"] = p.log_s
             out["information_criteria"] = A.information_criteria(out, pd.DataFrame(cbs), device=int(devices[0]),
                                                                  **ic_kw)
+        if fc_kw is not None:
+            from . import analysis as A
+            import pandas as pd
+            out["forecast"] = A.forecast(out, pd.DataFrame(dict(x=p.x, t_x=p.t_x, T_cal=p.T_cal)),
+                                         device=int(devices[0]), **fc_kw)
         return out
 
     n_dev = len(devices)

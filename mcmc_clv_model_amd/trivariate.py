@@ -9,7 +9,7 @@ from __future__ import annotations
 from typing import Optional, Sequence
 
 from .analysis import draw_future_transactions_rfm_m as draw_future_transactions  # tri:660-749
-from .sampler import build_problem, fit
+from .sampler import build_problem, fit, forecast_kwargs
 
 __all__ = ["mcmc_draw_parameters_rfm_m", "draw_future_transactions"]
 
@@ -20,7 +20,7 @@ def mcmc_draw_parameters_rfm_m(cal_cbs, covariates: Optional[Sequence[str]] = No
                                draw_sink: str = "full", rng: str = "philox", device: int = -1,
                                replay_tape=None, replay_sweeps: Optional[int] = None,
                                devices: Optional[Sequence[int]] = None, shard: str = "auto", exchange: str = "auto",
-                               diagnostics=False, lifetime_value=None, information_criteria=None):
+                               diagnostics=False, lifetime_value=None, information_criteria=None, forecast=None):
     """3-dimensional HB Pareto/NBD + spend sampler (trivariate/mcmc.py:580).
 
     Returns {"level_1": [(n_draws, N, 5) per chain: lambda, mu, tau, z, eta],
@@ -33,6 +33,7 @@ def mcmc_draw_parameters_rfm_m(cal_cbs, covariates: Optional[Sequence[str]] = No
               n_mh_steps=n_mh_steps, draw_sink=draw_sink, rng=rng, device=device,
               replay_tape=replay_tape, replay_sweeps=replay_sweeps, devices=devices, shard=shard,
               exchange=exchange, diagnostics=diagnostics, lifetime_value=lifetime_value,
-              information_criteria=information_criteria)
+              information_criteria=information_criteria,
+              forecast=forecast_kwargs(forecast, draw_sink, cal_cbs))
     out["log_likelihood"] = float(out["log_likelihood"])  # tri:652 returns a Python float
     return out
