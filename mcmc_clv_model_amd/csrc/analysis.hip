@@ -17,15 +17,13 @@
 // order (numpy's axis-0 reduction is sequential over draws) and the percentiles apply numpy's
 // 'linear' rule to exactly sorted draws.
 #include <hip/hip_runtime.h>
-#include <rocprim/device/device_segmented_radix_sort.hpp>
 
 #include <algorithm>
 #include <cmath>
 #include <string>
 #include <vector>
 
-#include "internal.h"
-#include "percentile.h"
+#include "analysis_host.h"
 #include "philox.h"
 
 using namespace clv;
@@ -217,11 +215,6 @@ __global__ __launch_bounds__(256) void gather_kernel(const double* level1, int64
   seg[c * n_draws + d] = level1[(d * n + i0 + c) * width + col];
 }
 
-__global__ void offsets_kernel(int64_t nc, int64_t n_draws, uint32_t* off) {
-  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (c <= nc) off[c] = (uint32_t)(c * n_draws);
-}
-
 // CLV_SINK_SUMMARY_PCT: column col (0 lambda, 1 mu) of customers [i0, i0 + nc) from the sampler's
 // float32 store [chain * draw][n] to [customer][chain * draw] (the sort's segments).
 __global__ __launch_bounds__(256) void gather_q_kernel(const float2* q, int64_t n_draws, int64_t n, int col,
@@ -247,17 +240,6 @@ __global__ __launch_bounds__(256) void sums_mean_kernel(const double* sums, int 
     for (int c = 0; c < n_chains; ++c) acc += sums[((int64_t)c * CLV_N_SUM_STATS + stat[k]) * n + i];
     out[i * CLV_N_L1_STATS + dst[k]] = (k == 5 && D != 3) ? 0.0 : acc / tot;
   }
-}
-
-template <class T>
-__global__ __launch_bounds__(256) void percentile_kernel(const T* sorted, int64_t nc, int64_t n_draws,
-                                                         int64_t i0, int col_lo, int col_hi, double* out) {
-  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= nc) return;
-  const T* a = sorted + c * n_draws;
-  double* o = out + (i0 + c) * CLV_N_L1_STATS;
-  o[col_lo] = np_percentile_sorted(a, n_draws, 2.5);
-  o[col_hi] = np_percentile_sorted(a, n_draws, 97.5);
 }
 
 // chain_total_loglik: per draw, sum over customers of x log(lam) + (1-z) log(mu)
@@ -299,16 +281,6 @@ void seed_key(uint64_t seed, uint32_t* k0, uint32_t* k1) {
   *k1 = (uint32_t)(seed >> 32);
 }
 
-// Uploads a host level-1 array [n_draws][n][width] (or uses the device pointer as is).
-int stage_level1(const double* host, int64_t n_draws, int64_t n, int32_t width, DevBuf& buf, const double** dev,
-                 hipStream_t st) {
-  const size_t bytes = sizeof(double) * (size_t)n_draws * n * width;
-  CLV_HIP(hipMalloc(&buf.p, bytes));
-  CLV_HIP(hipMemcpyAsync(buf.p, host, bytes, hipMemcpyHostToDevice, st));
-  *dev = (const double*)buf.p;
-  return CLV_OK;
-}
-
 int predict_dev(const double* l1, int64_t n_draws, int64_t n, int32_t width, const double* dT, double T_star,
                 uint64_t seed, int32_t spend, double sigma_s, int64_t* x_future, double* spend_future, hipStream_t st) {
   DevBuf bx, bs;
@@ -332,11 +304,9 @@ int track_dev(const double* l1, int64_t n_draws, int64_t n, int32_t width, const
   for (int j = 1; j < n_times; ++j)
     if (!(times[j] >= times[j - 1])) return fail(CLV_EINVAL, "times must be ascending");
   DevBuf bb, bt, bi;
-  CLV_HIP(hipMalloc(&bb.p, sizeof(double) * n));
-  CLV_HIP(hipMalloc(&bt.p, sizeof(double) * n_times));
+  int rc;
+  if ((rc = upload(bb, birth, n, st)) || (rc = upload(bt, times, n_times, st))) return rc;
   CLV_HIP(hipMalloc(&bi.p, sizeof(int64_t) * n_draws * n_times));
-  CLV_HIP(hipMemcpyAsync(bb.p, birth, sizeof(double) * n, hipMemcpyHostToDevice, st));
-  CLV_HIP(hipMemcpyAsync(bt.p, times, sizeof(double) * n_times, hipMemcpyHostToDevice, st));
   uint32_t k0, k1;
   seed_key(seed, &k0, &k1);
   hipLaunchKernelGGL(track_kernel, dim3((unsigned)std::min<int64_t>(n_draws, 1 << 20)), dim3(TRACK_LANES), 0, st,
@@ -355,45 +325,32 @@ int track_dev(const double* l1, int64_t n_draws, int64_t n, int32_t width, const
   return CLV_OK;
 }
 
-int summary_dev(const double* l1, int64_t n_draws, int64_t n, int32_t width, double mu_cap, double* out,
-                hipStream_t st) {
-  DevBuf bo;
+// The level-1 summary [n][CLV_N_L1_STATS] -> out (host): means(dout) launches the kernel of the six
+// means, gather(col, i0, nc, seg) the one laying column col (0 lambda, 1 mu) of customers
+// [i0, i0 + nc) out as [customer][draw] keys of type K.  Percentiles: customers in batches of
+// <= 2^27 keys, exact segmented radix sort per customer.
+template <class K, class Means, class Gather>
+int summary_dev(int64_t n_draws, int64_t n, double* out, hipStream_t st, Means means, Gather gather) {
+  DevBuf bo, bin;
   CLV_HIP(hipMalloc(&bo.p, sizeof(double) * n * CLV_N_L1_STATS));
   double* dout = (double*)bo.p;
-  hipLaunchKernelGGL(mean_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, l1, n_draws, n, width, mu_cap,
-                     dout);
+  means(dout);
   CLV_HIP(hipGetLastError());
-  // percentiles: customers in batches of <= 2^27 keys, exact segmented radix sort per customer
   const int64_t per_batch = std::max<int64_t>(1, std::min<int64_t>(n, (int64_t(1) << 27) / n_draws));
-  DevBuf bin, bsorted, boff, btmp;
-  const size_t keys = (size_t)per_batch * n_draws;
-  CLV_HIP(hipMalloc(&bin.p, sizeof(double) * keys));
-  CLV_HIP(hipMalloc(&bsorted.p, sizeof(double) * keys));
-  CLV_HIP(hipMalloc(&boff.p, sizeof(uint32_t) * (per_batch + 1)));
-  size_t tmp_bytes = 0;
-  CLV_HIP(rocprim::segmented_radix_sort_keys((void*)nullptr, tmp_bytes, (const double*)bin.p, (double*)bsorted.p,
-                                             (unsigned)keys, (unsigned)per_batch, (const uint32_t*)boff.p,
-                                             (const uint32_t*)boff.p + 1, 0, 64, st));
-  CLV_HIP(hipMalloc(&btmp.p, std::max<size_t>(tmp_bytes, 16)));
-  const int cols[2] = {0, 1};
-  const int lo_idx[2] = {CLV_L1_LAMBDA_P025, CLV_L1_MU_P025};
-  const int hi_idx[2] = {CLV_L1_LAMBDA_P975, CLV_L1_MU_P975};
+  CLV_HIP(hipMalloc(&bin.p, sizeof(K) * (size_t)per_batch * n_draws));
+  SegSorter<K> sorter;
+  int rc = sorter.init(per_batch, n_draws, st);
+  if (rc) return rc;
+  const PctCols pc[2] = {{2, {2.5, 97.5}, {CLV_L1_LAMBDA_P025, CLV_L1_LAMBDA_P975}},
+                         {2, {2.5, 97.5}, {CLV_L1_MU_P025, CLV_L1_MU_P975}}};
   for (int64_t i0 = 0; i0 < n; i0 += per_batch) {
     const int64_t nc = std::min<int64_t>(per_batch, n - i0);
-    hipLaunchKernelGGL(offsets_kernel, dim3((unsigned)((nc + 256) / 256)), dim3(256), 0, st, nc, n_draws,
-                       (uint32_t*)boff.p);
     for (int q = 0; q < 2; ++q) {
-      const int64_t ne = nc * n_draws;
-      hipLaunchKernelGGL(gather_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st, l1, n_draws, n, width,
-                         cols[q], i0, nc, (double*)bin.p);
+      gather(q, i0, nc, (K*)bin.p);
       CLV_HIP(hipGetLastError());
-      size_t tb = tmp_bytes;
-      CLV_HIP(rocprim::segmented_radix_sort_keys(btmp.p, tb, (const double*)bin.p, (double*)bsorted.p, (unsigned)ne,
-                                                 (unsigned)nc, (const uint32_t*)boff.p, (const uint32_t*)boff.p + 1,
-                                                 0, 64, st));
-      hipLaunchKernelGGL(percentile_kernel<double>, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, st,
-                         (const double*)bsorted.p, nc, n_draws, i0, lo_idx[q], hi_idx[q], dout);
-      CLV_HIP(hipGetLastError());
+      const K* sorted;
+      if ((rc = sorter.sort((const K*)bin.p, nc, &sorted))) return rc;
+      if ((rc = launch_percentiles(sorted, nc, n_draws, pc[q], i0, CLV_N_L1_STATS, dout, st))) return rc;
     }
   }
   CLV_HIP(hipMemcpyAsync(out, dout, sizeof(double) * n * CLV_N_L1_STATS, hipMemcpyDeviceToHost, st));
@@ -401,52 +358,37 @@ int summary_dev(const double* l1, int64_t n_draws, int64_t n, int32_t width, dou
   return CLV_OK;
 }
 
+// Level-1 draws in HBM: sequential means, float64 keys.
+int summary_l1(const double* l1, int64_t n_draws, int64_t n, int32_t width, double mu_cap, double* out,
+               hipStream_t st) {
+  return summary_dev<double>(
+      n_draws, n, out, st,
+      [&](double* dout) {
+        hipLaunchKernelGGL(mean_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, l1, n_draws, n, width,
+                           mu_cap, dout);
+      },
+      [&](int col, int64_t i0, int64_t nc, double* seg) {
+        hipLaunchKernelGGL(gather_kernel, dim3((unsigned)((nc * n_draws + 255) / 256)), dim3(256), 0, st, l1, n_draws,
+                           n, width, col, i0, nc, seg);
+      });
+}
+
 // CLV_SINK_SUMMARY_PCT sampler: means from the running sums, exact order statistics of the float32
-// (lambda, mu) store (segmented radix sort on 32-bit keys, customers in batches of <= 2^27 keys).
-int summary_pct_dev(clv_sampler* s, double* out) {
+// (lambda, mu) store (32-bit keys).
+int summary_pct(clv_sampler* s, double* out) {
   const Geometry& g = s->g;
   const int64_t n = g.n, n_draws = (int64_t)g.n_chains * g.n_draws;
   hipStream_t st = s->stream;
-  DevBuf bo;
-  CLV_HIP(hipMalloc(&bo.p, sizeof(double) * n * CLV_N_L1_STATS));
-  double* dout = (double*)bo.p;
-  hipLaunchKernelGGL(sums_mean_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const double*)s->d_sums,
-                     g.n_chains, n, (int64_t)g.n_draws, g.D, dout);
-  CLV_HIP(hipGetLastError());
-  const int64_t per_batch = std::max<int64_t>(1, std::min<int64_t>(n, (int64_t(1) << 27) / n_draws));
-  DevBuf bin, bsorted, boff, btmp;
-  const size_t keys = (size_t)per_batch * n_draws;
-  CLV_HIP(hipMalloc(&bin.p, sizeof(float) * keys));
-  CLV_HIP(hipMalloc(&bsorted.p, sizeof(float) * keys));
-  CLV_HIP(hipMalloc(&boff.p, sizeof(uint32_t) * (per_batch + 1)));
-  size_t tmp_bytes = 0;
-  CLV_HIP(rocprim::segmented_radix_sort_keys((void*)nullptr, tmp_bytes, (const float*)bin.p, (float*)bsorted.p,
-                                             (unsigned)keys, (unsigned)per_batch, (const uint32_t*)boff.p,
-                                             (const uint32_t*)boff.p + 1, 0, 32, st));
-  CLV_HIP(hipMalloc(&btmp.p, std::max<size_t>(tmp_bytes, 16)));
-  const int lo_idx[2] = {CLV_L1_LAMBDA_P025, CLV_L1_MU_P025};
-  const int hi_idx[2] = {CLV_L1_LAMBDA_P975, CLV_L1_MU_P975};
-  for (int64_t i0 = 0; i0 < n; i0 += per_batch) {
-    const int64_t nc = std::min<int64_t>(per_batch, n - i0);
-    hipLaunchKernelGGL(offsets_kernel, dim3((unsigned)((nc + 256) / 256)), dim3(256), 0, st, nc, n_draws,
-                       (uint32_t*)boff.p);
-    for (int q = 0; q < 2; ++q) {
-      const int64_t ne = nc * n_draws;
-      hipLaunchKernelGGL(gather_q_kernel, dim3((unsigned)((ne + 255) / 256)), dim3(256), 0, st,
-                         (const float2*)s->d_qstore, n_draws, n, q, i0, nc, (float*)bin.p);
-      CLV_HIP(hipGetLastError());
-      size_t tb = tmp_bytes;
-      CLV_HIP(rocprim::segmented_radix_sort_keys(btmp.p, tb, (const float*)bin.p, (float*)bsorted.p, (unsigned)ne,
-                                                 (unsigned)nc, (const uint32_t*)boff.p, (const uint32_t*)boff.p + 1,
-                                                 0, 32, st));
-      hipLaunchKernelGGL(percentile_kernel<float>, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, st,
-                         (const float*)bsorted.p, nc, n_draws, i0, lo_idx[q], hi_idx[q], dout);
-      CLV_HIP(hipGetLastError());
-    }
-  }
-  CLV_HIP(hipMemcpyAsync(out, dout, sizeof(double) * n * CLV_N_L1_STATS, hipMemcpyDeviceToHost, st));
-  CLV_HIP(hipStreamSynchronize(st));
-  return CLV_OK;
+  return summary_dev<float>(
+      n_draws, n, out, st,
+      [&](double* dout) {
+        hipLaunchKernelGGL(sums_mean_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
+                           (const double*)s->d_sums, g.n_chains, n, (int64_t)g.n_draws, g.D, dout);
+      },
+      [&](int col, int64_t i0, int64_t nc, float* seg) {
+        hipLaunchKernelGGL(gather_q_kernel, dim3((unsigned)((nc * n_draws + 255) / 256)), dim3(256), 0, st,
+                           (const float2*)s->d_qstore, n_draws, n, col, i0, nc, seg);
+      });
 }
 
 int loglik_dev(const double* l1, int64_t n_draws, int64_t n, int32_t width, const int32_t* dx, const double* dT,
@@ -472,16 +414,25 @@ namespace clv {
 int sampler_l1(clv_sampler* s, const double** l1, int64_t* n_draws, int32_t* width) {
   if (!s) return fail(CLV_EINVAL, "null sampler");
   if (!s->d_level1) return fail(CLV_ESTATE, "level-1 draws are on the device only with draw_sink == CLV_SINK_FULL");
-  int64_t stored = 0;
-  if (s->sweeps_done > s->g.burnin) stored = (s->sweeps_done - 1 - s->g.burnin) / s->g.thin + 1;
-  stored = std::min<int64_t>(stored, s->g.n_draws);
-  if (stored < (int64_t)s->g.n_draws) return fail(CLV_ESTATE, "the run has not stored all of its draws yet");
+  if (stored_draws(s) < (int64_t)s->g.n_draws) return fail(CLV_ESTATE, "the run has not stored all of its draws yet");
   CLV_HIP(hipSetDevice(s->device));
   CLV_HIP(hipStreamSynchronize(s->stream));
   *l1 = s->d_level1;
   *n_draws = (int64_t)s->g.n_chains * s->g.n_draws;  // [chain][draw] flattened = np.vstack order
   *width = s->g.D + 2;
   return check_l1(*n_draws, s->g.n, *width);
+}
+
+int sampler_l2(clv_sampler* s, const double** l2, const char* not_stored) {
+  if (!s) return fail(CLV_EINVAL, "null sampler");
+  if (!s->d_level2 || stored_draws(s) < (int64_t)s->g.n_draws) return fail(CLV_ESTATE, not_stored);
+  CLV_HIP(hipSetDevice(s->device));
+  CLV_HIP(hipStreamSynchronize(s->stream));
+  int rc = persist_flush(s);  // the last level-2 record may still be pending
+  if (rc) return rc;
+  CLV_HIP(hipStreamSynchronize(s->stream));
+  *l2 = s->d_level2;
+  return CLV_OK;
 }
 
 }  // namespace clv
@@ -497,13 +448,9 @@ int clv_predict(int32_t device, const double* level1, int64_t n_draws, int64_t n
     return fail(CLV_EINVAL, "bad arguments (spend needs width 5 and an output buffer)");
   DeviceScope ds(device);
   DevBuf b1, bT;
-  const double* l1;
-  rc = stage_level1(level1, n_draws, n, width, b1, &l1, nullptr);
-  if (rc) return rc;
-  CLV_HIP(hipMalloc(&bT.p, sizeof(double) * n));
-  CLV_HIP(hipMemcpy(bT.p, T_cal, sizeof(double) * n, hipMemcpyHostToDevice));
-  return predict_dev(l1, n_draws, n, width, (const double*)bT.p, T_star, seed, simulate_spend, sigma_s, x_future,
-                     spend_future, nullptr);
+  if ((rc = upload(b1, level1, (size_t)n_draws * n * width, nullptr)) || (rc = upload(bT, T_cal, n, nullptr))) return rc;
+  return predict_dev(b1.as<double>(), n_draws, n, width, bT.as<double>(), T_star, seed, simulate_spend, sigma_s,
+                     x_future, spend_future, nullptr);
 }
 
 int clv_predict_sampler(clv_sampler* s, double T_star, uint64_t seed, int32_t simulate_spend, double sigma_s,
@@ -525,10 +472,8 @@ int clv_track(int32_t device, const double* level1, int64_t n_draws, int64_t n, 
   if (!level1 || !birth_week || !times || !inc_weekly) return fail(CLV_EINVAL, "null argument");
   DeviceScope ds(device);
   DevBuf b1;
-  const double* l1;
-  rc = stage_level1(level1, n_draws, n, width, b1, &l1, nullptr);
-  if (rc) return rc;
-  return track_dev(l1, n_draws, n, width, birth_week, times, n_times, seed, inc_weekly, nullptr);
+  if ((rc = upload(b1, level1, (size_t)n_draws * n * width, nullptr))) return rc;
+  return track_dev(b1.as<double>(), n_draws, n, width, birth_week, times, n_times, seed, inc_weekly, nullptr);
 }
 
 int clv_track_sampler(clv_sampler* s, const double* birth_week, const double* times, int32_t n_times, uint64_t seed,
@@ -549,23 +494,18 @@ int clv_level1_summary(int32_t device, const double* level1, int64_t n_draws, in
   if (!level1 || !out) return fail(CLV_EINVAL, "null argument");
   DeviceScope ds(device);
   DevBuf b1;
-  const double* l1;
-  rc = stage_level1(level1, n_draws, n, width, b1, &l1, nullptr);
-  if (rc) return rc;
-  return summary_dev(l1, n_draws, n, width, mu_cap, out, nullptr);
+  if ((rc = upload(b1, level1, (size_t)n_draws * n * width, nullptr))) return rc;
+  return summary_l1(b1.as<double>(), n_draws, n, width, mu_cap, out, nullptr);
 }
 
 int clv_level1_summary_sampler(clv_sampler* s, double mu_cap, double* out) {
   if (s && !s->d_level1 && s->d_qstore) {  // CLV_SINK_SUMMARY_PCT
     if (!out) return fail(CLV_EINVAL, "null argument");
     if (mu_cap != CLV_SUMMARY_MU_CAP) return fail(CLV_EINVAL, "a summary sampler's capped mean uses mu_cap = CLV_SUMMARY_MU_CAP");
-    int64_t stored = 0;
-    if (s->sweeps_done > s->g.burnin) stored = (s->sweeps_done - 1 - s->g.burnin) / s->g.thin + 1;
-    if (std::min<int64_t>(stored, s->g.n_draws) < (int64_t)s->g.n_draws)
-      return fail(CLV_ESTATE, "the run has not stored all of its draws yet");
+    if (stored_draws(s) < (int64_t)s->g.n_draws) return fail(CLV_ESTATE, "the run has not stored all of its draws yet");
     CLV_HIP(hipSetDevice(s->device));
     CLV_HIP(hipStreamSynchronize(s->stream));
-    return summary_pct_dev(s, out);
+    return summary_pct(s, out);
   }
   const double* l1;
   int64_t nd;
@@ -573,7 +513,7 @@ int clv_level1_summary_sampler(clv_sampler* s, double mu_cap, double* out) {
   int rc = sampler_l1(s, &l1, &nd, &w);
   if (rc) return rc;
   if (!out) return fail(CLV_EINVAL, "null argument");
-  return summary_dev(l1, nd, s->g.n, w, mu_cap, out, s->stream);
+  return summary_l1(l1, nd, s->g.n, w, mu_cap, out, s->stream);
 }
 
 int clv_chain_total_loglik(int32_t device, const double* level1, int64_t n_draws, int64_t n, int32_t width,
@@ -583,14 +523,10 @@ int clv_chain_total_loglik(int32_t device, const double* level1, int64_t n_draws
   if (!level1 || !x || !T_cal || !mean_total) return fail(CLV_EINVAL, "null argument");
   DeviceScope ds(device);
   DevBuf b1, bx, bT;
-  const double* l1;
-  rc = stage_level1(level1, n_draws, n, width, b1, &l1, nullptr);
-  if (rc) return rc;
-  CLV_HIP(hipMalloc(&bx.p, sizeof(int32_t) * n));
-  CLV_HIP(hipMalloc(&bT.p, sizeof(double) * n));
-  CLV_HIP(hipMemcpy(bx.p, x, sizeof(int32_t) * n, hipMemcpyHostToDevice));
-  CLV_HIP(hipMemcpy(bT.p, T_cal, sizeof(double) * n, hipMemcpyHostToDevice));
-  return loglik_dev(l1, n_draws, n, width, (const int32_t*)bx.p, (const double*)bT.p, mean_total, nullptr);
+  if ((rc = upload(b1, level1, (size_t)n_draws * n * width, nullptr)) || (rc = upload(bx, x, n, nullptr)) ||
+      (rc = upload(bT, T_cal, n, nullptr)))
+    return rc;
+  return loglik_dev(b1.as<double>(), n_draws, n, width, bx.as<int32_t>(), bT.as<double>(), mean_total, nullptr);
 }
 
 int clv_chain_total_loglik_sampler(clv_sampler* s, double* mean_total) {

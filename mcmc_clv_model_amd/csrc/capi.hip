@@ -1483,11 +1483,7 @@ int clv_read_summary(clv_sampler* s, double* sums, int64_t* n_stored) {
   CLV_HIP(hipSetDevice(s->device));
   CLV_HIP(hipStreamSynchronize(s->stream));
   const Geometry& g = s->g;
-  if (n_stored) {
-    int64_t k = 0;
-    if (s->sweeps_done > g.burnin) k = (s->sweeps_done - 1 - g.burnin) / g.thin + 1;
-    *n_stored = std::min<int64_t>(k, g.n_draws);
-  }
+  if (n_stored) *n_stored = stored_draws(s);
   if (sums) {
     if (!s->d_sums) return fail(CLV_ESTATE, "summaries need draw_sink == CLV_SINK_SUMMARY (or _PCT)");
     CLV_HIP(hipMemcpy(sums, s->d_sums, sizeof(double) * g.n_chains * CLV_N_SUM_STATS * g.n, hipMemcpyDeviceToHost));

@@ -26,7 +26,7 @@
 #include <string>
 
 #include "fastmath.h"
-#include "internal.h"
+#include "analysis_host.h"
 
 using namespace clv;
 
@@ -607,43 +607,46 @@ int64_t batch_series(int64_t mn, int64_t n_series) {
   return std::max<int64_t>(1, std::min<int64_t>(n_series, DIAG_BATCH_ELEMS / mn));
 }
 
-void launch_gather(const double* d_in, int64_t mn, int64_t n_series, int64_t s0, int64_t nc, int period,
-                   uint32_t log_mask, double* seg, hipStream_t st) {
-  const int64_t tiles = ((nc + DIAG_TILE - 1) / DIAG_TILE) * ((mn + DIAG_TILE - 1) / DIAG_TILE);
-  hipLaunchKernelGGL(diag_gather_kernel, dim3((unsigned)tiles), dim3(256), 0, st, d_in, mn, n_series, s0, nc, period,
-                     log_mask, seg);
+// Walks the series of d_in (device, [chain * draw][n_series]) in batches of batch_series: each batch
+// [s0, s0 + nc) is gathered to seg [series][chain * draw] and handed to launch(seg, s0, nc), which
+// launches the batch's kernel on st.
+template <class F>
+int for_series_batches(const double* d_in, int64_t mn, int64_t n_series, int period, uint32_t log_mask, hipStream_t st,
+                       F launch) {
+  const int64_t per_batch = batch_series(mn, n_series);
+  DevBuf bseg;
+  CLV_HIP(hipMalloc(&bseg.p, sizeof(double) * (size_t)(per_batch * mn)));
+  for (int64_t s0 = 0; s0 < n_series; s0 += per_batch) {
+    const int64_t nc = std::min<int64_t>(per_batch, n_series - s0);
+    const int64_t tiles = ((nc + DIAG_TILE - 1) / DIAG_TILE) * ((mn + DIAG_TILE - 1) / DIAG_TILE);
+    hipLaunchKernelGGL(diag_gather_kernel, dim3((unsigned)tiles), dim3(256), 0, st, d_in, mn, n_series, s0, nc, period,
+                       log_mask, bseg.as<double>());
+    CLV_HIP(hipGetLastError());
+    launch(bseg.as<double>(), s0, nc);
+    CLV_HIP(hipGetLastError());
+  }
+  return CLV_OK;
 }
 
 // d_in: device [chain][draw][n_series]; host_out [n_series][CLV_N_DIAG_STATS].
 int diag_dev(const double* d_in, int32_t m, int64_t n, int64_t n_series, int period, uint32_t log_mask,
              double* host_out, hipStream_t st) {
   const int64_t mn = (int64_t)m * n;
-  const int64_t per_batch = batch_series(mn, n_series);
-  DevBuf bseg, bout;
-  CLV_HIP(hipMalloc(&bseg.p, sizeof(double) * (size_t)(per_batch * mn)));
+  DevBuf bout;
   CLV_HIP(hipMalloc(&bout.p, sizeof(double) * (size_t)n_series * CLV_N_DIAG_STATS));
   const bool lds = mn <= DIAG_LDS_ELEMS;
-  for (int64_t s0 = 0; s0 < n_series; s0 += per_batch) {
-    const int64_t nc = std::min<int64_t>(per_batch, n_series - s0);
-    launch_gather(d_in, mn, n_series, s0, nc, period, log_mask, bseg.as<double>(), st);
-    CLV_HIP(hipGetLastError());
+  int rc = for_series_batches(d_in, mn, n_series, period, log_mask, st, [&](double* seg, int64_t s0, int64_t nc) {
     if (lds)
-      hipLaunchKernelGGL(diag_kernel<true>, dim3((unsigned)nc), dim3(DIAG_LANES), sizeof(double) * (size_t)mn, st,
-                         bseg.as<double>(), (int)m, n, nc, s0, bout.as<double>());
+      hipLaunchKernelGGL(diag_kernel<true>, dim3((unsigned)nc), dim3(DIAG_LANES), sizeof(double) * (size_t)mn, st, seg,
+                         (int)m, n, nc, s0, bout.as<double>());
     else
-      hipLaunchKernelGGL(diag_kernel<false>, dim3((unsigned)nc), dim3(DIAG_LANES), 0, st, bseg.as<double>(), (int)m,
-                         n, nc, s0, bout.as<double>());
-    CLV_HIP(hipGetLastError());
-  }
+      hipLaunchKernelGGL(diag_kernel<false>, dim3((unsigned)nc), dim3(DIAG_LANES), 0, st, seg, (int)m, n, nc, s0,
+                         bout.as<double>());
+  });
+  if (rc) return rc;
   CLV_HIP(hipMemcpyAsync(host_out, bout.p, sizeof(double) * (size_t)n_series * CLV_N_DIAG_STATS,
                          hipMemcpyDeviceToHost, st));
   CLV_HIP(hipStreamSynchronize(st));
-  return CLV_OK;
-}
-
-int upload(const double* host, size_t count, DevBuf& buf) {
-  CLV_HIP(hipMalloc(&buf.p, sizeof(double) * count));
-  CLV_HIP(hipMemcpy(buf.p, host, sizeof(double) * count, hipMemcpyHostToDevice));
   return CLV_OK;
 }
 
@@ -658,28 +661,46 @@ size_t rank_lds_bytes(bool lds, int64_t mn) { return sizeof(double) * (size_t)(R
 int rank_dev(const double* d_in, int32_t m, int64_t n, int64_t n_series, int period, uint32_t log_mask,
              double hdi_prob, double* host_out, hipStream_t st) {
   const int64_t mn = (int64_t)m * n;
-  const int64_t per_batch = batch_series(mn, n_series);
   const int64_t hdi_k = std::min<int64_t>((int64_t)std::floor(hdi_prob * (double)mn), mn - 1);
   const bool lds = mn <= CLV_RANK_LDS_ELEMS;
-  DevBuf bseg, bscr, bout;
-  CLV_HIP(hipMalloc(&bseg.p, sizeof(double) * (size_t)(per_batch * mn)));
-  if (!lds) CLV_HIP(hipMalloc(&bscr.p, sizeof(double) * (size_t)(2 * per_batch * mn)));
+  DevBuf bscr, bout;
+  if (!lds) CLV_HIP(hipMalloc(&bscr.p, sizeof(double) * (size_t)(2 * batch_series(mn, n_series) * mn)));
   CLV_HIP(hipMalloc(&bout.p, sizeof(double) * (size_t)n_series * CLV_N_RANK_STATS));
-  for (int64_t s0 = 0; s0 < n_series; s0 += per_batch) {
-    const int64_t nc = std::min<int64_t>(per_batch, n_series - s0);
-    launch_gather(d_in, mn, n_series, s0, nc, period, log_mask, bseg.as<double>(), st);
-    CLV_HIP(hipGetLastError());
+  int rc = for_series_batches(d_in, mn, n_series, period, log_mask, st, [&](double* seg, int64_t s0, int64_t nc) {
     if (lds)
-      hipLaunchKernelGGL(rank_kernel<true>, dim3((unsigned)nc), dim3(RANK_THREADS), rank_lds_bytes(true, mn), st,
-                         bseg.as<double>(), (double*)nullptr, (int)m, n, nc, s0, hdi_k, bout.as<double>());
+      hipLaunchKernelGGL(rank_kernel<true>, dim3((unsigned)nc), dim3(RANK_THREADS), rank_lds_bytes(true, mn), st, seg,
+                         (double*)nullptr, (int)m, n, nc, s0, hdi_k, bout.as<double>());
     else
       hipLaunchKernelGGL(rank_kernel<false>, dim3((unsigned)nc), dim3(RANK_THREADS), rank_lds_bytes(false, mn), st,
-                         bseg.as<double>(), bscr.as<double>(), (int)m, n, nc, s0, hdi_k, bout.as<double>());
-    CLV_HIP(hipGetLastError());
-  }
+                         seg, bscr.as<double>(), (int)m, n, nc, s0, hdi_k, bout.as<double>());
+  });
+  if (rc) return rc;
   CLV_HIP(hipMemcpyAsync(host_out, bout.p, sizeof(double) * (size_t)n_series * CLV_N_RANK_STATS,
                          hipMemcpyDeviceToHost, st));
   CLV_HIP(hipStreamSynchronize(st));
+  return CLV_OK;
+}
+
+// The body of the two *_sampler entry points: dev(d_in, n_series, period, log_mask, host_out) is
+// diag_dev or rank_dev over the sampler's chains and draws.
+template <class F>
+int sampler_series(clv_sampler* s, uint32_t log_mask, double* level1_out, double* level2_out, F dev) {
+  const Geometry& g = s->g;
+  int rc;
+  if (level1_out) {
+    const double* l1;
+    int64_t nd;
+    int32_t w;
+    if ((rc = sampler_l1(s, &l1, &nd, &w)) || (rc = check_series(g.n_chains, g.n_draws, g.n * w)) ||
+        (rc = dev(l1, g.n * w, w, log_mask, level1_out)))
+      return rc;
+  }
+  if (level2_out) {
+    const double* l2;
+    if ((rc = sampler_l2(s, &l2, "the run has not stored all of its draws yet")) ||
+        (rc = check_series(g.n_chains, g.n_draws, g.l2w)) || (rc = dev(l2, g.l2w, 1, 0u, level2_out)))
+      return rc;
+  }
   return CLV_OK;
 }
 
@@ -697,8 +718,7 @@ int clv_rank_diagnostics(int32_t device, const double* series, int32_t n_chains,
   if (rc) return rc;
   DeviceScope ds(device);
   DevBuf bin;
-  rc = upload(series, (size_t)n_chains * n_draws * n_series, bin);
-  if (rc) return rc;
+  if ((rc = upload(bin, series, (size_t)n_chains * n_draws * n_series, nullptr))) return rc;
   return rank_dev(bin.as<double>(), n_chains, n_draws, n_series, period, log_mask, hdi_prob, out, nullptr);
 }
 
@@ -708,33 +728,11 @@ int clv_rank_diagnostics_sampler(clv_sampler* s, uint32_t log_mask, double hdi_p
   if (!level1_out && !level2_out) return fail(CLV_EINVAL, "null argument (no output asked for)");
   int rc = check_hdi_prob(hdi_prob);
   if (rc) return rc;
-  const Geometry& g = s->g;
-  if (level1_out) {
-    const double* l1;
-    int64_t nd;
-    int32_t w;
-    rc = sampler_l1(s, &l1, &nd, &w);
-    if (rc) return rc;
-    rc = check_series(g.n_chains, g.n_draws, g.n * w);
-    if (rc) return rc;
-    rc = rank_dev(l1, g.n_chains, g.n_draws, g.n * w, w, log_mask, hdi_prob, level1_out, s->stream);
-    if (rc) return rc;
-  }
-  if (level2_out) {
-    int64_t stored = 0;
-    if (s->sweeps_done > g.burnin) stored = (s->sweeps_done - 1 - g.burnin) / g.thin + 1;
-    if (!s->d_level2 || std::min<int64_t>(stored, g.n_draws) < (int64_t)g.n_draws)
-      return fail(CLV_ESTATE, "the run has not stored all of its draws yet");
-    rc = check_series(g.n_chains, g.n_draws, g.l2w);
-    if (rc) return rc;
-    CLV_HIP(hipSetDevice(s->device));
-    CLV_HIP(hipStreamSynchronize(s->stream));
-    rc = persist_flush(s);  // the last level-2 record may still be pending
-    if (rc) return rc;
-    rc = rank_dev(s->d_level2, g.n_chains, g.n_draws, g.l2w, 1, 0u, hdi_prob, level2_out, s->stream);
-    if (rc) return rc;
-  }
-  return CLV_OK;
+  return sampler_series(s, log_mask, level1_out, level2_out,
+                        [&](const double* d_in, int64_t n_series, int period, uint32_t mask, double* out) {
+                          return rank_dev(d_in, s->g.n_chains, s->g.n_draws, n_series, period, mask, hdi_prob, out,
+                                          s->stream);
+                        });
 }
 
 int clv_debug_zscale(int32_t device, const double* series, int32_t n_chains, int64_t n_draws, int64_t n_series,
@@ -743,30 +741,24 @@ int clv_debug_zscale(int32_t device, const double* series, int32_t n_chains, int
   int rc = check_series(n_chains, n_draws, n_series);
   if (rc) return rc;
   DeviceScope ds(device);
-  DevBuf bin, bseg, bscr, br, bz;
-  rc = upload(series, (size_t)n_chains * n_draws * n_series, bin);
-  if (rc) return rc;
+  DevBuf bin, bscr, br, bz;
+  if ((rc = upload(bin, series, (size_t)n_chains * n_draws * n_series, nullptr))) return rc;
   const int64_t mn = (int64_t)n_chains * n_draws, S = 2 * (int64_t)n_chains * (n_draws / 2);
-  const int64_t per_batch = batch_series(mn, n_series);
   const bool lds = mn <= CLV_RANK_LDS_ELEMS;
-  CLV_HIP(hipMalloc(&bseg.p, sizeof(double) * (size_t)(per_batch * mn)));
-  if (!lds) CLV_HIP(hipMalloc(&bscr.p, sizeof(double) * (size_t)(2 * per_batch * mn)));
+  if (!lds) CLV_HIP(hipMalloc(&bscr.p, sizeof(double) * (size_t)(2 * batch_series(mn, n_series) * mn)));
   CLV_HIP(hipMalloc(&br.p, sizeof(double) * (size_t)(n_series * S)));
   CLV_HIP(hipMalloc(&bz.p, sizeof(double) * (size_t)(n_series * S)));
-  for (int64_t s0 = 0; s0 < n_series; s0 += per_batch) {
-    const int64_t nc = std::min<int64_t>(per_batch, n_series - s0);
-    launch_gather(bin.as<double>(), mn, n_series, s0, nc, 1, 0u, bseg.as<double>(), nullptr);
-    CLV_HIP(hipGetLastError());
+  rc = for_series_batches(bin.as<double>(), mn, n_series, 1, 0u, nullptr, [&](double* seg, int64_t s0, int64_t nc) {
     if (lds)
       hipLaunchKernelGGL(zscale_kernel<true>, dim3((unsigned)nc), dim3(RANK_THREADS), rank_lds_bytes(true, mn),
-                         nullptr, bseg.as<double>(), (double*)nullptr, (int)n_chains, n_draws, nc, s0, (int)folded,
-                         br.as<double>(), bz.as<double>());
+                         nullptr, seg, (double*)nullptr, (int)n_chains, n_draws, nc, s0, (int)folded, br.as<double>(),
+                         bz.as<double>());
     else
       hipLaunchKernelGGL(zscale_kernel<false>, dim3((unsigned)nc), dim3(RANK_THREADS), rank_lds_bytes(false, mn),
-                         nullptr, bseg.as<double>(), bscr.as<double>(), (int)n_chains, n_draws, nc, s0, (int)folded,
-                         br.as<double>(), bz.as<double>());
-    CLV_HIP(hipGetLastError());
-  }
+                         nullptr, seg, bscr.as<double>(), (int)n_chains, n_draws, nc, s0, (int)folded, br.as<double>(),
+                         bz.as<double>());
+  });
+  if (rc) return rc;
   CLV_HIP(hipMemcpy(ranks_out, br.p, sizeof(double) * (size_t)(n_series * S), hipMemcpyDeviceToHost));
   CLV_HIP(hipMemcpy(z_out, bz.p, sizeof(double) * (size_t)(n_series * S), hipMemcpyDeviceToHost));
   return CLV_OK;
@@ -780,41 +772,17 @@ int clv_diagnostics(int32_t device, const double* series, int32_t n_chains, int6
   if (period < 1 || period > 32) return fail(CLV_EINVAL, "period must be in 1..32");
   DeviceScope ds(device);
   DevBuf bin;
-  rc = upload(series, (size_t)n_chains * n_draws * n_series, bin);
-  if (rc) return rc;
+  if ((rc = upload(bin, series, (size_t)n_chains * n_draws * n_series, nullptr))) return rc;
   return diag_dev(bin.as<double>(), n_chains, n_draws, n_series, period, log_mask, out, nullptr);
 }
 
 int clv_diagnostics_sampler(clv_sampler* s, uint32_t log_mask, double* level1_out, double* level2_out) {
   if (!s) return fail(CLV_EINVAL, "null sampler");
   if (!level1_out && !level2_out) return fail(CLV_EINVAL, "null argument (no output asked for)");
-  const Geometry& g = s->g;
-  if (level1_out) {
-    const double* l1;
-    int64_t nd;
-    int32_t w;
-    int rc = sampler_l1(s, &l1, &nd, &w);
-    if (rc) return rc;
-    rc = check_series(g.n_chains, g.n_draws, g.n * w);
-    if (rc) return rc;
-    rc = diag_dev(l1, g.n_chains, g.n_draws, g.n * w, w, log_mask, level1_out, s->stream);
-    if (rc) return rc;
-  }
-  if (level2_out) {
-    int64_t stored = 0;
-    if (s->sweeps_done > g.burnin) stored = (s->sweeps_done - 1 - g.burnin) / g.thin + 1;
-    if (!s->d_level2 || std::min<int64_t>(stored, g.n_draws) < (int64_t)g.n_draws)
-      return fail(CLV_ESTATE, "the run has not stored all of its draws yet");
-    int rc = check_series(g.n_chains, g.n_draws, g.l2w);
-    if (rc) return rc;
-    CLV_HIP(hipSetDevice(s->device));
-    CLV_HIP(hipStreamSynchronize(s->stream));
-    rc = persist_flush(s);  // the last level-2 record may still be pending
-    if (rc) return rc;
-    rc = diag_dev(s->d_level2, g.n_chains, g.n_draws, g.l2w, 1, 0u, level2_out, s->stream);
-    if (rc) return rc;
-  }
-  return CLV_OK;
+  return sampler_series(s, log_mask, level1_out, level2_out,
+                        [&](const double* d_in, int64_t n_series, int period, uint32_t mask, double* out) {
+                          return diag_dev(d_in, s->g.n_chains, s->g.n_draws, n_series, period, mask, out, s->stream);
+                        });
 }
 
 int clv_autocorr(int32_t device, const double* series, int32_t n_chains, int64_t n_draws, int64_t n_series,
@@ -824,27 +792,21 @@ int clv_autocorr(int32_t device, const double* series, int32_t n_chains, int64_t
   if (rc) return rc;
   if (max_lag < 0 || max_lag > n_draws - 1) return fail(CLV_EINVAL, "max_lag must be in 0..n_draws-1");
   DeviceScope ds(device);
-  DevBuf bin, bseg, bout;
-  rc = upload(series, (size_t)n_chains * n_draws * n_series, bin);
-  if (rc) return rc;
+  DevBuf bin, bout;
+  if ((rc = upload(bin, series, (size_t)n_chains * n_draws * n_series, nullptr))) return rc;
   const int64_t mn = (int64_t)n_chains * n_draws;
-  const int64_t per_batch = batch_series(mn, n_series);
   const size_t n_out = (size_t)n_chains * n_series * ((size_t)max_lag + 1);
-  CLV_HIP(hipMalloc(&bseg.p, sizeof(double) * (size_t)(per_batch * mn)));
   CLV_HIP(hipMalloc(&bout.p, sizeof(double) * n_out));
   const bool lds = mn <= DIAG_LDS_ELEMS;
-  for (int64_t s0 = 0; s0 < n_series; s0 += per_batch) {
-    const int64_t nc = std::min<int64_t>(per_batch, n_series - s0);
-    launch_gather(bin.as<double>(), mn, n_series, s0, nc, 1, 0u, bseg.as<double>(), nullptr);
-    CLV_HIP(hipGetLastError());
+  rc = for_series_batches(bin.as<double>(), mn, n_series, 1, 0u, nullptr, [&](double* seg, int64_t s0, int64_t nc) {
     if (lds)
       hipLaunchKernelGGL(acf_kernel<true>, dim3((unsigned)nc), dim3(DIAG_LANES), sizeof(double) * (size_t)mn, nullptr,
-                         bseg.as<double>(), (int)n_chains, n_draws, nc, s0, n_series, (int)max_lag, bout.as<double>());
+                         seg, (int)n_chains, n_draws, nc, s0, n_series, (int)max_lag, bout.as<double>());
     else
-      hipLaunchKernelGGL(acf_kernel<false>, dim3((unsigned)nc), dim3(DIAG_LANES), 0, nullptr, bseg.as<double>(),
-                         (int)n_chains, n_draws, nc, s0, n_series, (int)max_lag, bout.as<double>());
-    CLV_HIP(hipGetLastError());
-  }
+      hipLaunchKernelGGL(acf_kernel<false>, dim3((unsigned)nc), dim3(DIAG_LANES), 0, nullptr, seg, (int)n_chains,
+                         n_draws, nc, s0, n_series, (int)max_lag, bout.as<double>());
+  });
+  if (rc) return rc;
   CLV_HIP(hipMemcpy(out, bout.p, sizeof(double) * n_out, hipMemcpyDeviceToHost));
   return CLV_OK;
 }

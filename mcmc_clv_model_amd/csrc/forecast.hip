@@ -43,7 +43,7 @@
 #include <limits>
 #include <string>
 
-#include "internal.h"
+#include "analysis_host.h"
 
 using namespace clv;
 
@@ -269,10 +269,8 @@ int fc_dev(FcArgs A, const int32_t* x_star, int64_t batch_customers, int32_t gri
   CLV_HIP(hipMalloc(&bacc.p, sizeof(double) * (size_t)per_batch * K));
   CLV_HIP(hipMalloc(&bo.p, sizeof(double) * (size_t)n * CLV_N_FC_STATS));
   if (out_pmf) CLV_HIP(hipMalloc(&bp.p, sizeof(double) * (size_t)n * K));
-  if (x_star) {
-    CLV_HIP(hipMalloc(&bxs.p, sizeof(int32_t) * (size_t)n));
-    CLV_HIP(hipMemcpyAsync(bxs.p, x_star, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, st));
-  }
+  int rc = upload(bxs, x_star, (size_t)n, st);
+  if (rc) return rc;
   A.xs = (const int32_t*)bxs.p;
   for (int64_t i0 = 0; i0 < n; i0 += per_batch) {
     const int64_t nc = std::min<int64_t>(per_batch, n - i0);
@@ -307,13 +305,9 @@ int fc_host(int32_t device, const double* level1, int64_t n_draws, int64_t n, in
   DeviceScope ds(device);
   FcArgs A = make_args(n_draws, n, width, T_star, k_max);
   DevBuf bl, btx, bT;
-  const size_t bytes = sizeof(double) * (size_t)n_draws * n * width;
-  CLV_HIP(hipMalloc(&bl.p, bytes));
-  CLV_HIP(hipMemcpyAsync(bl.p, level1, bytes, hipMemcpyHostToDevice, nullptr));
-  CLV_HIP(hipMalloc(&btx.p, sizeof(double) * (size_t)n));
-  CLV_HIP(hipMemcpyAsync(btx.p, t_x, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, nullptr));
-  CLV_HIP(hipMalloc(&bT.p, sizeof(double) * (size_t)n));
-  CLV_HIP(hipMemcpyAsync(bT.p, T_cal, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, nullptr));
+  if ((rc = upload(bl, level1, (size_t)n_draws * n * width, nullptr)) || (rc = upload(btx, t_x, (size_t)n, nullptr)) ||
+      (rc = upload(bT, T_cal, (size_t)n, nullptr)))
+    return rc;
   A.level1 = (const double*)bl.p;
   A.tx = (const double*)btx.p;
   A.T = (const double*)bT.p;

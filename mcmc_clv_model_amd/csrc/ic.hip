@@ -36,14 +36,13 @@
 // the lanes by the xor tree (offsets 32 ... 1).  No atomics; no sum depends on the grid or on the
 // batch.
 #include <hip/hip_runtime.h>
-#include <rocprim/device/device_segmented_radix_sort.hpp>
 
 #include <algorithm>
 #include <cmath>
 #include <limits>
 #include <string>
 
-#include "internal.h"
+#include "analysis_host.h"
 
 using namespace clv;
 
@@ -196,11 +195,6 @@ __global__ __launch_bounds__(IC_BLOCK) void ic_pass_kernel(IcArgs A, int64_t i0,
       if (bad) o[CLV_IC_ELPD_LOO] = o[CLV_IC_P_LOO] = o[CLV_IC_PARETO_K] = o[CLV_IC_TAIL_LEN] = nan;
     }
   }
-}
-
-__global__ void ic_offsets_kernel(int64_t nc, int64_t n_draws, uint32_t* off) {
-  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (c <= nc) off[c] = (uint32_t)(c * n_draws);
 }
 
 // The 64 lanes' values added (or their maximum taken) by the xor tree, offsets 32 ... 1: every lane
@@ -382,18 +376,13 @@ int ic_dev(IcArgs A, double reff, int64_t batch_keys, int32_t grid, double* out,
   const int64_t bk = batch_keys > 0 ? std::min(batch_keys, IC_BATCH_KEYS) : IC_BATCH_KEYS;
   const int64_t per_batch = std::min<int64_t>(std::max<int64_t>(1, bk / S / IC_BLOCK), nb) * IC_BLOCK;
   const int64_t nc_max = std::min<int64_t>(per_batch, n);
-  const size_t keys = (size_t)nc_max * S;
   const int64_t max_grid = grid > 0 ? grid : IC_MAX_GRID;
-  DevBuf bo, bseg, bsorted, boff, btmp;
+  DevBuf bo, bseg;
   CLV_HIP(hipMalloc(&bo.p, sizeof(double) * n * CLV_N_IC_STATS));
-  CLV_HIP(hipMalloc(&bseg.p, sizeof(double) * keys));
-  CLV_HIP(hipMalloc(&bsorted.p, sizeof(double) * keys));
-  CLV_HIP(hipMalloc(&boff.p, sizeof(uint32_t) * (nc_max + 1)));
-  size_t tmp_bytes = 0;
-  CLV_HIP(rocprim::segmented_radix_sort_keys((void*)nullptr, tmp_bytes, (const double*)bseg.p, (double*)bsorted.p,
-                                             (unsigned)keys, (unsigned)nc_max, (const uint32_t*)boff.p,
-                                             (const uint32_t*)boff.p + 1, 0, 64, st));
-  CLV_HIP(hipMalloc(&btmp.p, std::max<size_t>(tmp_bytes, 16)));
+  CLV_HIP(hipMalloc(&bseg.p, sizeof(double) * (size_t)nc_max * S));
+  SegSorter<double> sorter;
+  int rc = sorter.init(nc_max, S, st);
+  if (rc) return rc;
   double* dout = (double*)bo.p;
   const size_t fit_lds = sizeof(double) * (size_t)(M + 4 * IC_MAX_POINTS);
   for (int64_t i0 = 0; i0 < n; i0 += per_batch) {
@@ -402,15 +391,10 @@ int ic_dev(IcArgs A, double reff, int64_t batch_keys, int32_t grid, double* out,
     hipLaunchKernelGGL(ic_pass_kernel, dim3((unsigned)std::min<int64_t>(nblk, max_grid)), dim3(IC_BLOCK), 0, st, A, i0,
                        nc, (double*)bseg.p, dout, (double*)nullptr);
     CLV_HIP(hipGetLastError());
-    hipLaunchKernelGGL(ic_offsets_kernel, dim3((unsigned)((nc + 256) / 256)), dim3(256), 0, st, nc, S,
-                       (uint32_t*)boff.p);
-    CLV_HIP(hipGetLastError());
-    size_t tb = tmp_bytes;
-    CLV_HIP(rocprim::segmented_radix_sort_keys(btmp.p, tb, (const double*)bseg.p, (double*)bsorted.p,
-                                               (unsigned)(nc * S), (unsigned)nc, (const uint32_t*)boff.p,
-                                               (const uint32_t*)boff.p + 1, 0, 64, st));
-    hipLaunchKernelGGL(ic_fit_kernel, dim3((unsigned)std::min<int64_t>(nc, max_grid)), dim3(64), fit_lds, st,
-                       (const double*)bsorted.p, nc, S, M, i0, dout);
+    const double* sorted;
+    if ((rc = sorter.sort((const double*)bseg.p, nc, &sorted))) return rc;
+    hipLaunchKernelGGL(ic_fit_kernel, dim3((unsigned)std::min<int64_t>(nc, max_grid)), dim3(64), fit_lds, st, sorted,
+                       nc, S, M, i0, dout);
     CLV_HIP(hipGetLastError());
   }
   CLV_HIP(hipMemcpyAsync(out, dout, sizeof(double) * n * CLV_N_IC_STATS, hipMemcpyDeviceToHost, st));
@@ -426,19 +410,10 @@ struct Staged {
 int stage(IcArgs& A, Staged& b, const double* level1, const int32_t* x, const double* t_x, const double* T_cal,
           const double* log_s, hipStream_t st) {
   const size_t n = (size_t)A.n;
-  const size_t bytes = sizeof(double) * (size_t)A.n_draws * n * A.width;
-  CLV_HIP(hipMalloc(&b.l1.p, bytes));
-  CLV_HIP(hipMemcpyAsync(b.l1.p, level1, bytes, hipMemcpyHostToDevice, st));
-  CLV_HIP(hipMalloc(&b.x.p, sizeof(int32_t) * n));
-  CLV_HIP(hipMemcpyAsync(b.x.p, x, sizeof(int32_t) * n, hipMemcpyHostToDevice, st));
-  CLV_HIP(hipMalloc(&b.tx.p, sizeof(double) * n));
-  CLV_HIP(hipMemcpyAsync(b.tx.p, t_x, sizeof(double) * n, hipMemcpyHostToDevice, st));
-  CLV_HIP(hipMalloc(&b.T.p, sizeof(double) * n));
-  CLV_HIP(hipMemcpyAsync(b.T.p, T_cal, sizeof(double) * n, hipMemcpyHostToDevice, st));
-  if (log_s) {
-    CLV_HIP(hipMalloc(&b.logs.p, sizeof(double) * n));
-    CLV_HIP(hipMemcpyAsync(b.logs.p, log_s, sizeof(double) * n, hipMemcpyHostToDevice, st));
-  }
+  int rc;
+  if ((rc = upload(b.l1, level1, (size_t)A.n_draws * n * A.width, st)) || (rc = upload(b.x, x, n, st)) ||
+      (rc = upload(b.tx, t_x, n, st)) || (rc = upload(b.T, T_cal, n, st)) || (rc = upload(b.logs, log_s, n, st)))
+    return rc;
   A.level1 = (const double*)b.l1.p;
   A.x = (const int32_t*)b.x.p;
   A.tx = (const double*)b.tx.p;
@@ -522,9 +497,7 @@ int clv_psis_loo(int32_t device, const double* loglik, int64_t n_draws, int64_t 
   DeviceScope ds(device);
   IcArgs A = make_args(n_draws, n, 0, false, 1.0);
   DevBuf bl;
-  const size_t bytes = sizeof(double) * (size_t)n_draws * n;
-  CLV_HIP(hipMalloc(&bl.p, bytes));
-  CLV_HIP(hipMemcpyAsync(bl.p, loglik, bytes, hipMemcpyHostToDevice, nullptr));
+  if ((rc = upload(bl, loglik, (size_t)n_draws * n, nullptr))) return rc;
   A.ll = (const double*)bl.p;
   return ic_dev(A, reff, 0, 0, out, nullptr);
 }

@@ -1,4 +1,4 @@
-// Internal declarations shared by the C ABI translation units (capi.hip, analysis.hip):
+// Internal declarations shared by the library's translation units (every .hip file):
 // the sampler handle's layout and the error/allocation helpers.  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -50,6 +50,9 @@ void stream_clear_failed(DrawStreamState* st);  // after a full copy has repaire
 // The level-1 draws a CLV_SINK_FULL sampler holds in HBM after its run (analysis.hip): *l1 =
 // [chain * draw][n][width], *n_draws = chains x stored draws; CLV_ESTATE without them.
 int sampler_l1(clv_sampler* s, const double** l1, int64_t* n_draws, int32_t* width);
+// The level-2 records [chain][draw][l2w] of a run that has stored them all, the deferred last one
+// flushed (analysis.hip); CLV_ESTATE with the caller's message without them.
+int sampler_l2(clv_sampler* s, const double** l2, const char* not_stored);
 
 // Scoring customers outside the fit (kernels.hip; host side in score.hip).  launch_score_prepare:
 // level2 [n_rec][D K + D (D + 1) / 2] -> hyper [n_rec][HS] (cleared by the caller).  launch_score:
@@ -201,4 +204,15 @@ struct clv_sampler {
   double t_sweep_ms = 0.0, t_hyper_ms = 0.0;
   int64_t n_sweep_timed = 0, n_hyper_timed = 0;
 };
+
+namespace clv {
+
+// Draws per chain the run has stored so far: at most n_draws.
+inline int64_t stored_draws(const clv_sampler* s) {
+  if (s->sweeps_done <= s->g.burnin) return 0;
+  const int64_t k = (s->sweeps_done - 1 - s->g.burnin) / s->g.thin + 1;
+  return k < s->g.n_draws ? k : (int64_t)s->g.n_draws;
+}
+
+}  // namespace clv
 

@@ -29,9 +29,8 @@
 // customers in batches of at most LTV_BATCH_KEYS keys, whole 256-customer blocks); ltv_sd_kernel
 // forms the sd from the unsorted series (numpy's std: deviations from the mean, squares, sum in
 // draw order; one lane per series, the rows staged through LDS LTV_SD_TILE draws at a time) and
-// ltv_percentile_kernel numpy's 'linear' percentiles from the sorted one.  No atomics.
+// percentile_kernel numpy's 'linear' percentiles from the sorted one.  No atomics.
 #include <hip/hip_runtime.h>
-#include <rocprim/device/device_segmented_radix_sort.hpp>
 
 #include <algorithm>
 #include <cmath>
@@ -40,8 +39,7 @@
 #include <string>
 #include <vector>
 
-#include "internal.h"
-#include "percentile.h"
+#include "analysis_host.h"
 
 using namespace clv;
 
@@ -220,11 +218,6 @@ __global__ __launch_bounds__(LTV_BLOCK) void ltv_final_kernel(const double* part
   }
 }
 
-__global__ void ltv_offsets_kernel(int64_t nc, int64_t n_draws, uint32_t* off) {
-  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (c <= nc) off[c] = (uint32_t)(c * n_draws);
-}
-
 // sd (numpy's std, ddof 1) of the value series (blockIdx.y 0) and the residual series (1) of the
 // batch from the series in draw order and the mean already in out: one lane per series, one
 // wavefront per 64 customers.  A lane's series is a row of seg, so the 64 rows are read LTV_SD_TILE
@@ -270,18 +263,6 @@ __global__ __launch_bounds__(64) void ltv_sd_kernel(const double* seg_value, con
   if (live) o[1] = sqrt(acc / (double)(n_draws - 1));  // 0 / 0 = NaN at one draw, as numpy
 }
 
-// numpy's 'linear' 2.5 / 50 / 97.5 percentiles of the batch's sorted series: columns col0 + 2 .. + 4.
-__global__ __launch_bounds__(256) void ltv_percentile_kernel(const double* sorted, int64_t nc, int64_t n_draws,
-                                                             int64_t i0, int col0, double* out) {
-  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= nc) return;
-  double* o = out + (i0 + c) * CLV_N_LTV_STATS + col0;
-  const double* a = sorted + c * n_draws;
-  o[2] = np_percentile_sorted(a, n_draws, 2.5);
-  o[3] = np_percentile_sorted(a, n_draws, 50.0);
-  o[4] = np_percentile_sorted(a, n_draws, 97.5);
-}
-
 // Customers per batch: whole 256-customer blocks within LTV_BATCH_KEYS keys (at least one block);
 // CLV_LTV_BATCH (customers, rounded up to whole blocks) forces a smaller one — the tests' knob.
 int64_t batch_customers(int64_t n_draws) {
@@ -324,19 +305,15 @@ int ltv_dev(const double* l1, int64_t n_draws, int64_t n, int32_t width, const d
   const int64_t nb = (n + LTV_BLOCK - 1) / LTV_BLOCK;
   const int64_t per_batch = std::min<int64_t>(batch_customers(n_draws), nb * LTV_BLOCK);
   const size_t keys = (size_t)std::min<int64_t>(per_batch, n) * n_draws;
-  DevBuf bo, bd, bpart, bval, bres, bsorted, boff, btmp;
+  DevBuf bo, bd, bpart, bval, bres;
   CLV_HIP(hipMalloc(&bo.p, sizeof(double) * n * CLV_N_LTV_STATS));
   CLV_HIP(hipMalloc(&bd.p, sizeof(double) * n_draws * CLV_N_LTV_DRAW_STATS));
   CLV_HIP(hipMalloc(&bpart.p, sizeof(double) * CLV_N_LTV_DRAW_STATS * n_draws * nb));
   CLV_HIP(hipMalloc(&bval.p, sizeof(double) * keys));
   CLV_HIP(hipMalloc(&bres.p, sizeof(double) * keys));
-  CLV_HIP(hipMalloc(&bsorted.p, sizeof(double) * keys));
-  CLV_HIP(hipMalloc(&boff.p, sizeof(uint32_t) * (per_batch + 1)));
-  size_t tmp_bytes = 0;
-  CLV_HIP(rocprim::segmented_radix_sort_keys((void*)nullptr, tmp_bytes, (const double*)bval.p, (double*)bsorted.p,
-                                             (unsigned)keys, (unsigned)std::min<int64_t>(per_batch, n),
-                                             (const uint32_t*)boff.p, (const uint32_t*)boff.p + 1, 0, 64, st));
-  CLV_HIP(hipMalloc(&btmp.p, std::max<size_t>(tmp_bytes, 16)));
+  SegSorter<double> sorter;
+  int rc = sorter.init(std::min<int64_t>(per_batch, n), n_draws, st);
+  if (rc) return rc;
   double* dout = (double*)bo.p;
   for (int64_t i0 = 0; i0 < n; i0 += per_batch) {
     const int64_t nc = std::min<int64_t>(per_batch, n - i0);
@@ -344,22 +321,16 @@ int ltv_dev(const double* l1, int64_t n_draws, int64_t n, int32_t width, const d
     hipLaunchKernelGGL(ltv_pass_kernel, dim3((unsigned)std::min<int64_t>(nblk, LTV_MAX_GRID)), dim3(LTV_BLOCK), 0, st,
                        A, i0, nc, nb, (double*)bval.p, (double*)bres.p, (double*)bpart.p, dout);
     CLV_HIP(hipGetLastError());
-    hipLaunchKernelGGL(ltv_offsets_kernel, dim3((unsigned)((nc + 256) / 256)), dim3(256), 0, st, nc, n_draws,
-                       (uint32_t*)boff.p);
-    CLV_HIP(hipGetLastError());
     hipLaunchKernelGGL(ltv_sd_kernel, dim3((unsigned)((nc + 63) / 64), 2), dim3(64), 0, st, (const double*)bval.p,
                        (const double*)bres.p, nc, n_draws, i0, dout);
     CLV_HIP(hipGetLastError());
     const double* series[2] = {(const double*)bval.p, (const double*)bres.p};
     const int col0[2] = {CLV_LTV_VALUE_MEAN, CLV_LTV_RESIDUAL_MEAN};
-    for (int q = 0; q < 2; ++q) {
-      size_t tb = tmp_bytes;
-      CLV_HIP(rocprim::segmented_radix_sort_keys(btmp.p, tb, series[q], (double*)bsorted.p, (unsigned)(nc * n_draws),
-                                                 (unsigned)nc, (const uint32_t*)boff.p, (const uint32_t*)boff.p + 1,
-                                                 0, 64, st));
-      hipLaunchKernelGGL(ltv_percentile_kernel, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, st,
-                         (const double*)bsorted.p, nc, n_draws, i0, col0[q], dout);
-      CLV_HIP(hipGetLastError());
+    for (int q = 0; q < 2; ++q) {  // the 2.5 / 50 / 97.5 percentiles: columns col0 + 2 .. + 4
+      const PctCols pc{3, {2.5, 50.0, 97.5}, {col0[q] + 2, col0[q] + 3, col0[q] + 4}};
+      const double* sorted;
+      if ((rc = sorter.sort(series[q], nc, &sorted))) return rc;
+      if ((rc = launch_percentiles(sorted, nc, n_draws, pc, i0, CLV_N_LTV_STATS, dout, st))) return rc;
     }
   }
   hipLaunchKernelGGL(ltv_final_kernel, dim3((unsigned)std::min<int64_t>(n_draws, LTV_MAX_GRID), CLV_N_LTV_DRAW_STATS),
@@ -368,13 +339,6 @@ int ltv_dev(const double* l1, int64_t n_draws, int64_t n, int32_t width, const d
   CLV_HIP(hipMemcpyAsync(out_customers, dout, sizeof(double) * n * CLV_N_LTV_STATS, hipMemcpyDeviceToHost, st));
   CLV_HIP(hipMemcpyAsync(out_draws, bd.p, sizeof(double) * n_draws * CLV_N_LTV_DRAW_STATS, hipMemcpyDeviceToHost, st));
   CLV_HIP(hipStreamSynchronize(st));
-  return CLV_OK;
-}
-
-int stage_monetary(const double* monetary, int64_t n, DevBuf& buf, hipStream_t st) {
-  if (!monetary) return CLV_OK;
-  CLV_HIP(hipMalloc(&buf.p, sizeof(double) * n));
-  CLV_HIP(hipMemcpyAsync(buf.p, monetary, sizeof(double) * n, hipMemcpyHostToDevice, st));
   return CLV_OK;
 }
 
@@ -400,11 +364,7 @@ int clv_lifetime_value(int32_t device, const double* level1, int64_t n_draws, in
   if (!level1 || !out_customers || !out_draws) return fail(CLV_EINVAL, "null argument");
   DeviceScope ds(device);
   DevBuf b1, bm;
-  const size_t bytes = sizeof(double) * (size_t)n_draws * n * width;
-  CLV_HIP(hipMalloc(&b1.p, bytes));
-  CLV_HIP(hipMemcpyAsync(b1.p, level1, bytes, hipMemcpyHostToDevice, nullptr));
-  rc = stage_monetary(monetary, n, bm, nullptr);
-  if (rc) return rc;
+  if ((rc = upload(b1, level1, (size_t)n_draws * n * width, nullptr)) || (rc = upload(bm, monetary, n, nullptr))) return rc;
   return ltv_dev((const double*)b1.p, n_draws, n, width, (const double*)bm.p, delta, horizon, value_scale,
                  periods_per_year, out_customers, out_draws, nullptr);
 }
@@ -421,8 +381,7 @@ int clv_lifetime_value_sampler(clv_sampler* s, const double* monetary, double de
   if (rc) return rc;
   if (!out_customers || !out_draws) return fail(CLV_EINVAL, "null argument");
   DevBuf bm;
-  rc = stage_monetary(monetary, s->g.n, bm, s->stream);
-  if (rc) return rc;
+  if ((rc = upload(bm, monetary, s->g.n, s->stream))) return rc;
   return ltv_dev(l1, nd, s->g.n, w, (const double*)bm.p, delta, horizon, value_scale, periods_per_year,
                  out_customers, out_draws, s->stream);
 }

@@ -1,5 +1,5 @@
-// numpy's 'linear' percentile of a sorted segment, shared by the analysis kernels (analysis.hip,
-// ltv.hip).
+// numpy's 'linear' percentile of a sorted segment, for analysis_host.h's percentile_kernel (the
+// level-1 summary of analysis.hip and the lifetime value of ltv.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 

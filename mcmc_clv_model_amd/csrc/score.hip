@@ -6,7 +6,7 @@
 #include <cmath>
 #include <string>
 
-#include "internal.h"
+#include "analysis_host.h"
 
 using namespace clv;
 
@@ -103,18 +103,11 @@ int score_run(const ScoreCall& q, const double* d_level2, hipStream_t st) {
                                                     "sink=\"summary\" (CLV_SINK_SUMMARY) or score fewer customers per call"));
   }
   DevBuf bx, btx, bT, bcov, blogs, blam, bmu, blam_o, bmu_o, bhyper, bout;
-  auto up = [&](DevBuf& b, const void* src, size_t bytes) -> hipError_t {
-    hipError_t err = hipMalloc(&b.p, bytes);
-    if (err != hipSuccess) return err;
-    return hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, st);
-  };
-  CLV_HIP(up(bx, q.x, sizeof(int32_t) * n));
-  CLV_HIP(up(btx, q.t_x, sizeof(double) * n));
-  CLV_HIP(up(bT, q.T_cal, sizeof(double) * n));
-  if (q.cov) CLV_HIP(up(bcov, q.cov, sizeof(double) * (size_t)(q.K - 1) * n));
-  if (q.log_s) CLV_HIP(up(blogs, q.log_s, sizeof(double) * n));
-  CLV_HIP(up(blam, q.init_lam, sizeof(double) * cn));
-  CLV_HIP(up(bmu, q.init_mu, sizeof(double) * cn));
+  int rc;
+  if ((rc = upload(bx, q.x, n, st)) || (rc = upload(btx, q.t_x, n, st)) || (rc = upload(bT, q.T_cal, n, st)) ||
+      (rc = upload(bcov, q.cov, (size_t)(q.K - 1) * n, st)) || (rc = upload(blogs, q.log_s, n, st)) ||
+      (rc = upload(blam, q.init_lam, cn, st)) || (rc = upload(bmu, q.init_mu, cn, st)))
+    return rc;
   CLV_HIP(hipMalloc(&blam_o.p, sizeof(double) * cn));
   CLV_HIP(hipMalloc(&bmu_o.p, sizeof(double) * cn));
   CLV_HIP(hipMalloc(&bhyper.p, sizeof(double) * hyper_doubles));
@@ -194,10 +187,10 @@ int clv_debug_score_hyper(int32_t device, int32_t D, int32_t K, int64_t n_rec, c
   if (D == 3 && !(omega2 > 0.0 && std::isfinite(omega2))) return fail(CLV_EINVAL, "omega2 must be finite and > 0");
   DeviceScope ds(device);
   DevBuf bl2, bh;
-  const size_t in_bytes = sizeof(double) * (size_t)n_rec * (D * K + D * (D + 1) / 2), out_bytes = sizeof(double) * (size_t)n_rec * HS;
-  CLV_HIP(hipMalloc(&bl2.p, in_bytes));
+  const size_t out_bytes = sizeof(double) * (size_t)n_rec * HS;
+  int rc = upload(bl2, level2, (size_t)n_rec * (D * K + D * (D + 1) / 2), nullptr);
+  if (rc) return rc;
   CLV_HIP(hipMalloc(&bh.p, out_bytes));
-  CLV_HIP(hipMemcpyAsync(bl2.p, level2, in_bytes, hipMemcpyHostToDevice, nullptr));
   CLV_HIP(hipMemsetAsync(bh.p, 0, out_bytes, nullptr));
   CLV_HIP(launch_score_prepare(D, K, bl2.as<double>(), n_rec, D == 3 ? omega2 : 1.0, bh.as<double>(), nullptr));
   CLV_HIP(hipMemcpyAsync(out, bh.p, out_bytes, hipMemcpyDeviceToHost, nullptr));
@@ -219,9 +212,7 @@ int clv_score_customers(int32_t device, int32_t D, int32_t K, int32_t n_chains, 
   if (rc) return rc;
   DeviceScope ds(device);
   DevBuf bl2;
-  const size_t bytes = sizeof(double) * (size_t)n_chains * n_draws * (D * K + D * (D + 1) / 2);
-  CLV_HIP(hipMalloc(&bl2.p, bytes));
-  CLV_HIP(hipMemcpyAsync(bl2.p, level2, bytes, hipMemcpyHostToDevice, nullptr));
+  if ((rc = upload(bl2, level2, (size_t)n_chains * n_draws * (D * K + D * (D + 1) / 2), nullptr))) return rc;
   return score_run(q, bl2.as<double>(), nullptr);
 }
 
@@ -238,15 +229,9 @@ int clv_score_customers_sampler(clv_sampler* s, int64_t n, const int32_t* x, con
   int rc = score_check(q, nullptr);
   if (rc) return rc;
   if (s->replay) return fail(CLV_ESTATE, "scoring draws Philox variates: not for a replay-mode sampler");
-  int64_t stored = 0;
-  if (s->sweeps_done > g.burnin) stored = std::min<int64_t>((s->sweeps_done - 1 - g.burnin) / g.thin + 1, g.n_draws);
-  if (!s->d_level2 || stored < (int64_t)g.n_draws) return fail(CLV_ESTATE, "the run has not stored all of its level-2 records yet");
-  CLV_HIP(hipSetDevice(s->device));
-  CLV_HIP(hipStreamSynchronize(s->stream));
-  rc = persist_flush(s);  // the last level-2 record may still be pending
-  if (rc) return rc;
-  CLV_HIP(hipStreamSynchronize(s->stream));
-  return score_run(q, s->d_level2, s->stream);
+  const double* l2;
+  if ((rc = sampler_l2(s, &l2, "the run has not stored all of its level-2 records yet"))) return rc;
+  return score_run(q, l2, s->stream);
 }
 
 }  // extern "C"

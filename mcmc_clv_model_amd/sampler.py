@@ -702,24 +702,34 @@ def fit(p: Problem, *, mcmc: int, burnin: int, thin: int, chains: int, seed, tra
         s.close()
 
 
+def analysis_kwargs(name: str, value, draw_sink: str, allowed: tuple):
+    """The fit functions' keyword ``name`` (an analysis of the level-1 draws) as a dict of that
+    analysis's keywords, None when it is not asked for: None / False / True / a dict whose keys are
+    among ``allowed``, and the full draw sink."""
+    if value is None or value is False:
+        return None
+    if value is True:
+        kw = {}
+    elif isinstance(value, dict):
+        kw = dict(value)
+    else:
+        raise ValueError(f"{name} must be None, True or a dict of keywords (got {value!r})")
+    if draw_sink != "full":
+        raise ValueError(f"{name} needs draw_sink='full' (it is computed from the level-1 draws)")
+    bad = sorted(set(kw) - set(allowed))
+    if bad:
+        raise ValueError(f"{name} takes the keywords {allowed} (got {bad})")
+    return kw
+
+
 def lifetime_value_kwargs(lifetime_value, draw_sink: str):
     """The ``lifetime_value=`` keyword of the fit functions as analysis.lifetime_value's keywords
     (None: not asked for), validated before the run starts."""
-    if lifetime_value is None or lifetime_value is False:
+    kw = analysis_kwargs("lifetime_value", lifetime_value, draw_sink,
+                         ("discount_rate", "periods_per_year", "horizon", "monetary", "omega2"))
+    if kw is None:
         return None
-    if lifetime_value is True:
-        kw = {}
-    elif isinstance(lifetime_value, dict):
-        kw = dict(lifetime_value)
-    else:
-        raise ValueError(f"lifetime_value must be None, True or a dict of keywords (got {lifetime_value!r})")
-    if draw_sink != "full":
-        raise ValueError("lifetime_value needs draw_sink='full' (it is computed from the level-1 draws)")
     from . import analysis as A
-    allowed = ("discount_rate", "periods_per_year", "horizon", "monetary", "omega2")
-    bad = sorted(set(kw) - set(allowed))
-    if bad:
-        raise ValueError(f"lifetime_value takes the keywords {allowed} (got {bad})")
     A.ltv_params(kw.get("discount_rate", 0.15), kw.get("periods_per_year", 52.0), kw.get("horizon"),
                  kw.get("omega2", 0.0))
     return kw
@@ -728,22 +738,10 @@ def lifetime_value_kwargs(lifetime_value, draw_sink: str):
 def information_criteria_kwargs(information_criteria, draw_sink: str, D: int):
     """The ``information_criteria=`` keyword of the fit functions as analysis.information_criteria's
     keywords (None: not asked for), validated before the run starts."""
-    if information_criteria is None or information_criteria is False:
+    kw = analysis_kwargs("information_criteria", information_criteria, draw_sink, ("spend", "omega2", "reff"))
+    if kw is None:
         return None
-    if information_criteria is True:
-        kw = {}
-    elif isinstance(information_criteria, dict):
-        kw = dict(information_criteria)
-    else:
-        raise ValueError("information_criteria must be None, True or a dict of keywords "
-                         f"(got {information_criteria!r})")
-    if draw_sink != "full":
-        raise ValueError("information_criteria needs draw_sink='full' (it is computed from the level-1 draws)")
     from . import analysis as A
-    allowed = ("spend", "omega2", "reff")
-    bad = sorted(set(kw) - set(allowed))
-    if bad:
-        raise ValueError(f"information_criteria takes the keywords {allowed} (got {bad})")
     if kw.get("spend") and D != 3:
         raise ValueError("spend=True needs the trivariate model (D = 3)")
     A.ic_params(kw.get("spend", False), kw.get("omega2", 1.0 if kw.get("spend") else None), kw.get("reff", 1.0))
@@ -754,21 +752,10 @@ def forecast_kwargs(forecast, draw_sink: str, cbs=None, n=None):
     """The ``forecast=`` keyword of the fit functions as analysis.forecast's keywords (None: not asked
     for), validated before the run starts; an ``x_star`` given as a column name is taken from
     ``cbs`` (the drop-ins have one)."""
-    if forecast is None or forecast is False:
+    kw = analysis_kwargs("forecast", forecast, draw_sink, ("T_star", "x_star", "k_max", "pmf"))
+    if kw is None:
         return None
-    if forecast is True:
-        kw = {}
-    elif isinstance(forecast, dict):
-        kw = dict(forecast)
-    else:
-        raise ValueError(f"forecast must be None, True or a dict of keywords (got {forecast!r})")
-    if draw_sink != "full":
-        raise ValueError("forecast needs draw_sink='full' (it is computed from the level-1 draws)")
     from . import analysis as A
-    allowed = ("T_star", "x_star", "k_max", "pmf")
-    bad = sorted(set(kw) - set(allowed))
-    if bad:
-        raise ValueError(f"forecast takes the keywords {allowed} (got {bad})")
     par = A.forecast_params(kw.get("T_star", 39.0), kw.get("x_star"), kw.get("k_max"), kw.get("pmf", False), cbs, n)
     if "x_star" in kw and kw["x_star"] is not None:
         kw["x_star"] = par["x_star"]
