@@ -353,12 +353,22 @@ int clv_debug_persist_choice(int32_t D, int32_t K, int32_t n_chains, int64_t gri
  * point R (0, 8 or 12) between a relayed row's owner and its relay wavefront, as [begin, end):
  * out[8] = steps run by the owner, by the relay wavefront, steps whose variates the owner draws, the
  * relay wavefront draws.  S <= R (or R = 0) is not relayed: the owner has all of it.
+ * clv_debug_split_draw_plan: who draws the next sweep's variates in the relay instance at relay point R
+ * (8 or 12) and draw share 0..5 (CLV_SPLIT_RELAY_DRAW: 0 nothing in the relay wavefronts' idle gaps,
+ * 1 their own chunks after their row's reduction, 2 / 3 also one / two chunks of the rows on the
+ * owner's SIMD before the flag, 4 / 5 those one / two chunks alone; 4 is built by default, DESIGN.md §8
+ * round 9): out[row 0..5][chunk 0..4][4] = the wavefront that draws the chunk
+ * first, its slot (0 the hand-off window, 1 gap 1 before the flag, 2 gap 2 after the row's reduction),
+ * whether it is staged outside the pool, and the chunk's reader, which draws it in the window if the
+ * gap ended first.  share = -1: out[0] = the share the library was built with.
  * clv_debug_split_stamps (CLV_STAMPS build): out[workgroup][16], the relay wavefronts' flag-seen and
- * row-done times of the stamped sweep (rows 4, 5), then HW_ID of wavefronts 0..7 (bits 5:4: SIMD). */
+ * row-done times of the stamped sweep (rows 4, 5), then HW_ID of wavefronts 0..7 (bits 5:4: SIMD),
+ * then the end of the relay wavefronts' gap 1 (two words) and gap 2 (two words) in that sweep. */
 int clv_debug_split_fits(int32_t n_chains, int32_t nb, int32_t blocks_per_cu, int32_t n_cu);
 int clv_debug_split_choice(int32_t n_chains, int32_t nb, int32_t blocks_per_cu, int32_t n_cu);
 int clv_debug_split_layout(int32_t n_chains, int32_t nb, int32_t* out);
 int clv_debug_split_relay_plan(int32_t S, int32_t R, int32_t* out);
+int clv_debug_split_draw_plan(int32_t R, int32_t share, int32_t* out);
 int clv_debug_split_stamps(clv_sampler* s, uint64_t* out);
 
 /* ---- In-process multi-device runs (SURVEY.md §8b devices=, §8e) ----

@@ -126,6 +126,7 @@ def lib() -> ctypes.CDLL:
         "clv_debug_wg_stamps": (c_int32, [sp, POINTER(c_uint64)]),
         "clv_debug_split_stamps": (c_int32, [sp, POINTER(c_uint64)]),
         "clv_debug_split_relay_plan": (c_int32, [c_int32, c_int32, POINTER(c_int32)]),
+        "clv_debug_split_draw_plan": (c_int32, [c_int32, c_int32, POINTER(c_int32)]),
         "clv_debug_exp": (c_int32, [dp, c_int64, dp]),
         "clv_debug_log": (c_int32, [dp, c_int64, dp]),
         "clv_debug_mh_step": (c_int32, [c_int64, POINTER(c_int32), POINTER(c_uint8), dp, dp, dp, dp, dp,

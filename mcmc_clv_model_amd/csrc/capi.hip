@@ -1764,6 +1764,23 @@ int clv_debug_split_relay_plan(int32_t S, int32_t R, int32_t* out) {
   return CLV_OK;
 }
 
+int clv_debug_split_draw_plan(int32_t R, int32_t share, int32_t* out) {
+  if (!out || !(R == 8 || R == 12) || share < -1 || share >= SPLIT_DRAW_SHARES) return fail(CLV_EINVAL, "bad arguments");
+  if (share < 0) {  // the share this library's relay instance was built with
+    out[0] = SPLIT_RELAY_DRAW;
+    return CLV_OK;
+  }
+  constexpr int NQ = PRE_STEPS / 4;
+  for (int row = 0; row < SPLIT_CW; ++row) {
+    for (int q = 0; q < NQ; ++q) {
+      const SplitDrawSlot d = split_draw_plan(R, share, row, q);
+      const int32_t o[4] = {d.wave, d.slot, d.staged, d.reader};
+      std::copy(o, o + 4, out + (row * NQ + q) * 4);
+    }
+  }
+  return CLV_OK;
+}
+
 int clv_debug_split_layout(int32_t n_chains, int32_t nb, int32_t* out) {
   if (!out || n_chains < 1 || nb < 1 || nb > SPLIT_MAX_NB || n_chains >= (1 << 15)) return fail(CLV_EINVAL, "bad arguments");
   const std::vector<int32_t> m = persist_split_layout(n_chains, nb);

@@ -40,13 +40,61 @@ enum : int { WAIT_HYPER = 1, WAIT_BLOCKS = 2, WAIT_P2P_MAIL = 3, WAIT_FX_MAIL = 
 constexpr int SPLIT_RELAY_STEPS = CLV_SPLIT_RELAY_STEPS;
 static_assert(SPLIT_RELAY_STEPS == 0 || SPLIT_RELAY_STEPS == 8 || SPLIT_RELAY_STEPS == 12, "relay point: 8 or 12 steps");
 // Which wavefront of a relayed row runs which of the sweep's S MH steps, [begin, end) each: the
-// owner (wavefront 4 or 5) and the relay wavefront (6 or 7).  Each draws exactly the variates of the
-// steps it runs.  A sweep of S <= R steps (or R = 0) is not relayed: the owner runs all of it.
+// owner (wavefront 4 or 5) and the relay wavefront (6 or 7).  Each reads the pool columns of the steps
+// it runs, and draws them unless split_draw_plan (below) names an earlier drawer.  A sweep of S <= R
+// steps (or R = 0) is not relayed: the owner runs all of it.
 struct SplitRelayPlan {
   int own_begin, own_end, relay_begin, relay_end;
 };
 __host__ __device__ constexpr SplitRelayPlan split_relay_plan(int S, int R) {
   return SplitRelayPlan{0, (R > 0 && S > R) ? R : S, (R > 0 && S > R) ? R : S, S};
+}
+// Who draws sweep s + 1's variates of the relay instance, and when in sweep s.  split_relay_plan says
+// who *runs* (reads) a chunk; this table says who draws it.  Slots of a sweep, in time order:
+//   gap 1   the relay wavefront's idle time between the (beta, Sigma) barrier and its row's flag.  The
+//           readers still read sweep s's columns then, so what is drawn here is staged in an LDS
+//           buffer of its own and copied into the pool by the chunk's reader in the window.
+//   gap 2   the relay wavefront's idle time between its row's reduction and the reduction's barrier:
+//           its own columns, read for the last time in this sweep, so drawn straight into the pool.
+//   window  after the reduction's barrier (the only slot before this table existed).
+// A gap ends when the event it waits for arrives (the flag; the customer wavefronts' arrivals at the
+// barrier), so a gap chunk may stay undrawn: its fallback is always the window and its reader.
+// Share (CLV_SPLIT_RELAY_DRAW): 0 nothing in the gaps, 1 gap 2, 2 gap 2 and gap 1 with one chunk of
+// each helped row (0 and 4 by wavefront 6, 1 and 5 by wavefront 7), 3 the same with two chunks, 4 / 5
+// gap 1 alone with one / two chunks.  Gap 2 takes at most CLV_SPLIT_RELAY_GAP2_CHUNKS of the relay
+// wavefront's chunks and starts none once CLV_SPLIT_RELAY_GAP2_STOP of the six customer wavefronts are
+// at the reduction's barrier (a chunk begun is finished: the barrier waits for it).
+#ifndef CLV_SPLIT_RELAY_DRAW
+#define CLV_SPLIT_RELAY_DRAW 4
+#endif
+#ifndef CLV_SPLIT_RELAY_GAP2_CHUNKS
+#define CLV_SPLIT_RELAY_GAP2_CHUNKS 3
+#endif
+#ifndef CLV_SPLIT_RELAY_GAP2_STOP
+#define CLV_SPLIT_RELAY_GAP2_STOP 6
+#endif
+constexpr int SPLIT_RELAY_DRAW = CLV_SPLIT_RELAY_DRAW;
+constexpr int SPLIT_RELAY_GAP2_CHUNKS = CLV_SPLIT_RELAY_GAP2_CHUNKS;
+constexpr int SPLIT_RELAY_GAP2_STOP = CLV_SPLIT_RELAY_GAP2_STOP;
+constexpr int SPLIT_DRAW_SHARES = 6;
+static_assert(SPLIT_RELAY_DRAW >= 0 && SPLIT_RELAY_DRAW < SPLIT_DRAW_SHARES, "draw share: 0..5");
+static_assert(SPLIT_RELAY_GAP2_CHUNKS >= 1 && SPLIT_RELAY_GAP2_STOP >= 1 && SPLIT_RELAY_GAP2_STOP <= SPLIT_CW, "gap 2 limits");
+enum : int { DRAW_WINDOW = 0, DRAW_GAP1 = 1, DRAW_GAP2 = 2 };
+struct SplitDrawSlot {
+  int wave;    // the wavefront that draws the chunk first, if its slot lasts long enough
+  int slot;    // DRAW_WINDOW, DRAW_GAP1 or DRAW_GAP2
+  int staged;  // drawn into the staging buffer, not the pool (the reader copies it in the window)
+  int reader;  // the wavefront that runs the chunk's steps; draws it in the window if it is undrawn
+};
+__host__ __device__ constexpr int split_draw_gap1_chunks(int share) { return share >= 4 ? share - 3 : share >= 2 ? share - 1 : 0; }
+__host__ __device__ constexpr SplitDrawSlot split_draw_plan(int R, int share, int row, int chunk) {
+  const int qr = R / 4;  // first chunk of the relay wavefront (split_relay_plan: the cut is a whole chunk)
+  const int reader = (row >= 4 && chunk >= qr) ? row + 2 : row;
+  if (share >= 1 && share <= 3 && row >= 4 && chunk >= qr && chunk < qr + SPLIT_RELAY_GAP2_CHUNKS)
+    return SplitDrawSlot{row + 2, DRAW_GAP2, 0, reader};
+  if ((row & 3) < 2 && chunk < split_draw_gap1_chunks(share) && chunk < qr)
+    return SplitDrawSlot{6 + (row & 1), DRAW_GAP1, 1, reader};
+  return SplitDrawSlot{reader, DRAW_WINDOW, 0, reader};
 }
 
 // Doubles of peer-mail slots before the progress words.

@@ -382,12 +382,13 @@ __device__ __forceinline__ void wg_stamp(unsigned long long* st, int64_t wg, int
   } while (0)
 // split layout, after those records: 16 words per workgroup (clv_debug_split_stamps) — [0..3] the
 // relay wavefronts' flag-seen and row-done times of the stamped sweep (rows 4 and 5), [4..11] HW_ID
-// of wavefronts 0..7, once per launch (bits 5:4: the SIMD)
+// of wavefronts 0..7, once per launch (bits 5:4: the SIMD), [12..13] the end of the relay wavefronts'
+// gap 1 and [14..15] of their gap 2 in the stamped sweep (split_draw_plan)
 #define CLV_R_STAMP(a, wg, k, on)                                                                                       \
   do {                                                                                                                  \
     if ((on) && (a).stamps && (threadIdx.x & 63) == 0)                                                                  \
       (a).stamps[1024 * 8 + ((int64_t)(a).g.n_chains * ((a).g.nb_local + 1)) * 12 + (wg) * 16 + (k)] =                   \
-          (k) >= 4 ? __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11)) : __builtin_amdgcn_s_memrealtime();    \
+          (k) >= 4 && (k) < 12 ? __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11)) : __builtin_amdgcn_s_memrealtime(); \
   } while (0)
 #else
 #define CLV_R_STAMP(a, wg, k, on) ((void)0)
@@ -1642,6 +1643,47 @@ __device__ __forceinline__ void mh_pre_variates_range(const SlotPhilox& ph, int 
     }
   }
 }
+// The same in the relay instance's hand-off window, when part of the chunks may already have been
+// drawn in one of the relay wavefronts' gaps (split_draw_plan): bit q of `have` (wave-uniform) says
+// that chunk q was.  COPY: it lies in the staging column sv (NS columns, chunks from 0) and is copied
+// into the pool here, by its reader; else it is in the pool already.  The others are drawn.
+template <int Q0, int Q1, int NT, int NS, bool COPY>
+__device__ __forceinline__ void mh_pre_variates_window(const SlotPhilox& ph, int S_, const PreVariates& v,
+                                                       const PreVariates& sv, uint32_t have) {
+  constexpr int MC = MH_CHUNK_STEPS;
+  const int S = opaque_uniform(S_);
+  have = (uint32_t)__builtin_amdgcn_readfirstlane((int)have);
+#pragma unroll
+  for (int q = Q0; q < Q1; ++q) {
+    if (q * MC < S) {  // wave-uniform
+      if ((have >> q) & 1u) {
+        if constexpr (COPY) {
+          float2 t[MC];
+          float u[MC];
+#pragma unroll
+          for (int st = 0; st < MC; ++st) {
+            t[st] = sv.t[(q * MC + st) * NS + sv.lane];
+            u[st] = sv.u[(q * MC + st) * NS + sv.lane];
+          }
+#pragma unroll
+          for (int st = 0; st < MC; ++st) {
+            v.t[(q * MC + st) * NT + v.lane] = t[st];
+            v.u[(q * MC + st) * NT + v.lane] = u[st];
+          }
+        }
+      } else {
+        float tl[MC], tm[MC], lu[MC];
+        mh_chunk_variates(ph, (uint32_t)q, tl, tm, lu);
+#pragma unroll
+        for (int st = 0; st < MC; ++st) {
+          const int k = q * MC + st;
+          v.t[k * NT + v.lane] = make_float2(tl[st], tm[st]);
+          v.u[k * NT + v.lane] = k < S ? lu[st] : __builtin_inff();  // as mh_pre_variates pads
+        }
+      }
+    }
+  }
+}
 template <int Q0, int Q1, int NT, int D, int K, bool CL>
 __device__ __forceinline__ void mh_run_pre_range(Cust<D, K, CL>& cu, const PreVariates& v, double s00, double s11, int S,
                                                  const double* exp_tab) {
@@ -2830,9 +2872,15 @@ constexpr int SPLIT_PRE_LDS_BYTES = PRE_STEPS * SPLIT_NC * 12;
 // with the sweep's number in the launch; wavefront 6 / 7 (lane l for the owner's lane l) polls the
 // flag, runs steps R .. S-1, cust_finish and the row's reduction into red[4] / red[5], and writes
 // lambda, mu and their logs back for the owner to read after the reduction's barrier.  That flag is
-// the only wait added; the barriers are the helper instance's.  Every wavefront draws the variates
-// of exactly the steps it runs (split_relay_plan) into pool columns only it reads, in the hand-off
-// window after the reduction's barrier (the prologue for the launch's first sweep).  The relayed
+// the only wait added; the barriers are the helper instance's.  A pool column is read by one
+// wavefront only (split_relay_plan).  Who draws it, and when, is split_draw_plan's: by default its
+// reader in the hand-off window after the reduction's barrier (the prologue for the launch's first
+// sweep); the relay wavefronts also draw in their two idle gaps, at priority 0 — before the flag the
+// first chunks of the two rows on the owner's SIMD, staged in LDS and copied into the pool by their
+// readers in the window; after the row's reduction their own chunks, straight into the pool.  A gap
+// ends with the event after it (the flag, the customer wavefronts' arrival count — both read between
+// chunks, never waited for); what it left is drawn in the window by the reader (a mask per row).
+// Same Philox slots of the customer's own global index, so the same bits whoever draws.  The relayed
 // row's chain is the longest serial path of the workgroup: both its wavefronts run it at priority 3.
 // LDS order within a sweep: record and flag after the (beta, Sigma) barrier, the values written back
 // before the reduction's barrier and read after it, so neither is overwritten while still unread.
@@ -2865,6 +2913,35 @@ __device__ __forceinline__ void split_relay_sweeps(const SweepArgs& a_launch, in
   const bool first_wait = a_launch.pend_in != nullptr;
   if (tid < 2) relay_flag[tid] = 0;
   if (tid == 2) relay_abort = 0;
+  // Drawing ahead in the relay wavefronts' gaps (split_draw_plan; nothing of it at share 0).
+  constexpr int DRAW = SPLIT_RELAY_DRAW;
+  constexpr int HC1 = split_draw_gap1_chunks(DRAW);  // gap-1 chunks of each helped row
+  constexpr bool GAP2 = split_draw_plan(R, DRAW, 4, QR).slot == DRAW_GAP2;
+  static_assert(HC1 <= QR, "gap 1 draws owner chunks only");
+  static_assert(HC1 == 0 || (split_draw_plan(R, DRAW, 0, HC1 - 1).wave == SPLIT_CW && split_draw_plan(R, DRAW, 4, HC1 - 1).wave == SPLIT_CW &&
+                             split_draw_plan(R, DRAW, 1, HC1 - 1).wave == SPLIT_CW + 1 && split_draw_plan(R, DRAW, 5, HC1 - 1).wave == SPLIT_CW + 1 &&
+                             split_draw_plan(R, DRAW, 0, HC1).slot == DRAW_WINDOW && split_draw_plan(R, DRAW, 2, 0).slot == DRAW_WINDOW),
+                "gap 1: the first HC1 chunks of rows 0 and 4 by wavefront 6, of rows 1 and 5 by wavefront 7");
+  static_assert(GAP2 == (split_draw_plan(R, DRAW, 5, QR).slot == DRAW_GAP2) && split_draw_plan(R, DRAW, 4, QR - 1).slot != DRAW_GAP2,
+                "gap 2: the relay wavefront's own chunks, the same of rows 4 and 5");
+  constexpr int STAGE_STEPS = (HC1 > 0 ? HC1 : 1) * MC;  // steps of a staged row
+  // staged rows 0, 1, 4, 5 -> 0, 1, 2, 3: [row][step][lane] float2, then the same of float
+  float2* stage_t = nullptr;
+  float* stage_u = nullptr;
+  uint32_t* relay_drawn = nullptr;   // [4] per staged row: bit q = chunk q is in the staging buffer
+  uint32_t* relay_arrive = nullptr;  // customer wavefronts arrived at the reduction's barrier, all sweeps so far
+  if constexpr (HC1 > 0) {
+    __shared__ __attribute__((aligned(16))) char stage[4 * STAGE_STEPS * 64 * 12];
+    __shared__ uint32_t drawn[4];
+    stage_t = (float2*)stage;
+    stage_u = (float*)(stage + 4 * STAGE_STEPS * 64 * 8);
+    relay_drawn = drawn;
+  }
+  if constexpr (GAP2) {
+    __shared__ uint32_t arrive;
+    relay_arrive = &arrive;
+    if (tid == 3) arrive = 0;
+  }
 
   if (wave >= SPLIT_CW) {
     // ================= relay wavefronts =================
@@ -2896,6 +2973,47 @@ __device__ __forceinline__ void split_relay_sweeps(const SweepArgs& a_launch, in
       const int64_t s = uniform64(s_first + it);
       const bool stored = is_stored(s, g);
       const uint32_t tag = (uint32_t)it + 1u;
+      const bool ahead = it + 1 < n_sweeps;
+      if constexpr (HC1 > 0) {
+        // gap 1: until the row's flag is up, the first chunks of sweep s + 1 for the two rows on the
+        // owner's SIMD (rw and 4 + rw), staged; looked at between chunks, never waited for
+        if (ahead) {
+          const int S = opaque_uniform(g.S);
+          uint32_t have[2] = {0u, 0u};
+          bool go = true;
+#pragma unroll
+          for (int q = 0; q < HC1; ++q) {
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+              if (q * MC < S) {  // wave-uniform
+                if (go)
+                  go = (uint32_t)__builtin_amdgcn_readfirstlane(
+                           (int)__hip_atomic_load(&relay_flag[rw], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) != tag;
+                if (go) {
+                  const int64_t i = (int64_t)p * SPLIT_NC + (rw + 4 * t) * 64 + (tid & 63);
+                  if (i < g.n) {
+                    const SlotPhilox ph(k0, k1, (uint32_t)(g.shard_begin + i), (uint32_t)(s + 1));
+                    float tl[MC], tm[MC], lu[MC];
+                    mh_chunk_variates(ph, (uint32_t)q, tl, tm, lu);
+                    const int col = ((2 * t + rw) * STAGE_STEPS + q * MC) * 64 + (tid & 63);
+#pragma unroll
+                    for (int st = 0; st < MC; ++st) {
+                      stage_t[col + st * 64] = make_float2(tl[st], tm[st]);
+                      stage_u[col + st * 64] = q * MC + st < S ? lu[st] : __builtin_inff();  // as mh_pre_variates pads
+                    }
+                  }
+                  have[t] |= 1u << q;
+                }
+              }
+            }
+          }
+          if ((tid & 63) == 0) {  // read by the rows' wavefronts after the reduction's barrier
+            relay_drawn[rw] = have[0];
+            relay_drawn[2 + rw] = have[1];
+          }
+        }
+        CLV_R_STAMP(a, wgi, 12 + rw, it == it_stamp);  // (diagnostic build) end of gap 1
+      }
       bool seen = true;
       {  // the row's flag (bounded like every wait here; an expired or abandoned wait ends the launch
          // for the whole workgroup after the reduction's barrier)
@@ -2945,11 +3063,52 @@ __device__ __forceinline__ void split_relay_sweeps(const SweepArgs& a_launch, in
       }
       wave_reduce_gen_row<NS, SWEEP_REDUCE_CHUNK>(st, red[4 + rw]);  // the owner's lane order
       CLV_R_STAMP(a, wgi, 2 * rw + 1, it == it_stamp);  // (diagnostic build) row done
-      __syncthreads();  // the reduction's barrier
-      __builtin_amdgcn_s_setprio(0);
-      if (relay_abort) return;
-      if (cu.active && it + 1 < n_sweeps)
-        mh_pre_variates_range<QR, NQ, SPLIT_NC>(SlotPhilox(k0, k1, cu.gi, (uint32_t)(s + 1)), g.S, pv);
+      if constexpr (GAP2) {
+        // gap 2: this wavefront has read its columns for the last time in sweep s, so sweep s + 1's go
+        // straight into them, chunk by chunk until the six customer wavefronts are at the barrier
+        // (their count is read, not waited for: the barrier is late by one chunk's draw at most)
+        uint32_t have = 0u;
+        if (ahead) {
+          __builtin_amdgcn_s_setprio(0);
+          const int S = opaque_uniform(g.S);
+          const SlotPhilox ph(k0, k1, cu.gi, (uint32_t)(s + 1));
+          bool go = true;
+#pragma unroll
+          for (int q = QR; q < NQ; ++q) {
+            if (split_draw_plan(R, DRAW, 4, q).slot == DRAW_GAP2 && q * MC < S) {  // wave-uniform
+              if (go)  // (sweeps before this one: SPLIT_CW arrivals each)
+                go = (int32_t)((uint32_t)__builtin_amdgcn_readfirstlane(
+                                   (int)__hip_atomic_load(relay_arrive, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) -
+                               ((tag - 1u) * (uint32_t)SPLIT_CW + (uint32_t)SPLIT_RELAY_GAP2_STOP)) < 0;
+              if (go) {
+                if (cu.active) {
+                  float tl[MC], tm[MC], lu[MC];
+                  mh_chunk_variates(ph, (uint32_t)q, tl, tm, lu);
+#pragma unroll
+                  for (int st = 0; st < MC; ++st) {
+                    const int k = q * MC + st;
+                    pv.t[k * SPLIT_NC + pv.lane] = make_float2(tl[st], tm[st]);
+                    pv.u[k * SPLIT_NC + pv.lane] = k < S ? lu[st] : __builtin_inff();  // as mh_pre_variates pads
+                  }
+                }
+                have |= 1u << q;
+              }
+            }
+          }
+        }
+        CLV_R_STAMP(a, wgi, 14 + rw, it == it_stamp);  // (diagnostic build) end of gap 2
+        __syncthreads();  // the reduction's barrier
+        __builtin_amdgcn_s_setprio(0);
+        if (relay_abort) return;
+        if (cu.active && ahead)  // what gap 2 left
+          mh_pre_variates_window<QR, NQ, SPLIT_NC, SPLIT_NC, false>(SlotPhilox(k0, k1, cu.gi, (uint32_t)(s + 1)), g.S, pv, pv, have);
+      } else {
+        __syncthreads();  // the reduction's barrier
+        __builtin_amdgcn_s_setprio(0);
+        if (relay_abort) return;
+        if (cu.active && ahead)
+          mh_pre_variates_range<QR, NQ, SPLIT_NC>(SlotPhilox(k0, k1, cu.gi, (uint32_t)(s + 1)), g.S, pv);
+      }
     }
     return;
   }
@@ -3046,6 +3205,9 @@ __device__ __forceinline__ void split_relay_sweeps(const SweepArgs& a_launch, in
       CLV_P_STAMP(a.stamps, wgi, 4, stp);
       wave_reduce_gen<NS, SWEEP_REDUCE_CHUNK>(st, red);
     }
+    if constexpr (GAP2) {  // arrived: the relay wavefronts stop drawing in gap 2 once all six have
+      if ((tid & 63) == 0) __hip_atomic_fetch_add(relay_arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
     __syncthreads();
     if (relay_abort) return;
     {  // the workgroup's records, as the helper instance writes them
@@ -3089,7 +3251,18 @@ __device__ __forceinline__ void split_relay_sweeps(const SweepArgs& a_launch, in
       if (it + 1 < n_sweeps) {
         cust_ztau<D, K, false>(cu, a, s + 1, k0, k1, nullptr, exp_tab);
         const SlotPhilox ph(k0, k1, cu.gi, (uint32_t)(s + 1));
-        mh_pre_variates_range<0, QR, SPLIT_NC>(ph, g.S, pv);
+        if constexpr (HC1 > 0) {
+          // the chunks gap 1 drew for this row (0, 1, 4, 5) are copied from the staging buffer, the
+          // others drawn here as before; wavefronts 2 and 3 have none staged
+          const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+          const int sr = 2 * (w >> 2) + (w & 1);  // the staged row
+          const uint32_t have = (w & 3) < 2 ? relay_drawn[sr] : 0u;
+          const PreVariates sv{stage_t + sr * STAGE_STEPS * 64, stage_u + sr * STAGE_STEPS * 64, tid & 63};
+          mh_pre_variates_window<0, HC1, SPLIT_NC, 64, true>(ph, g.S, pv, sv, have);
+          mh_pre_variates_range<HC1, QR, SPLIT_NC>(ph, g.S, pv);
+        } else {
+          mh_pre_variates_range<0, QR, SPLIT_NC>(ph, g.S, pv);
+        }
         if (!relayed) mh_pre_variates_range<QR, NQ, SPLIT_NC>(ph, g.S, pv);
       }
     }

@@ -13,6 +13,6 @@ if [ "$3" = capi ]; then cp $C/kernels.o $R/build/$1/kernels.o; else
 fi
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -Wno-unused-variable -Wno-bitwise-instead-of-logical \
   -ffp-contract=off $2 -c $C/capi.hip -o $R/build/$1/capi.o
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $R/build/$1/kernels.o $R/build/$1/capi.o $C/analysis.o $C/elog.o $C/group.o \
-  $C/drawstream.o $C/probe.o -lpthread -o $R/build/$1/libclvmcmc.so
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $R/build/$1/kernels.o $R/build/$1/capi.o $C/analysis.o $C/diag.o $C/elog.o $C/group.o \
+  $C/drawstream.o $C/probe.o $C/pnbd.o $C/ltv.o $C/ic.o $C/score.o $C/forecast.o -lpthread -o $R/build/$1/libclvmcmc.so
 echo built build/$1/libclvmcmc.so

@@ -92,6 +92,12 @@ def main(workload="c2", sweeps=1500):
                 rel = dict(flag4=rs[on, 0] - R, done4=rs[on, 1] - R, flag5=rs[on, 2] - R, done5=rs[on, 3] - R)
                 print("    relay wavefronts, from the publish (median/max us): " +
                       "  ".join(f"{n} {np.median(v) * us:5.2f}/{v.max() * us:5.2f}" for n, v in rel.items()))
+            gs = sp[c, :nb, 12:16]  # ends of the relay wavefronts' gap 1 / gap 2 (drawing ahead; 0: not built in)
+            for k, n in enumerate(("gap1end6", "gap1end7", "gap2end6", "gap2end7")):
+                m = gs[:, k] > 0
+                if m.any():
+                    v = gs[m, k] - R
+                    print(f"    {n} (median/max us): {np.median(v) * us:5.2f}/{v.max() * us:5.2f}")
         print(f"    last partial issued {(cust[:, 5].max() - R) * us:6.2f}  tail: variates {(tail[1] - tail[0]) * us:5.2f}"
               f"  partials seen {(tail[2] - R) * us:6.2f}  draw {(tail[3] - tail[2]) * us:5.2f} (reduce {(tail[6] - tail[2]) * us:4.2f}"
               f" algebra {(tail[7] - tail[6]) * us:4.2f} finalize {(tail[3] - tail[7]) * us:4.2f})"
