@@ -14,6 +14,8 @@ Fixtures written:
   envelope_*.npz             G3: per-customer posterior summaries over M independent reference chains
                              (abe subset: c1/bi K=2/tri K=3; full CDNOW: c2 and c3 at reduced length)
   oracle_pin_full.json       the bitwise oracle-vs-reference checks on the full CDNOW c2/c3 inputs
+  oracle_pin_edge.json       the same on the edge frames (tests/helpers.edge_cbs: capped tau exponents, tau
+                             below t_x, T == t_x, states at the +-70 clip), non-finite values counted
   published_table3.json      abe_replication.xlsx "Table 3" (published loose pins)
   oracle_pin.json            the bitwise oracle-vs-reference checks that passed
   analysis_abe400.npz        row f: the reference's analysis helpers (draw_future_transactions bi/tri,
@@ -466,6 +468,39 @@ def write_envelope_synth(rbi, rtri, M=16, burnin=1000, mcmc=1000):
         json.dump(dict(reference=REF, checks=pins), f, indent=1)
 
 
+def write_edge_pin(rbi, rtri):
+    """The oracle against the reference, bitwise, on the frames of philox_sweep_ref.EDGE_CASES (2 chains x
+    4 sweeps, every sweep stored, each case's own seed and MH step count): customers far from CDNOW,
+    where the reference caps tau's exponents at 700 (tau = 700 / ml, below t_x, when both are capped),
+    draws alive for certain at T == t_x and carries states at the +-70 clip.  Non-finite values would be
+    part of the comparison (bit patterns) and are counted in the fixture; the reference raises on none
+    of the archetypes."""
+    from tests import philox_sweep_ref as M
+    pins = []
+    for name, case in M.EDGE_CASES.items():
+        df = M.case_frame(case)
+        kind = "bi" if case["D"] == 2 else "tri"
+        kw = dict(mcmc=4, burnin=0, thin=1, chains=2, seed=case["seed"], trace=0, n_mh_steps=case["S"])
+        fn_r = rbi.mcmc_draw_parameters if kind == "bi" else rtri.mcmc_draw_parameters_rfm_m
+        fn_o = orc.mcmc_draw_parameters if kind == "bi" else orc.mcmc_draw_parameters_rfm_m
+        with np.errstate(all="ignore"):
+            ref, ora = fn_r(df, case["covs"], **kw), fn_o(df, case["covs"], **kw)
+        ok = bitwise_equal(ref, ora)
+        l1 = np.stack(ref["level_1"])
+        tau_lt_tx = int(((l1[..., 3] == 0) & (l1[..., 2] < df["t_x"].to_numpy())).sum())
+        nonfinite = int(sum((~np.isfinite(np.stack(ref[k]))).sum() for k in ("level_1", "level_2"))
+                        + (not np.isfinite(ref["log_likelihood"])))
+        pins.append(dict(case=name, kind=kind, n=len(df), covariates=case["covs"], sha256=frame_sha256(df), **kw,
+                         nonfinite_values=nonfinite, churned_tau_below_t_x=tau_lt_tx,
+                         lambda_range=[float(l1[..., 0].min()), float(l1[..., 0].max())],
+                         mu_range=[float(l1[..., 1].min()), float(l1[..., 1].max())], bitwise=ok))
+        print("pinned edge", name, ok, "non-finite", nonfinite, "churned tau < t_x", tau_lt_tx)
+        if not ok:
+            raise SystemExit(f"oracle is NOT bitwise equal to the reference on {name}; refusing to write the fixture")
+    with open(os.path.join(HERE, "oracle_pin_edge.json"), "w") as f:
+        json.dump(dict(numpy=np.__version__, pandas=pd.__version__, checks=pins), f, indent=1)
+
+
 # ---------------------------------------------------------------------------------------------
 def read_xlsx_sheets(path):
     ns = {"m": "http://schemas.openxmlformats.org/spreadsheetml/2006/main"}
@@ -708,7 +743,7 @@ def main():
              ("formulas", lambda: write_formulas(rbi, rtri)), ("replay", lambda: write_replay(rbi, rtri, set(a.replay_names.split(",")) if a.replay_names else None)),
              ("published", write_published), ("analysis", lambda: write_analysis(rbi, rtri)),
              ("dataprep", lambda: write_dataprep(rbi)), ("generator_replay", lambda: write_generator_replay(rbi)),
-             ("elog_cases", write_elog_cases)]
+             ("elog_cases", write_elog_cases), ("edge_pin", lambda: write_edge_pin(rbi, rtri))]
     if not a.skip_envelope:
         steps.append(("envelope", write_envelope))
         steps.append(("envelope_full", lambda: write_envelope_full(rbi, rtri)))

@@ -33,6 +33,39 @@ def cdnow_tiled(n: int) -> pd.DataFrame:
     return df.iloc[np.arange(n) % len(df)].copy().reset_index(drop=True)
 
 
+EDGE_T = (0.01, 1.0, 39.0, 520.0, 3650.0)
+EDGE_X = (50, 400, 2000, 20000)
+EDGE_LOG_S = (-12.0, 0.0, 14.0)
+
+
+def edge_archetypes():
+    """(x, t_x, T_cal) of the edge frame: for every span T no purchase at all, one purchase at T (alive for
+    certain), at T (1 - 2^-40), at 1e-9 T, three by T / 2; then heavy buyers on a weekly and a daily
+    clock.  41 rows, no random numbers."""
+    rows = []
+    for T in EDGE_T:
+        rows += [(0, 0.0, T), (1, T, T), (1, T * (1.0 - 2.0 ** -40), T), (1, 1e-9 * T, T), (3, T / 2, T)]
+    for x in EDGE_X:
+        rows += [(x, 38.9, 39.0), (x, 20.0, 39.0), (x, 3649.0, 3650.0), (x, 0.5, 39.0)]
+    return rows
+
+
+def edge_cbs(n: int) -> pd.DataFrame:
+    """The edge archetypes taken cyclically up to n (as cdnow_tiled): customers far from CDNOW — daily
+    units, long histories, heavy buyers, spans of 0 and of 2^-40 T.  ``sales`` is set so that log_s, derived
+    as cdnow() derives it, cycles through -12, 0 and +14 along the frame and is 0 where x = 0 (no sales)."""
+    rows = edge_archetypes()
+    a = [rows[i % len(rows)] for i in range(n)]
+    x = np.array([r[0] for r in a], dtype=np.int64)
+    target = np.array([EDGE_LOG_S[i % len(EDGE_LOG_S)] for i in range(n)])
+    df = pd.DataFrame(dict(x=x, t_x=np.array([r[1] for r in a], dtype=np.float64),
+                           T_cal=np.array([r[2] for r in a], dtype=np.float64),
+                           sales=np.where(x == 0, 0.0, (x + 1) * np.exp(target))))
+    with np.errstate(divide="ignore"):
+        df["log_s"] = np.log(df["sales"] / (df["x"] + 1)).replace(-np.inf, 0.0).fillna(0.0)
+    return df
+
+
 def with_covariates(df: pd.DataFrame, n_cov: int, seed: int = 4242) -> pd.DataFrame:
     """c1..c{n_cov}: U(-1,1) covariate columns (the c4/c5 covariate model) added to a CBS."""
     df = df.copy()

@@ -73,23 +73,29 @@ def tau_atol(lam, mu):
 # ---------------------------------------------------------------------------------------------
 # level 1
 # ---------------------------------------------------------------------------------------------
-def draw_z_tau(t_x, T_cal, lam, mu, u_z, u_tau, e_alive, swap_tau_branch=False):
+def draw_z_tau(t_x, T_cal, lam, mu, u_z, u_tau, e_alive, swap_tau_branch=False, no_cap700=False, swap_span=False):
     """bi:193-227 with the sweep's Philox variates: z = u_z < P(alive); tau = T + E / mu (alive, E =
     -log U' of the SLOT_ZTAU words (z, w)) or the truncated-exponential inverse CDF at U of the same
     words (churned).  Returns (z, tau, relative margin of the z decision).
-    ``swap_tau_branch`` (power checks only): each branch's formula on the other branch's lanes."""
+    Power checks only: ``swap_tau_branch`` puts each branch's formula on the other branch's lanes;
+    ``no_cap700`` leaves min(700, .) out of tau's exponents (bi:223); ``swap_span`` forms P(alive)'s
+    exponential from ml (t_x - T) instead of ml (T - t_x)."""
     ml = mu + lam
-    with np.errstate(under="ignore"):
-        e = np.exp(-(ml * (T_cal - t_x)))
+    with np.errstate(under="ignore", over="ignore"):
+        e = np.exp(-(ml * ((t_x - T_cal) if swap_span else (T_cal - t_x))))
     a = ml * e
     b = a + mu * (1.0 - e)
-    z = u_z < a / b
+    with np.errstate(invalid="ignore", divide="ignore"):
+        z = u_z < a / b
     lhs = u_z * b
     with np.errstate(invalid="ignore", divide="ignore"):
         margin = np.abs(lhs - a) / (lhs + a)   # both sides carry a few ulp of their own size
     margin = np.where(np.isfinite(margin), margin, 0.0)
-    with np.errstate(under="ignore"):
-        churned = orc.tau_churned(t_x, T_cal, ml, u_tau)
+    with np.errstate(under="ignore", divide="ignore"):
+        if no_cap700:
+            churned = -np.log((1 - u_tau) * np.exp(-(ml * t_x)) + u_tau * np.exp(-(ml * T_cal))) / ml
+        else:
+            churned = orc.tau_churned(t_x, T_cal, ml, u_tau)
     alive = T_cal + (1.0 / mu) * e_alive
     tau = np.where(z != bool(swap_tau_branch), alive, churned)
     return z, tau, margin
@@ -111,10 +117,11 @@ def lp_magnitude(x, w, mv, P, ll, lm, pl, pm):
             + quad(ll, lm) + quad(pl, pm) + np.abs(mv).sum(1) ** 2 * pmax + 1.0)
 
 
-def mh_steps(x, T_cal, z, tau, mv, P, s00, s11, ll, lm, t_l, t_m, log2_u, stages=None):
+def mh_steps(x, T_cal, z, tau, mv, P, s00, s11, ll, lm, t_l, t_m, log2_u, stages=None, clip=CLIP):
     """bi:312-335 for S = len(t_l) steps from (ll, lm): proposal ll + Sigma[0,0] t (variance as the
     scale, quirk Q2) clipped to [-70, 70]; accept iff pm <= 5 and lp' - lp > ln2 log2 U (false on NaN;
-    any finite lp' from lp = -inf).  Returns (ll, lm, cur, margin, hit_clip, hit_cap)."""
+    any finite lp' from lp = -inf).  Returns (ll, lm, cur, margin, hit_clip, hit_cap).
+    ``clip`` (power checks only): another clip than the reference's 70."""
     n = ll.shape[0]
     ll, lm = ll.copy(), lm.copy()
     w = np.where(z, T_cal, tau)
@@ -128,9 +135,9 @@ def mh_steps(x, T_cal, z, tau, mv, P, s00, s11, ll, lm, t_l, t_m, log2_u, stages
     for j in range(len(t_l)):
         raw_l = ll + s00 * t_l[j].astype(np.float64)
         raw_m = lm + s11 * t_m[j].astype(np.float64)
-        pl = np.clip(raw_l, -CLIP, CLIP)
-        pm = np.clip(raw_m, -CLIP, CLIP)
-        hit_clip |= (np.abs(raw_l) >= CLIP) | (np.abs(raw_m) >= CLIP)
+        pl = np.clip(raw_l, -clip, clip)
+        pm = np.clip(raw_m, -clip, clip)
+        hit_clip |= (np.abs(raw_l) >= clip) | (np.abs(raw_m) >= clip)
         with np.errstate(invalid="ignore", over="ignore"):
             plp = orc.log_posterior(pl, pm, xf, zf, T_cal, tau, mv, P)
             thr = LN2 * log2_u[j].astype(np.float64)
@@ -160,24 +167,26 @@ class _One:
 
 
 def sweep_level1(x, t_x, T_cal, X, lam, mu, beta, Sigma, var, log_s=None, omega2=None,
-                 swap_tau_branch=False, stages=False):
+                 swap_tau_branch=False, stages=False, no_cap700=False, swap_span=False, clip=CLIP):
     """One chain, one sweep's level-1 half (bi:388-396; tri:511-526) from the state (lam, mu) entering
     it, the (beta K x D, Sigma D x D) its MH uses, and its variates ``var``: u_z, u_tau, e_alive (n),
     t_l / t_m / log2_u (S x n, the device's fp32 values or the oracle's), eta_z (n, D = 3).
     Returns a dict: z, tau, lam, mu, ll, lm, (eta, leta), lik (the likelihood term, bi:415-427),
     margin (the smallest of margin_z, margin_mh) and hit_clip / hit_cap flags; ``stages=True`` adds
-    the per-step proposals and log posteriors under "steps" and the coefficients mv, P."""
+    the per-step proposals and log posteriors under "steps" and the coefficients mv, P.
+    ``no_cap700``, ``swap_span``, ``clip``: the power checks' wrong models (draw_z_tau, mh_steps)."""
     lam = np.asarray(lam, dtype=np.float64)
     mu = np.asarray(mu, dtype=np.float64)
     beta = np.asarray(beta, dtype=np.float64)
     Sigma = np.asarray(Sigma, dtype=np.float64)
-    z, tau, margin_z = draw_z_tau(t_x, T_cal, lam, mu, var["u_z"], var["u_tau"], var["e_alive"], swap_tau_branch)
+    z, tau, margin_z = draw_z_tau(t_x, T_cal, lam, mu, var["u_z"], var["u_tau"], var["e_alive"], swap_tau_branch,
+                                   no_cap700, swap_span)
     mv = X @ beta
     P = inv_sigma_block(Sigma)
     steps = [] if stages else None
     ll, lm, cur, margin_mh, hit_clip, hit_cap = mh_steps(
         x, T_cal, z, tau, mv, P, Sigma[0, 0], Sigma[1, 1], np.log(lam), np.log(mu),
-        var["t_l"], var["t_m"], var["log2_u"], steps)
+        var["t_l"], var["t_m"], var["log2_u"], steps, clip)
     out = dict(z=z, tau=tau, ll=ll, lm=lm, lam=np.exp(ll), mu=np.exp(lm), cur=cur, margin_z=margin_z,
                margin_mh=margin_mh, margin=np.minimum(margin_z, margin_mh), hit_clip=hit_clip, hit_cap=hit_cap)
     if Sigma.shape[0] == 3:
@@ -433,13 +442,60 @@ SPLIT_GRID_CASES = {
                                "block 64 row 3": _rows(64, 3)}, 42, data="full", covs=["first_sales_scaled"],
                               chains=4, S=20),
 }
-ALL_CASES = {**CASES, **INSTANCE_CASES, **GRID_CASES, **SPLIT_INSTANCE_CASES, **SPLIT_GRID_CASES}
+
+
+# ---------------------------------------------------------------------------------------------
+# customers far from CDNOW (tests/helpers.edge_cbs; tests/test_gpu_edge_sweep.py): daily units, heavy
+# buyers, long histories, spans of 0 and of 2^-40 T.  N = 385: two blocks and two split workgroups, the
+# second of either with one live lane; S = 13: a partial last MH chunk.  Every sweep is stored.
+# ---------------------------------------------------------------------------------------------
+def _edge_case(D, K, n, S, chains, seed, drive):
+    sweeps = sum(a[1] for a in drive if a[0] == "run")
+    return dict(D=D, covs=[f"c{k}" for k in range(1, K)], data=("edge", n, K - 1), S=S, chains=chains, chain_first=0,
+                seed=seed, burnin=0, mcmc=sweeps, thin=1, drive=drive)
+
+
+EDGE_CASES = {
+    "e_bi1": _edge_case(2, 1, 385, 20, 2, 20250101, [("run", 4), ("state",), ("run", 4)]),
+    "e_bi2": _edge_case(2, 2, 385, 13, 1, 20250102, [("run", 6)]),
+    "e_tri1": _edge_case(3, 1, 257, 20, 2, 20250103, [("run", 6)]),
+}
+# What the edge frame is for, per (chain, sweep, customer) lane, from the state (lambda, mu) entering the
+# sweep, ml = lambda + mu: a churned draw with ml t_x >= 700 / with ml T >= 700 (tau's exponents on the
+# cap, bi:223); ml (T - t_x) > 700 (P(alive)'s exponential on the kernel's cap); T == t_x (P(alive) = 1);
+# a churned tau below t_x (both exponents capped: tau = 700 / ml, as the reference gives it); a state at
+# +-70 after the sweep (a clipped proposal accepted and carried).  |log eta| > 70 is not among them: the
+# conjugate draw's mean lies between the prior mean and log_s (|log_s| <= 14) and its standard deviation
+# is below sqrt(omega2) ~ 11, so no frame within the prior reaches it — the kernel's |xe| <= 700 guard
+# is exercised on its taken side only.
+EDGE_EVENTS = ("cap_tx", "cap_T", "zz700", "span0", "tau_lt_tx", "clip_state")
+CDNOW_EVENTS = COVERAGE_EVENTS
+COVERAGE_EVENTS = CDNOW_EVENTS + EDGE_EVENTS
+# near_T (a churned tau in the last 5% of [t_x, T]) is neither required nor forbidden: at these rates a
+# churned tau sits at t_x, and the model's free runs show 0, 0 and 5 such lanes — the CDNOW cases hold it
+EDGE_UNASSERTED = ("near_T",)
+EDGE_COVERAGE = {name: tuple(e for e in COVERAGE_EVENTS if e not in EDGE_UNASSERTED) for name in EDGE_CASES}
+EDGE_MIN_LANES = 10    # every event of EDGE_COVERAGE on at least this many lanes of a case's run
+
+
+def edge_events(mp, lam, mu, z, tau, lam_after, mu_after):
+    """Masks of EDGE_EVENTS for one (chain, sweep): (lam, mu) the state entering it, (z, tau) its draw,
+    (lam_after, mu_after) the state it leaves (at the clip if within 1e-9 of +-70 on the log scale)."""
+    ml = lam + mu
+    churned = ~np.asarray(z, dtype=bool)
+    at_clip = lambda v: np.abs(np.abs(np.log(v)) - CLIP) < 1e-9  # noqa: E731
+    return dict(cap_tx=churned & (ml * mp.t_x >= 700.0), cap_T=churned & (ml * mp.T_cal >= 700.0),
+                zz700=ml * (mp.T_cal - mp.t_x) > 700.0, span0=mp.T_cal == mp.t_x,
+                tau_lt_tx=churned & (tau < mp.t_x), clip_state=at_clip(lam_after) | at_clip(mu_after))
+
+
+ALL_CASES = {**CASES, **INSTANCE_CASES, **GRID_CASES, **SPLIT_INSTANCE_CASES, **SPLIT_GRID_CASES, **EDGE_CASES}
 
 
 def case_frame(case):
-    from tests.helpers import cdnow, cdnow_tiled, with_covariates
+    from tests.helpers import cdnow, cdnow_tiled, edge_cbs, with_covariates
     name, n, n_cov = case["data"]
-    df = cdnow_tiled(n) if name == "tiled" else cdnow(name, n)
+    df = edge_cbs(n) if name == "edge" else cdnow_tiled(n) if name == "tiled" else cdnow(name, n)
     return with_covariates(df, n_cov) if n_cov else df
 
 

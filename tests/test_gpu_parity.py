@@ -566,7 +566,9 @@ def test_sharded_sampler_rccl_matches_fused(L, graph_chunk):
 def test_device_fast_exp_accuracy(L):
     """exp_fast (csrc/fastmath.h), used by the Philox-mode MH step on arguments clipped to
     [-70, 70] (bi:323): <= 2 ulp from the correctly rounded exp (numpy's exp is within 1 ulp of
-    it, so the test allows 3 ulp against numpy) over the whole range and near 0."""
+    it, so the test allows 3 ulp against numpy) over the whole range and near 0.  The same bound over
+    the range fastmath.h claims, |x| <= 700, which draw_z, draw_tau (exponents capped at 700, bi:223)
+    and the eta draw call it on, with the caps and the clip themselves and their neighbours."""
     rng = np.random.default_rng(3)
     x = np.concatenate([rng.uniform(-70, 70, 200_000), rng.uniform(-1e-3, 1e-3, 20_000),
                         np.array([-70.0, 70.0, 0.0, -0.0, 1e-300, np.log(2) / 128, -np.log(2) / 128])])
@@ -576,6 +578,15 @@ def test_device_fast_exp_accuracy(L):
     ulp = np.abs(out - ref) / np.spacing(ref)
     assert ulp.max() <= 3.0, ulp.max()
     assert np.mean(out == ref) > 0.6
+    e = 70.0 + 2.0 ** -40
+    xw = np.concatenate([np.random.default_rng(4).uniform(-700, 700, 200_000),
+                         np.array([-700.0, 700.0, -70.0, 70.0, -e, e])])
+    outw = np.zeros_like(xw)
+    assert L.clv_debug_exp(_dp(xw), xw.size, _dp(outw)) == 0
+    refw = np.exp(xw)
+    ulpw = np.abs(outw - refw) / np.spacing(refw)
+    print(f"exp_fast on [-700, 700]: largest deviation {ulpw.max():.2f} ulp, at the listed points {ulpw[-6:]}")
+    assert np.isfinite(outw).all() and ulpw.max() <= 3.0, (ulpw.max(), xw[ulpw.argmax()])
 
 
 @pytest.mark.parametrize("packed", [0, 1])

@@ -187,17 +187,23 @@ class Device:
 
 
 def _close(got, ref, atol=0.0):
-    return np.abs(got - ref) <= M.RTOL * np.abs(ref) + atol
+    """Within RTOL (+ atol) of a finite model value; a non-finite one (a power check's wrong model) is
+    matched by the same value only."""
+    with np.errstate(invalid="ignore"):
+        return np.where(np.isfinite(ref), np.abs(got - ref) <= M.RTOL * np.abs(ref) + atol, got == ref)
 
 
 def compare(dev, chains, var_of=None, swap_t=False, swap_tau_branch=False, l2_sweep_shift=0, beta_slot_shift=0,
-            l1_cache=None, drop=None, level2=True):
+            l1_cache=None, drop=None, level2=True, model_kw=None, on_sweep=None):
     """Model against device over the given chains.  Returns dict(fail (chain, customer) mask, l2_fail, ll_fail,
     lanes, set_aside, n_l1, n_l2, dev_* largest relative deviations, edge counts).
     ``l1_cache``: a dict that keeps the level-1 model's results per (chain, sweep) between calls with the
     same level-1 inputs; ``drop`` (power checks only): a customer mask left out of the level-2 model's X
     and Y (nu_n unchanged) and of the log-likelihood's sum (still divided by N) — what a unit missing
-    from the reduction would give; ``level2=False`` skips the level-2 comparison."""
+    from the reduction would give; ``level2=False`` skips the level-2 comparison; ``model_kw`` (power
+    checks only): further wrong-model switches of philox_sweep_ref.sweep_level1; ``on_sweep``: called for
+    every stored sweep compared with (chain, sweep, entering state, leaving state, the stored level-1 row,
+    the model's result, the lanes that differ before the margin gate, the lanes whose margin is clear)."""
     mp, case = dev.mp, dev.case
     D, N = mp.D, mp.N
     var_of = var_of or (lambda c, s: dev.var[c, s])
@@ -218,7 +224,7 @@ def compare(dev, chains, var_of=None, swap_t=False, swap_tau_branch=False, l2_sw
                     v["t_l"], v["t_m"] = v["t_m"], v["t_l"]
                 r = l1_cache.get((c, s)) if l1_cache is not None else None
                 if r is None:
-                    r = mp.level1(ent[0], ent[1], hyp[0], hyp[1], v, swap_tau_branch=swap_tau_branch)
+                    r = mp.level1(ent[0], ent[1], hyp[0], hyp[1], v, swap_tau_branch=swap_tau_branch, **(model_kw or {}))
                     if l1_cache is not None:
                         l1_cache[c, s] = r
                 clear = r["margin"] > M.RTOL
@@ -252,6 +258,8 @@ def compare(dev, chains, var_of=None, swap_t=False, swap_tau_branch=False, l2_sw
                     out["loglik"] = max(out["loglik"], abs(ll_dev - ll_ref) / abs(ll_ref))
                     if not _close(ll_dev, ll_ref):
                         out["ll_fail"] = True
+                    if on_sweep is not None:
+                        on_sweep(c, s, ent, post, row, r, bad, clear)
                 out["fail"][ci] |= bad & clear
         # level 2: the draw belonging to sweep hs, from the device's own level-1 output
         for hs in range(1, dev.T + 2 if level2 else 0):

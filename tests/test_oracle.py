@@ -17,6 +17,17 @@ def test_oracle_pin_record_all_bitwise():
     for name in ("oracle_pin_full.json", "oracle_pin_synth.json"):  # c2/c3 inputs; c4/c5-model inputs
         pin = json.load(open(os.path.join(GOLDEN, name)))
         assert pin["checks"] and all(c["bitwise"] for c in pin["checks"])
+    # the edge frames (tests/helpers.edge_cbs): the reference raises on no archetype and yields no
+    # non-finite value in 2 chains x 4 sweeps; where both of tau's exponents sit on the 700 cap it
+    # gives tau = 700 / ml below t_x, and the oracle reproduces every bit
+    from tests import philox_sweep_ref as M
+    pin = json.load(open(os.path.join(GOLDEN, "oracle_pin_edge.json")))
+    assert [c["case"] for c in pin["checks"]] == list(M.EDGE_CASES)
+    for c in pin["checks"]:
+        case = M.EDGE_CASES[c["case"]]
+        assert c["bitwise"] and (c["chains"], c["mcmc"], c["burnin"], c["thin"]) == (2, 4, 0, 1)
+        assert (c["n"], c["seed"], c["n_mh_steps"], c["covariates"]) == (case["data"][1], case["seed"], case["S"], case["covs"])
+        assert c["nonfinite_values"] == 0 and c["churned_tau_below_t_x"] >= 100
 
 
 @pytest.mark.parametrize("name", ["synth_bi_k5", "synth_tri_k9"])

@@ -13,7 +13,10 @@ here it is pinned to the REFERENCE, never to the kernel:
   margin is below the comparison tolerance stays within the 0.1% cap, and the level-2 tolerance
   covers ten times the measured sensitivity to the variates' and Y's documented uncertainty — for
   CASES, INSTANCE_CASES (every compiled (D, K)), GRID_CASES (up to 153,345 customers) and the split
-  layout's SPLIT_INSTANCE_CASES / SPLIT_GRID_CASES (tests/test_gpu_split_model.py) alike;
+  layout's SPLIT_INSTANCE_CASES / SPLIT_GRID_CASES (tests/test_gpu_split_model.py) alike, and for
+  EDGE_CASES (tests/test_gpu_edge_sweep.py: customers far from CDNOW), which also run whole against the
+  oracle's chain and whose coverage table (EDGE_COVERAGE: capped tau exponents, tau below t_x, T == t_x,
+  states carried at the +-70 clip) is exactly what the model's free run produces, no lane borderline;
 * the coverage events the GPU module asserts per instance case (INSTANCE_COVERAGE) are exactly those
   the model's free run of the case produces;
 * at the grid cases' sizes numpy's mean of the likelihood terms and the exactly rounded one differ by
@@ -177,10 +180,13 @@ class PhiloxStream(orc.Stream):
         return self._rec("mvn_noise", np.linalg.cholesky(cov) @ self.hv[2])
 
 
-@pytest.mark.parametrize("name", ["bi_k2", "tri_k3"])
+@pytest.mark.parametrize("name", ["bi_k2", "tri_k3"] + list(M.EDGE_CASES))
 def test_model_sweep_agrees_with_the_oracle_chain(name):
-    case = M.CASES[name]
-    mp = M.ModelProblem(M.case_frame(case).iloc[:300], case["covs"], case["D"])
+    """The edge cases run whole (385 / 257 customers): the oracle's chain passes through the capped tau
+    exponents, tau = 700 / ml below t_x, T == t_x and states carried at the +-70 clip, and the model
+    must follow it there to the same tolerances."""
+    case = M.ALL_CASES[name]
+    mp = M.ModelProblem(M.case_frame(case).iloc[:None if name in M.EDGE_CASES else 300], case["covs"], case["D"])
     seed, chain, S, T = case["seed"], 1, case["S"], 3
     free = {s: (r, l2) for s, r, l2 in M.model_chain(mp, seed, chain, T, S)}
     st = PhiloxStream(mp, seed, chain, S, {s: free[s][0]["z"] for s in free})
@@ -236,11 +242,17 @@ def free_runs():
     return _FreeRuns()
 
 
-def coverage_of(mp, chains):
-    """Lanes of each coverage event (philox_sweep_ref.COVERAGE_EVENTS) over a case's free run."""
-    n = dict.fromkeys(M.COVERAGE_EVENTS, 0)
+def coverage_of(mp, chains, edge=False):
+    """Lanes of each coverage event (philox_sweep_ref.COVERAGE_EVENTS) over a case's free run;
+    ``edge``: the events of EDGE_EVENTS too (counted for the edge cases only)."""
+    n = dict.fromkeys(M.COVERAGE_EVENTS if edge else M.CDNOW_EVENTS, 0)
     for runs in chains.values():
+        lam, mu = mp.lam0, mp.mu0
         for s, r, _ in runs:
+            if edge:
+                for k, v in M.edge_events(mp, lam, mu, r["z"], r["tau"], r["lam"], r["mu"]).items():
+                    n[k] += int(v.sum())
+                lam, mu = r["lam"], r["mu"]
             edges = M.near_edges(mp, r["z"], r["tau"])
             n["x0"] += int(((mp.x == 0) & (mp.t_x == 0)).sum())
             n["near_tx"] += int(edges[0].sum())
@@ -267,14 +279,21 @@ def test_borderline_share_is_within_the_cap(free_runs, name):
     print(f"{name}: {lanes} lanes, borderline {border} ({100 * share:.4f}%), clip lanes {clip}, cap lanes {cap}, "
           f"churned tau near t_x {near_tx}, near T {near_T}, x = 0 customers {(mp.x == 0).sum()}")
     assert share <= M.BORDERLINE_CAP
-    assert (mp.x == 0).any() and near_tx > 0 and near_T > 0
+    # the edge frame's churned draws sit at t_x (ml (T - t_x) is large): its own coverage table is
+    # asserted by test_edge_coverage_table_is_what_the_model_produces
+    assert (mp.x == 0).any() and near_tx > 0 and (near_T > 0 or name in M.EDGE_CASES)
+    if name in M.EDGE_CASES:  # measured: no lane of 6,160 / 2,310 / 3,084 is borderline
+        assert border == 0
 
 
 @pytest.mark.parametrize("name", list(M.ALL_CASES))
 def test_level2_tolerance_covers_the_measured_sensitivity(free_runs, name):
     """The hyper variates are pinned to <= 1e-12 relative (test_device_hyper_variates_match_oracle) and
     the device's Y is the log-scale state, within 2 ulp of log of the stored natural-scale one: the
-    level-2 tolerance must cover ten times what those move beta and Sigma at this shape."""
+    level-2 tolerance must cover ten times what those move beta and Sigma at this shape.  The edge cases
+    (Sigma11 up to 1,200, Y from -70 to 19) measure 1.1e-12 (e_bi1), 2.4e-12 (e_bi2) and 3.1e-12
+    (e_tri1) beyond the absolute term: ten times that is 3.1e-11, so L2_RTOL = 1e-10 holds for them too
+    and they get no tolerance of their own."""
     mp, chains = free_runs[name]
     case = M.ALL_CASES[name]
     rng = np.random.default_rng(1)
@@ -309,6 +328,26 @@ def test_instance_coverage_table_is_what_the_model_produces(free_runs, name):
     n = coverage_of(mp, chains)
     print(f"{name}: N {mp.N}, coverage lanes " + ", ".join(f"{k} {v}" for k, v in n.items()))
     assert {k for k, v in n.items() if v > 0} == set(M.INSTANCE_COVERAGE[name])
+
+
+@pytest.mark.parametrize("name", list(M.EDGE_CASES))
+def test_edge_coverage_table_is_what_the_model_produces(free_runs, name):
+    """philox_sweep_ref.EDGE_COVERAGE, which tests/test_gpu_edge_sweep.py asserts per case from the
+    device's own state, is exactly the set of events the model's free run of the case produces, each
+    on at least EDGE_MIN_LANES lanes (near_T aside: EDGE_UNASSERTED).  Measured, (chain, sweep,
+    customer) lanes of e_bi1 (6,160) / e_bi2 (2,310) / e_tri1 (3,084): x0 784 / 294 / 396, near_tx
+    2544 / 970 / 1263, near_T 0 / 0 / 5, clip 5600 / 1997 / 2587, cap 6133 / 2281 / 2987, cap_tx 320 /
+    95 / 320, cap_T 1143 / 352 / 798, zz700 1078 / 339 / 734, span0 768 / 288 / 384, tau_lt_tx 320 /
+    95 / 320, clip_state 3212 / 979 / 289; lambda ends in [5.4e-8, 1.5e8] / [0.11, 31] / [6.1e-9,
+    2.5e10], mu in [e^-70, 141] / [e^-70, 134] / [e^-70, 126]; everything finite."""
+    mp, chains = free_runs[name]
+    n = coverage_of(mp, chains, edge=True)
+    print(f"{name}: N {mp.N}, coverage lanes " + ", ".join(f"{k} {v}" for k, v in n.items()))
+    for runs in chains.values():
+        for s, r, _ in runs:
+            assert all(np.isfinite(r[k]).all() for k in ("tau", "lam", "mu", "lik"))
+    assert {k for k, v in n.items() if v > 0} - set(M.EDGE_UNASSERTED) == set(M.EDGE_COVERAGE[name])
+    assert min(n[k] for k in M.EDGE_COVERAGE[name]) >= M.EDGE_MIN_LANES
 
 
 @pytest.mark.parametrize("name", list(M.GRID_CASES) + list(M.SPLIT_GRID_CASES))
