@@ -631,6 +631,70 @@ int clv_debug_forecast(int32_t device, const double* level1, int64_t n_draws, in
                        const int32_t* x, const double* t_x, const double* T_cal, double T_star, int32_t k_max,
                        const int32_t* x_star, int64_t batch_customers, int32_t grid, double* out, double* out_pmf);
 
+/* ---- Posterior predictive checks of the calibration data (csrc/ppc.hip) ----
+ * One replicate (x_rep, t_x_rep) of every customer's calibration data (x, t_x) on (0, T_cal] per
+ * stacked draw d (chains stacked chain-major).  Philox4x32-10 keyed by the seed (low word, high
+ * word), counter (customer_offset + i, d, slot, 5):
+ *   level 0 (customer):   lambda = level1[d][i][0], mu = level1[d][i][1].
+ *   level 1 (population): (beta, Sigma) = record d of level2 [n_draws][D K + D (D + 1) / 2] (the layout
+ *     of clv_score_customers; only beta's first two columns and Sigma's leading 2 x 2 block are read);
+ *     m_j = sum_k X_ik beta_kj, k ascending, X_i0 = 1; l00 = sqrt(S00), l10 = S01 / l00,
+ *     l11 = sqrt(S11 - l10^2); (n0, n1) = sqrt(-2 log(u53_open0(x, y))) (cos, sin)(2 pi u53(z, w)) of
+ *     slot 1; lambda = exp(m0 + l00 n0), mu = exp((m1 + l10 n0) + l11 n1).
+ *   slot 0: E = -log(u53_open0(x, y)), U = u53_open0(z, w); tau = E / mu (may be +inf);
+ *     alive = tau > T_cal; L = alive ? T_cal : tau.
+ *   x_rep = Poisson(lambda L) from slots 16 + attempt (0 for a mean <= 0 or NaN, inversion below 10,
+ *     PTRS from 10, at most 2^16 steps or attempts);
+ *   t_x_rep = x_rep > 0 ? L exp(log(U) / x_rep) : 0  (the largest of x_rep uniform times on (0, L]).
+ * No multiply-add is contracted.  out_customers [n][CLV_N_PPC_STATS], over the S = n_draws draws:
+ * x_rep_mean = (int64 sum) / S, p_x_lt = #(x_rep < x) / S, p_x_eq, p_zero = #(x_rep = 0) / S,
+ * tx_rep_mean = (the sum of t_x_rep in draw order from zero) / S, p_tx_le = #(t_x_rep <= t_x) / S,
+ * p_alive_rep = #(alive) / S.  out_draws_int [n_draws][k_hist + 1 + CLV_N_PPC_DRAW_INTS], over the
+ * customers: the histogram of x_rep in bins 0 ... k_hist - 1 and a last bin for x_rep >= k_hist, then
+ * sum x_rep, sum x_rep^2, max x_rep and the number alive (integer atomics: exact in any order).
+ * out_draws_f [n_draws][CLV_N_PPC_DRAW_FLOATS]: sum t_x_rep in the fixed order of
+ * clv_lifetime_value's per-draw sums (zero-padded 256-customer blocks by the 256-tree, the block
+ * partials by the same scheme): its bits depend neither on the grid nor on the customer batch.
+ * out_x_rep / out_tx_rep (either may be NULL) take the replicates [n_draws][n]; the other outputs have
+ * the same bits with and without them.  Host pointers; cov [(K - 1)][n] (NULL for K = 1).
+ * CLV_EINVAL before any device call: a null pointer, level not 0 or 1, n_draws or n < 1 or
+ * > 2^31 - 1, width not 4 or 5 (level 0), D not 2 or 3, K not 1 .. 9 or cov not matching K (level 1),
+ * k_hist not in [1, 4096], customer_offset < 0 or customer_offset + n beyond 32 bits. */
+enum {
+  CLV_PPC_X_REP_MEAN = 0, CLV_PPC_P_X_LT, CLV_PPC_P_X_EQ, CLV_PPC_P_ZERO, CLV_PPC_TX_REP_MEAN, CLV_PPC_P_TX_LE,
+  CLV_PPC_P_ALIVE_REP, CLV_N_PPC_STATS
+};
+enum { CLV_PPC_DRAW_SUM_X = 0, CLV_PPC_DRAW_SUM_X2, CLV_PPC_DRAW_MAX_X, CLV_PPC_DRAW_N_ALIVE, CLV_N_PPC_DRAW_INTS };
+enum { CLV_PPC_DRAW_SUM_TX = 0, CLV_N_PPC_DRAW_FLOATS };
+int clv_ppc(int32_t device, int32_t level,
+            const double* level1, int32_t width,          /* level 0; NULL at level 1 */
+            const double* level2, int32_t D, int32_t K,   /* level 1; NULL at level 0 */
+            const double* cov /* [K - 1][n] or NULL */,
+            int64_t n_draws, int64_t n, const int32_t* x, const double* t_x, const double* T_cal,
+            int32_t k_hist, uint64_t seed, int64_t customer_offset,
+            double* out_customers, int64_t* out_draws_int, double* out_draws_f,
+            int64_t* out_x_rep /* NULL or [n_draws][n] */, double* out_tx_rep /* NULL or [n_draws][n] */);
+/* From the draws (level 0) or the level-2 records (level 1) a CLV_SINK_FULL sampler holds in HBM and
+ * the data and covariates it was created with (CLV_ESTATE as clv_predict_sampler); the counter's
+ * customer word starts at the sampler's shard_begin.  The outputs on the host. */
+int clv_ppc_sampler(clv_sampler* s, int32_t level, int32_t k_hist, uint64_t seed, double* out_customers,
+                    int64_t* out_draws_int, double* out_draws_f, int64_t* out_x_rep, double* out_tx_rep);
+/* The limits of csrc/ppc.hip: out[0] customers per workgroup and per reduction block (256), out[1]
+ * the largest k_hist (4096), out[2] the t_x_rep doubles of one customer batch by default; of the
+ * replicate kernel the calling thread's last clv_ppc* call launched (-1 before one): out[3] VGPRs and
+ * out[4] scratch bytes per lane (hipFuncGetAttributes), out[5] the device time of the call's kernels
+ * in ns (events around them). */
+int clv_ppc_info(int64_t* out);
+/* clv_ppc with batch_customers (> 0: customers per batch, rounded up to whole 256-customer blocks)
+ * and grid (> 0: the most workgroups per launch) overridden: the tests' knobs, the results do not
+ * depend on them — nor on the environment variable CLV_PPC_ITEM_DRAWS (draws per work item of the
+ * replicate kernel, whole 32-draw chunks, default 32: the profile's knob, every clv_ppc* call). */
+int clv_debug_ppc(int32_t device, int32_t level, const double* level1, int32_t width, const double* level2,
+                  int32_t D, int32_t K, const double* cov, int64_t n_draws, int64_t n, const int32_t* x,
+                  const double* t_x, const double* T_cal, int32_t k_hist, uint64_t seed, int64_t customer_offset,
+                  double* out_customers, int64_t* out_draws_int, double* out_draws_f, int64_t* out_x_rep,
+                  double* out_tx_rep, int64_t batch_customers, int32_t grid);
+
 /* ---- Convergence diagnostics on device (csrc/diag.hip) ----
  * The reference checks convergence with ArviZ on its level-2 draws (bivariate/analysis_abe.py:
  * 651-706: az.summary, az.plot_autocorr).  Here a series is m chains x n draws (n >= 8) of one

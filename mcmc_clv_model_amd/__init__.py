@@ -29,6 +29,8 @@ enters each record distributed for the one before, a bias that shrinks as inner_
 The holdout forecast in closed form: every customer's posterior predictive distribution of the
 number of holdout purchases, marginal over z and tau, with its mean, P(alive), quantiles, log score,
 PIT and ranked probability score (forecast, forecast_pit, compare_forecasts, forecast_table).
+Posterior predictive checks of the calibration data, replicated per draw at the customer or at the
+population level: frequency histogram, p-values, per-customer PITs (posterior_predictive_check, ppc_pit).
 
 The per-sweep work runs in hand-written HIP kernels for gfx950 (csrc/), bound through the C
 ABI in include/clvmcmc.h.  There is no CPU fallback.
@@ -38,7 +40,8 @@ from .analysis import (chain_total_loglik, compare_forecasts, compare_models, co
                        forecast, forecast_pit, forecast_table, information_criteria, level1_diagnostics,
                        level1_rank_diagnostics, level2_autocorr, level2_diagnostics, level2_rank_diagnostics,
                        level2_summary, lifetime_value, lifetime_value_elasticities, pointwise_log_likelihood,
-                       post_mean_lambdas, post_mean_mus, posterior_weekly_tracking, psis_loo, score_customers,
+                       post_mean_lambdas, post_mean_mus, posterior_predictive_check, posterior_weekly_tracking, ppc_pit,
+                       psis_loo, score_customers,
                        summarize_level2, summary_rhat)
 from .bivariate import mcmc_draw_parameters
 from .mle import ParetoNBDFitter, mape_aggregate, pnbd_weekly_tracking
@@ -52,5 +55,5 @@ __all__ = ["mcmc_draw_parameters", "mcmc_draw_parameters_rfm_m", "draw_future_tr
            "pnbd_weekly_tracking", "mape_aggregate", "lifetime_value", "customer_equity",
            "lifetime_value_elasticities", "pointwise_log_likelihood", "information_criteria", "psis_loo",
            "compare_models", "score_customers", "forecast", "forecast_pit", "compare_forecasts",
-           "forecast_table"]
+           "forecast_table", "posterior_predictive_check", "ppc_pit"]
 __version__ = "0.1.0"

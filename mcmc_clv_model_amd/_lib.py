@@ -173,6 +173,14 @@ def lib() -> ctypes.CDLL:
         "clv_forecast_info": (c_int32, [POINTER(c_int64)]),
         "clv_debug_forecast": (c_int32, [c_int32, dp, c_int64, c_int64, c_int32, POINTER(c_int32), dp, dp, c_double,
                                          c_int32, POINTER(c_int32), c_int64, c_int32, dp, dp]),
+        "clv_ppc": (c_int32, [c_int32, c_int32, dp, c_int32, dp, c_int32, c_int32, dp, c_int64, c_int64,
+                              POINTER(c_int32), dp, dp, c_int32, c_uint64, c_int64, dp, POINTER(c_int64), dp,
+                              POINTER(c_int64), dp]),
+        "clv_ppc_sampler": (c_int32, [sp, c_int32, c_int32, c_uint64, dp, POINTER(c_int64), dp, POINTER(c_int64), dp]),
+        "clv_ppc_info": (c_int32, [POINTER(c_int64)]),
+        "clv_debug_ppc": (c_int32, [c_int32, c_int32, dp, c_int32, dp, c_int32, c_int32, dp, c_int64, c_int64,
+                                    POINTER(c_int32), dp, dp, c_int32, c_uint64, c_int64, dp, POINTER(c_int64), dp,
+                                    POINTER(c_int64), dp, c_int64, c_int32]),
         "clv_diagnostics": (c_int32, [c_int32, dp, c_int32, c_int64, c_int64, c_int32, c_uint32, dp]),
         "clv_diagnostics_sampler": (c_int32, [sp, c_uint32, dp, dp]),
         "clv_autocorr": (c_int32, [c_int32, dp, c_int32, c_int64, c_int64, c_int32, dp]),
@@ -279,6 +287,28 @@ def forecast_info() -> dict:
     check(lib().clv_forecast_info(out))
     return dict(block=int(out[0]), max_k=int(out[1]), max_draws=int(out[2]), series_cap=int(out[3]),
                 batch_doubles=int(out[4]))
+
+
+# Columns of clv_ppc() (include/clvmcmc.h CLV_PPC_* / CLV_PPC_DRAW_*): per customer; per draw the integer
+# columns that follow the k_hist + 1 histogram bins, and the float column.
+PPC_STATS = ("x_rep_mean", "p_x_lt", "p_x_eq", "p_zero", "tx_rep_mean", "p_tx_le", "p_alive_rep")
+PPC_DRAW_INTS = ("sum_x", "sum_x2", "max_x", "n_alive")
+PPC_DRAW_FLOATS = ("sum_tx",)
+PPC_LEVELS = {"customer": 0, "population": 1}
+# The limits of csrc/ppc.hip (clv_ppc_info reports the library's own; tests/test_ppc_cpu.py compares):
+# customers per workgroup, the largest k_hist, the t_x_rep doubles of one customer batch.
+PPC_BLOCK, PPC_MAX_K, PPC_BATCH_DOUBLES = 256, 4096, 1 << 27
+PPC_ITEM_ENV = "CLV_PPC_ITEM_DRAWS"  # draws per work item of the replicate kernel (whole 32-draw chunks; default 32): the profile's knob
+
+
+def ppc_info() -> dict:
+    """clv_ppc_info: the limits of csrc/ppc.hip and, of the replicate kernel this thread's last
+    posterior predictive check launched (-1 before one), VGPRs and scratch bytes per lane and the
+    device time of the call's kernels in ns."""
+    out = (c_int64 * 6)()
+    check(lib().clv_ppc_info(out))
+    keys = ("block", "max_k", "batch_doubles", "vgprs", "scratch_bytes", "kernel_ns")
+    return {k: int(v) for k, v in zip(keys, out)}
 
 
 def exported_symbols():

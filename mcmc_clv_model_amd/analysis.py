@@ -30,6 +30,10 @@ Reference functions mirrored (same names, arguments, defaults and return layout)
   reference builds its draws for, in closed form (``csrc/forecast.hip``): every customer's predictive
   distribution of the holdout count, its out-of-sample scores, Table 2's disaggregate rows and
   Figure 3's conditional expectations from the posterior mean instead of a plug-in.
+* ``posterior_predictive_check``, ``ppc_pit`` — the ``posterior_predictive`` group the reference's
+  ``az.from_dict`` objects never get: the calibration data replicated per draw at the customer or at
+  the population level (``csrc/ppc.hip``), the actual-vs-replicated frequency histogram, posterior
+  predictive p-values and per-customer calibration PITs.
 
 The per-customer / per-draw work runs in ``csrc/analysis.hip`` through the C ABI (``clv_predict``,
 ``clv_track``, ``clv_level1_summary``, ``clv_chain_total_loglik``); the host only reshapes and
@@ -55,7 +59,7 @@ __all__ = ["draw_future_transactions", "draw_future_transactions_rfm_m", "post_m
            "summary_rhat", "level1_rank_diagnostics", "level2_rank_diagnostics", "level2_summary",
            "lifetime_value", "customer_equity", "lifetime_value_elasticities",
            "pointwise_log_likelihood", "information_criteria", "psis_loo", "compare_models", "score_customers",
-           "forecast", "forecast_pit", "compare_forecasts", "forecast_table"]
+           "forecast", "forecast_pit", "compare_forecasts", "forecast_table", "posterior_predictive_check", "ppc_pit"]
 
 
 def _stacked_level1(level1_chains) -> np.ndarray:
@@ -892,6 +896,172 @@ def forecast_table(fc: Dict[str, Any], cbs: pd.DataFrame, pool_from: int = 7) ->
         labels.append(f"{pool_from}+" if k == pool_from else str(k))
         rows.append(dict(n=int(sel.sum()), actual=float(act[sel].mean()), predicted=float(pred[sel].mean())))
     return dict(metrics=metrics, by_frequency=pd.DataFrame(rows, index=pd.Index(labels, name="x")))
+
+
+# ---- posterior predictive checks of the calibration data (csrc/ppc.hip) ----------------------
+PPC_STATISTICS = ("share_zero", "total_x", "max_x", "var_x", "mean_recency")
+
+
+def ppc_params(level="customer", k_hist=None, seed=0, replicates=False, customer_offset=0, x=None,
+               n: Optional[int] = None) -> dict:
+    """level / k_hist / seed / customer_offset of :func:`posterior_predictive_check`, validated
+    (ValueError) on the host.  ``k_hist=None`` gives ``max(8, min(int(x.max()) + 1, 256))`` (8 without
+    ``x``)."""
+    if level not in _lib.PPC_LEVELS:
+        raise ValueError(f"level must be one of {sorted(_lib.PPC_LEVELS)} (got {level!r})")
+    if k_hist is None:
+        k_hist = 8 if x is None or len(x) == 0 else max(8, min(int(np.max(x)) + 1, 256))
+    if isinstance(k_hist, bool) or int(k_hist) != k_hist or not 1 <= int(k_hist) <= _lib.PPC_MAX_K:
+        raise ValueError(f"k_hist must be a whole number in [1, {_lib.PPC_MAX_K}] (got {k_hist!r})")
+    off = int(customer_offset)
+    if off < 0 or off + int(n or 0) > 1 << 32:
+        raise ValueError("customer_offset + N must fit in 32 bits")
+    return dict(level=level, k_hist=int(k_hist), seed=resolve_seed(seed), replicates=bool(replicates),
+                customer_offset=off)
+
+
+def _ppc_data(cbs: pd.DataFrame):
+    """x (int32), t_x, T_cal of the calibration CBS, checked."""
+    for col in ("x", "t_x", "T_cal"):
+        if col not in cbs:
+            raise ValueError(f"cbs has no column {col!r}")
+    if len(cbs) < 1:
+        raise ValueError("no customer")
+    xv = cbs["x"].to_numpy()
+    if np.any(xv < 0) or np.any(xv > np.iinfo(np.int32).max) or np.any(xv != np.round(xv)):
+        raise ValueError("x must hold non-negative integer counts")
+    return (np.ascontiguousarray(xv, dtype=np.int32), np.ascontiguousarray(cbs["t_x"].to_numpy(float)),
+            np.ascontiguousarray(cbs["T_cal"].to_numpy(float)))
+
+
+def ppc_outputs(nd: int, n: int, k_hist: int, replicates: bool):
+    """(customers, draws_int, draws_f, x_rep or None, t_x_rep or None) host buffers of a check."""
+    return (np.empty((n, len(_lib.PPC_STATS)), np.float64),
+            np.empty((nd, k_hist + 1 + len(_lib.PPC_DRAW_INTS)), np.int64),
+            np.empty((nd, len(_lib.PPC_DRAW_FLOATS)), np.float64),
+            np.empty((nd, n), np.int64) if replicates else None,
+            np.empty((nd, n), np.float64) if replicates else None)
+
+
+def _ppc_statistics(n: int, n_zero, sum_x, sum_x2, max_x, sum_tx) -> dict:
+    """The test statistics of one data set (or, vectorised, of every replicate) from its sums:
+    share_zero = n_zero / n, total_x, max_x, var_x = sum_x2 / n - (sum_x / n)^2 (ddof 0),
+    mean_recency = sum_tx / (n - n_zero), NaN when nobody repeats."""
+    n_zero, sum_x, sum_x2 = (np.asarray(v, dtype=np.float64) for v in (n_zero, sum_x, sum_x2))
+    rep = n - n_zero
+    with np.errstate(invalid="ignore", divide="ignore"):
+        rec = np.where(rep > 0, np.asarray(sum_tx, dtype=np.float64) / np.where(rep > 0, rep, 1.0), np.nan)
+    mean = sum_x / n
+    return dict(share_zero=n_zero / n, total_x=sum_x, max_x=np.asarray(max_x, dtype=np.float64),
+                var_x=sum_x2 / n - mean * mean, mean_recency=rec)
+
+
+def ppc_frames(cust: np.ndarray, draws_int: np.ndarray, draws_f: np.ndarray, x, t_x, k_hist: int, level: str,
+               seed: int, x_rep=None, t_x_rep=None) -> Dict[str, Any]:
+    """The outputs of ``clv_ppc`` as the return value of :func:`posterior_predictive_check`; ``x`` and
+    ``t_x`` are the observed calibration data, from which ``observed`` is computed by the replicates'
+    own definitions (the recency sum by :func:`fixed_order_sum`)."""
+    x = np.asarray(x, dtype=np.int64)
+    n, nd = len(x), draws_int.shape[0]
+    hist = draws_int[:, :k_hist + 1]
+    ints = {k: draws_int[:, k_hist + 1 + j] for j, k in enumerate(_lib.PPC_DRAW_INTS)}
+    sum_tx = draws_f[:, _lib.PPC_DRAW_FLOATS.index("sum_tx")]
+    rep = _ppc_statistics(n, hist[:, 0], ints["sum_x"], ints["sum_x2"], ints["max_x"], sum_tx)
+    draws = pd.DataFrame(dict(n_zero=hist[:, 0], total_x=ints["sum_x"], max_x=ints["max_x"], n_alive=ints["n_alive"],
+                              var_x=rep["var_x"], mean_recency=rep["mean_recency"]))
+    obs_hist = np.bincount(np.minimum(x, k_hist), minlength=k_hist + 1)
+    pct = np.percentile(hist, [5.0, 50.0, 95.0], axis=0)
+    freq = pd.DataFrame(dict(observed=obs_hist, rep_mean=hist.mean(axis=0), rep_p05=pct[0], rep_p50=pct[1],
+                             rep_p95=pct[2]),
+                        index=pd.Index(list(range(k_hist)) + [f"{k_hist}+"], name="x"))
+    obs = _ppc_statistics(n, int(np.count_nonzero(x == 0)), int(x.sum()), int((x * x).sum()), int(x.max()),
+                          fixed_order_sum(np.asarray(t_x, dtype=np.float64)))
+    rows = []
+    for name in PPC_STATISTICS:
+        r, o = np.asarray(rep[name], dtype=np.float64), float(obs[name])
+        ok = ~np.isnan(r)
+        m = int(ok.sum())
+        if m == 0 or np.isnan(o):
+            rows.append(dict(observed=o, rep_mean=np.nan, rep_sd=np.nan, p_value=np.nan, p_mid=np.nan))
+            continue
+        gt, eq = np.count_nonzero(r[ok] > o), np.count_nonzero(r[ok] == o)
+        rows.append(dict(observed=o, rep_mean=float(r[ok].mean()), rep_sd=float(r[ok].std(ddof=1)) if m > 1 else np.nan,
+                         p_value=(gt + eq) / m, p_mid=(gt + 0.5 * eq) / m))
+    out = dict(customers=pd.DataFrame(cust, columns=list(_lib.PPC_STATS)), frequency=freq, draws=draws,
+               statistics=pd.DataFrame(rows, index=pd.Index(list(PPC_STATISTICS), name="statistic")),
+               level=level, n_samples=int(nd), seed=int(seed))
+    if x_rep is not None:
+        out["x_rep"], out["t_x_rep"] = x_rep, t_x_rep
+    return out
+
+
+def posterior_predictive_check(draws: Dict[str, Any], cbs: pd.DataFrame, covariates=None, *, level: str = "customer",
+                               k_hist=None, seed: Optional[int] = 0, replicates: bool = False,
+                               customer_offset: int = 0, device: int = -1) -> Dict[str, Any]:
+    """Posterior predictive checks of the calibration data, on the GPU (``csrc/ppc.hip``, ``clv_ppc``):
+    for every stacked draw one replicate (x_rep, t_x_rep) of every customer's (x, t_x) on (0, T_cal] —
+    a lifetime tau ~ Exp(mu), x_rep ~ Poisson(lambda min(tau, T_cal)) purchases and the last of them
+    — and what the replicated data sets look like next to the observed one.
+
+    ``level="customer"`` replicates each customer from their own level-1 draws (lambda_i, mu_i): a
+    check of the Poisson / exponential individual model.  ``level="population"`` is the mixed
+    replicate: for each level-2 record (beta, Sigma) of ``draws["level_2"]`` a new
+    (lambda, mu) ~ LogNormal(beta' d_i, Sigma) for every customer's covariates d_i (``covariates``: the
+    fit's covariate columns of ``cbs``) — a check of the log-normal heterogeneity and the covariate
+    regression, which level-1 draws, adapting to each customer's own data, cannot give.
+
+    Returns a dict: ``customers`` (one row per customer, columns _lib.PPC_STATS: x_rep_mean, p_x_lt =
+    P(x_rep < x), p_x_eq, p_zero, tx_rep_mean, p_tx_le = P(t_x_rep <= t_x), p_alive_rep);
+    ``frequency`` (index 0 ... k_hist - 1 and "{k_hist}+": the observed number of customers with that
+    many repeat purchases and the mean, 5 / 50 / 95 % points of the replicated numbers over the
+    draws); ``draws`` (one row per replicated data set: n_zero, total_x, max_x, n_alive, var_x,
+    mean_recency = sum t_x_rep / (n - n_zero), NaN when nobody repeats); ``statistics`` (one row per
+    test statistic share_zero, total_x, max_x, var_x (ddof 0), mean_recency: observed, rep_mean,
+    rep_sd, p_value = P(T_rep >= T_obs), p_mid = P(>) + P(=) / 2, over the replicates where the
+    statistic is defined); ``level``, ``n_samples``, ``seed``; and with ``replicates=True`` the
+    (n_draws, n) arrays ``x_rep`` (int64) and ``t_x_rep``.  ``k_hist`` defaults to
+    ``max(8, min(max x + 1, 256))``, at most 4096.  The variates are a function of (seed,
+    customer_offset + i, stacked draw) alone: shard a customer base with ``customer_offset`` (the
+    per-draw integer columns of the shards add up).  Arguments are checked before any device is
+    touched."""
+    if level not in _lib.PPC_LEVELS:
+        raise ValueError(f"level must be one of {sorted(_lib.PPC_LEVELS)} (got {level!r})")
+    l1 = l2 = cov = None
+    w = D = K = 0
+    if level == "customer":
+        x, t_x, T_cal = _ppc_data(cbs)
+        l1 = _stacked_level1(draws.get("level_1") if isinstance(draws, dict) else draws)
+        nd, n, w = l1.shape
+        if n != x.shape[0]:
+            raise ValueError("cbs and draws disagree on the number of customers")
+    else:
+        rec = score_level2(draws)
+        l2 = np.ascontiguousarray(rec.reshape(-1, rec.shape[2]))
+        D, K, x, t_x, T_cal, cov, _ = score_problem(cbs, covariates, rec.shape[2])
+        nd, n = l2.shape[0], x.shape[0]
+    par = ppc_params(level, k_hist, seed, replicates, customer_offset, x, n)
+    L = _L()
+    cust, di, df, xr, tr = ppc_outputs(nd, n, par["k_hist"], par["replicates"])
+    check(L.clv_ppc(int(device), _lib.PPC_LEVELS[level], dptr(l1), int(w), dptr(l2), int(D), int(K), dptr(cov), nd, n,
+                    _i32p(x), dptr(t_x), dptr(T_cal), par["k_hist"], par["seed"], par["customer_offset"], dptr(cust),
+                    _i64p(di), dptr(df), None if xr is None else _i64p(xr), dptr(tr)))
+    return ppc_frames(cust, di, df, x, t_x, par["k_hist"], level, par["seed"], xr, tr)
+
+
+def ppc_pit(ppc: Dict[str, Any], bins: int = 10, seed: int = 0) -> pd.Series:
+    """The randomised probability integral transform histogram of the calibration counts under a
+    :func:`posterior_predictive_check`: u_i = p_x_lt + v_i p_x_eq with v_i uniform (numpy's
+    default_rng(seed)), counted in ``bins`` equal bins of [0, 1].  A model that replicates the
+    customers' counts gives a flat histogram.  Host numpy."""
+    cu = ppc["customers"]
+    lo, eq = cu["p_x_lt"].to_numpy(), cu["p_x_eq"].to_numpy()
+    if int(bins) < 1:
+        raise ValueError("bins must be >= 1")
+    if np.isnan(lo).any() or np.isnan(eq).any():
+        raise ValueError("the check carries no PIT values (a customer is NaN)")
+    u = lo + np.random.default_rng(seed).random(len(lo)) * eq
+    counts, edges = np.histogram(np.clip(u, 0.0, 1.0), bins=int(bins), range=(0.0, 1.0))
+    return pd.Series(counts, index=pd.Index(edges[:-1], name="pit_bin_left"), name="customers")
 
 
 # ---- convergence diagnostics (csrc/diag.hip) -------------------------------------------------

@@ -35,6 +35,11 @@ line and return layout (bivariate/mcmc.py:437-504); the sweeps run on the GPU
   the name of a column of ``cal_cbs`` —, ``k_max``, ``pmf``), adds ``out["forecast"]``: the closed-form
   predictive distribution of every customer's holdout purchases and, with ``x_star``, its scores, from
   the draws still in HBM (``csrc/forecast.hip``; ``draw_sink="full"`` only).  None changes nothing.
+* ``ppc``: True, or a dict of ``analysis.posterior_predictive_check``'s keywords (``level``, ``k_hist``,
+  ``seed``, ``replicates``), adds ``out["ppc"]``: the calibration data replicated per draw at the customer
+  or at the population level, with the frequency histogram, posterior predictive p-values and
+  per-customer PIT columns, from the draws still in HBM (``csrc/ppc.hip``; ``draw_sink="full"`` only).
+  None changes nothing.
 """
 from __future__ import annotations
 
@@ -52,7 +57,7 @@ def mcmc_draw_parameters(cal_cbs, covariates: Optional[Sequence[str]] = None, mc
                          rng: str = "philox", device: int = -1, replay_tape=None,
                          replay_sweeps: Optional[int] = None, devices: Optional[Sequence[int]] = None,
                          shard: str = "auto", exchange: str = "auto", diagnostics=False, lifetime_value=None,
-                         information_criteria=None, forecast=None):
+                         information_criteria=None, forecast=None, ppc=None):
     """Run the Abe (2009) Gibbs/MH sampler on calibration CBS (bivariate/mcmc.py:437).
 
     Returns dict(level_1=[(n_draws, N, 4) per chain: lambda, mu, tau, z],
@@ -72,4 +77,4 @@ def mcmc_draw_parameters(cal_cbs, covariates: Optional[Sequence[str]] = None, mc
                replay_tape=replay_tape, replay_sweeps=replay_sweeps, devices=devices, shard=shard,
                exchange=exchange, diagnostics=diagnostics, lifetime_value=lifetime_value,
                information_criteria=information_criteria,
-               forecast=forecast_kwargs(forecast, draw_sink, cal_cbs))
+               forecast=forecast_kwargs(forecast, draw_sink, cal_cbs), ppc=ppc)

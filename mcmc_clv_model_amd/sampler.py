@@ -509,6 +509,21 @@ class HipSampler:
                                            dptr(out), dptr(dist)))
         return A.forecast_frames(out, dist, self.chains * self.n_draws, xs is not None)
 
+    def posterior_predictive_check(self, *, level: str = "customer", k_hist=None, seed: Optional[int] = 0,
+                                   replicates: bool = False) -> dict:
+        """clv_ppc_sampler: analysis.posterior_predictive_check (the calibration data replicated per
+        draw, at the customer or at the population level) from the draws and level-2 records this
+        sampler holds in HBM, with the data and covariates it was created with, without the host
+        round trip; the same bits as the host-array route."""
+        from . import analysis as A
+        par = A.ppc_params(level, k_hist, seed, replicates, 0, self.p.x, self.n)
+        cust, di, df, xr, tr = A.ppc_outputs(self.chains * self.n_draws, self.n, par["k_hist"], par["replicates"])
+        i64 = ctypes.POINTER(ctypes.c_int64)
+        check(self._L.clv_ppc_sampler(self.h, _lib.PPC_LEVELS[level], par["k_hist"], par["seed"], dptr(cust),
+                                      di.ctypes.data_as(i64), dptr(df),
+                                      None if xr is None else xr.ctypes.data_as(i64), dptr(tr)))
+        return A.ppc_frames(cust, di, df, self.p.x, self.p.t_x, par["k_hist"], level, par["seed"], xr, tr)
+
     def chain_total_loglik(self) -> float:
         out = ctypes.c_double()
         check(self._L.clv_chain_total_loglik_sampler(self.h, ctypes.byref(out)))
@@ -623,7 +638,7 @@ def fit(p: Problem, *, mcmc: int, burnin: int, thin: int, chains: int, seed, tra
         draw_sink: str = "full", rng: str = "philox", device: int = -1, replay_tape=None,
         replay_sweeps: Optional[int] = None, devices: Optional[Sequence[int]] = None, shard: str = "auto",
         exchange: str = "auto", diagnostics=False, lifetime_value=None, information_criteria=None,
-        forecast=None) -> dict:
+        forecast=None, ppc=None) -> dict:
     """Run all chains of one problem in one batched launch sequence and return the reference's
     output layout (bi:499-504).  ``devices`` (two or more): the run is spread over those devices
     in this process (:func:`fit_multi`).  ``diagnostics``: also out["diagnostics"] = {"level_1",
@@ -639,7 +654,10 @@ def fit(p: Problem, *, mcmc: int, burnin: int, thin: int, chains: int, seed, tra
     same way.
     ``forecast``: True or a dict of analysis.forecast's keywords (T_star, x_star as an array, k_max,
     pmf) adds out["forecast"] (the closed-form holdout predictive distribution; full sink only),
-    routed the same way."""
+    routed the same way.
+    ``ppc``: True or a dict of analysis.posterior_predictive_check's keywords (level, k_hist, seed,
+    replicates) adds out["ppc"] (posterior predictive checks of the calibration data; full sink
+    only), routed the same way."""
     if chains < 1:
         raise ValueError("chains must be >= 1")
     if thin < 1:
@@ -651,6 +669,7 @@ def fit(p: Problem, *, mcmc: int, burnin: int, thin: int, chains: int, seed, tra
     ltv_kw = lifetime_value_kwargs(lifetime_value, draw_sink)
     ic_kw = information_criteria_kwargs(information_criteria, draw_sink, p.D)
     fc_kw = forecast_kwargs(forecast, draw_sink, n=p.N)
+    ppc_kw = ppc_kwargs(ppc, draw_sink)
     if devices is not None:
         devices = [int(d) for d in devices]
         if not devices:
@@ -661,7 +680,7 @@ def fit(p: Problem, *, mcmc: int, burnin: int, thin: int, chains: int, seed, tra
             out = fit_multi(p, mcmc=mcmc, burnin=burnin, thin=thin, chains=chains, seed=seed, trace=trace,
                             n_mh_steps=n_mh_steps, draw_sink=draw_sink, devices=devices, shard=shard,
                             exchange=exchange, lifetime_value=lifetime_value,
-                            information_criteria=information_criteria, forecast=forecast)
+                            information_criteria=information_criteria, forecast=forecast, ppc=ppc)
             if diagnostics:
                 from . import analysis as A
                 out["diagnostics"] = dict(level_1=A.level1_diagnostics(out, device=devices[0]),
@@ -697,6 +716,8 @@ def fit(p: Problem, *, mcmc: int, burnin: int, thin: int, chains: int, seed, tra
             out["information_criteria"] = s.information_criteria(**ic_kw)
         if fc_kw is not None:
             out["forecast"] = s.forecast(**fc_kw)
+        if ppc_kw is not None:
+            out["ppc"] = s.posterior_predictive_check(**ppc_kw)
         return out
     finally:
         s.close()
@@ -762,6 +783,17 @@ def forecast_kwargs(forecast, draw_sink: str, cbs=None, n=None):
     return kw
 
 
+def ppc_kwargs(ppc, draw_sink: str):
+    """The ``ppc=`` keyword of the fit functions as analysis.posterior_predictive_check's keywords
+    (None: not asked for), validated before the run starts."""
+    kw = analysis_kwargs("ppc", ppc, draw_sink, ("level", "k_hist", "seed", "replicates"))
+    if kw is None:
+        return None
+    from . import analysis as A
+    A.ppc_params(kw.get("level", "customer"), kw.get("k_hist"), kw.get("seed", 0), kw.get("replicates", False))
+    return kw
+
+
 def multi_plan(chains: int, n_dev: int, draw_sink: str, shard: str = "auto"):
     """How :func:`fit_multi` spreads a run over ``n_dev`` devices: ("chains", [(first chain,
     chains), ...] one group per device used) or ("customers", None).  "auto" takes chain groups
@@ -783,7 +815,7 @@ def multi_plan(chains: int, n_dev: int, draw_sink: str, shard: str = "auto"):
 
 def fit_multi(p: Problem, *, mcmc: int, burnin: int, thin: int, chains: int, seed, trace: int, n_mh_steps: int,
               draw_sink: str, devices: Sequence[int], shard: str = "auto", exchange: str = "auto",
-              lifetime_value=None, information_criteria=None, forecast=None) -> dict:
+              lifetime_value=None, information_criteria=None, forecast=None, ppc=None) -> dict:
     """One run over several devices of this process (SURVEY §8b ``devices=``), same output as the
     single-device run, bit for bit:
 
@@ -797,12 +829,13 @@ def fit_multi(p: Problem, *, mcmc: int, burnin: int, thin: int, chains: int, see
     * ``"auto"``: chains when they divide evenly over the devices (and the sink is not
       "summary+pct", whose percentiles pool all chains), else customers.
 
-    ``lifetime_value``, ``information_criteria``, ``forecast``: as :func:`fit`, computed from the returned arrays
+    ``lifetime_value``, ``information_criteria``, ``forecast``, ``ppc``: as :func:`fit`, computed from the returned arrays
     on ``devices[0]``."""
     import threading
     ltv_kw = lifetime_value_kwargs(lifetime_value, draw_sink)
     ic_kw = information_criteria_kwargs(information_criteria, draw_sink, p.D)
     fc_kw = forecast_kwargs(forecast, draw_sink, n=p.N)
+    ppc_kw = ppc_kwargs(ppc, draw_sink)
 
     def finish(out):
         if ltv_kw is not None:
@@ -821,6 +854,16 @@ def fit_multi(p: Problem, *, mcmc: int, burnin: int, thin: int, chains: int, see
             import pandas as pd
             out["forecast"] = A.forecast(out, pd.DataFrame(dict(x=p.x, t_x=p.t_x, T_cal=p.T_cal)),
                                          device=int(devices[0]), **fc_kw)
+        if ppc_kw is not None:
+            from . import analysis as A
+            import pandas as pd
+            cbs = dict(x=p.x, t_x=p.t_x, T_cal=p.T_cal)
+            names = [f"cov{k}" for k in range(1, p.K)]
+            for k, nm in enumerate(names):
+                cbs[nm] = p.cov[k]
+            if p.log_s is not None:
+                cbs["log_s"] = p.log_s
+            out["ppc"] = A.posterior_predictive_check(out, pd.DataFrame(cbs), names, device=int(devices[0]), **ppc_kw)
         return out
 
     n_dev = len(devices)

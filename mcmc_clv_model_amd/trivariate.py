@@ -20,7 +20,8 @@ def mcmc_draw_parameters_rfm_m(cal_cbs, covariates: Optional[Sequence[str]] = No
                                draw_sink: str = "full", rng: str = "philox", device: int = -1,
                                replay_tape=None, replay_sweeps: Optional[int] = None,
                                devices: Optional[Sequence[int]] = None, shard: str = "auto", exchange: str = "auto",
-                               diagnostics=False, lifetime_value=None, information_criteria=None, forecast=None):
+                               diagnostics=False, lifetime_value=None, information_criteria=None, forecast=None,
+                               ppc=None):
     """3-dimensional HB Pareto/NBD + spend sampler (trivariate/mcmc.py:580).
 
     Returns {"level_1": [(n_draws, N, 5) per chain: lambda, mu, tau, z, eta],
@@ -34,6 +35,6 @@ def mcmc_draw_parameters_rfm_m(cal_cbs, covariates: Optional[Sequence[str]] = No
               replay_tape=replay_tape, replay_sweeps=replay_sweeps, devices=devices, shard=shard,
               exchange=exchange, diagnostics=diagnostics, lifetime_value=lifetime_value,
               information_criteria=information_criteria,
-              forecast=forecast_kwargs(forecast, draw_sink, cal_cbs))
+              forecast=forecast_kwargs(forecast, draw_sink, cal_cbs), ppc=ppc)
     out["log_likelihood"] = float(out["log_likelihood"])  # tri:652 returns a Python float
     return out
