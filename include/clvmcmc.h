@@ -473,7 +473,9 @@ int clv_lifetime_value_sampler(clv_sampler* s, const double* monetary, double de
  * tile of the transposing pass, out[2] keys per sort batch, out[3] the most stacked draws, out[4]
  * draws per LDS tile of the sd kernel.  The
  * environment variable CLV_LTV_BATCH (customers, rounded up to whole blocks) lowers the customer
- * batch: a test knob, the results do not depend on it. */
+ * batch: a test knob, the results do not depend on it.
+ * CLV_DIAG_BATCH (series) likewise lowers the series batch of clv_diagnostics, clv_rank_diagnostics and clv_autocorr.
+ * CLV_SUMMARY_BATCH (customers) likewise lowers the customer batch of clv_level1_summary's percentile sort. */
 int clv_ltv_info(int64_t* out);
 
 /* ---- Model comparison: pointwise log-likelihood, WAIC and PSIS-LOO (csrc/ic.hip) ----

@@ -230,6 +230,8 @@ LTV_STATS = ("value_mean", "value_sd", "value_p025", "value_p50", "value_p975", 
              "residual_p025", "residual_p50", "residual_p975", "p_alive", "lifetime_yrs", "survival_1yr")
 LTV_DRAW_STATS = ("equity", "value_total", "n_alive", "mu_share")
 LTV_BATCH_ENV = "CLV_LTV_BATCH"  # customers per sort batch (whole 256-customer blocks): the tests' knob
+DIAG_BATCH_ENV = "CLV_DIAG_BATCH"  # series per batch of the diagnostics (csrc/diag.hip batch_series): the tests' knob
+SUMMARY_BATCH_ENV = "CLV_SUMMARY_BATCH"  # customers per sort batch of the level-1 summary: the tests' knob
 # The limits of csrc/ltv.hip (clv_ltv_info reports the library's own; tests/test_ltv_cpu.py compares):
 # customers per reduction block, draws per LDS tile of the transposing pass, keys per sort batch,
 # the most stacked draws, draws per LDS tile of the sd kernel.

@@ -286,7 +286,7 @@ int track_dev(const double* l1, int64_t n_draws, int64_t n, int32_t width, const
 // The level-1 summary [n][CLV_N_L1_STATS] -> out (host): means(dout) launches the kernel of the six
 // means, gather(col, i0, nc, seg) the one laying column col (0 lambda, 1 mu) of customers
 // [i0, i0 + nc) out as [customer][draw] keys of type K.  Percentiles: customers in batches of
-// <= 2^27 keys, exact segmented radix sort per customer.
+// <= 2^27 keys (fewer customers with CLV_SUMMARY_BATCH), exact segmented radix sort per customer.
 template <class K, class Means, class Gather>
 int summary_dev(int64_t n_draws, int64_t n, double* out, hipStream_t st, Means means, Gather gather) {
   DevBuf bo, bin;
@@ -294,7 +294,8 @@ int summary_dev(int64_t n_draws, int64_t n, double* out, hipStream_t st, Means m
   double* dout = (double*)bo.p;
   means(dout);
   CLV_HIP(hipGetLastError());
-  const int64_t per_batch = std::max<int64_t>(1, std::min<int64_t>(n, (int64_t(1) << 27) / n_draws));
+  const int64_t per_batch =
+      lowered_by_env("CLV_SUMMARY_BATCH", std::max<int64_t>(1, std::min<int64_t>(n, (int64_t(1) << 27) / n_draws)));
   CLV_HIP(hipMalloc(&bin.p, sizeof(K) * (size_t)per_batch * n_draws));
   SegSorter<K> sorter;
   int rc = sorter.init(per_batch, n_draws, st);

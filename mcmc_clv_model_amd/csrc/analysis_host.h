@@ -6,6 +6,7 @@
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 
 #include <algorithm>
+#include <cstdlib>
 #include <string>
 
 #include "internal.h"
@@ -21,6 +22,16 @@ int upload(DevBuf& buf, const T* host, size_t count, hipStream_t st) {
   CLV_HIP(hipMalloc(&buf.p, sizeof(T) * count));
   CLV_HIP(hipMemcpyAsync(buf.p, host, sizeof(T) * count, hipMemcpyHostToDevice, st));
   return CLV_OK;
+}
+
+// per, lowered to the positive count the environment variable `name` holds, if it holds one: the
+// tests' knob for a batch size (read at call time; it never raises a batch).
+inline int64_t lowered_by_env(const char* name, int64_t per) {
+  if (const char* e = std::getenv(name)) {
+    const long long v = std::atoll(e);
+    if (v > 0) per = std::min<int64_t>(per, v);
+  }
+  return per;
 }
 
 // off[c] = c * len for c = 0 .. nc: the segment boundaries of nc segments of len keys.

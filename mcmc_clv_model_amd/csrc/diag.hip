@@ -603,8 +603,11 @@ int check_series(int32_t n_chains, int64_t n_draws, int64_t n_series) {
   return CLV_OK;
 }
 
+// Series per batch: as many as DIAG_BATCH_ELEMS values hold (at least one); CLV_DIAG_BATCH (series)
+// forces a smaller one — the tests' knob.  The batch loop and the global-path scratch both size
+// themselves here.
 int64_t batch_series(int64_t mn, int64_t n_series) {
-  return std::max<int64_t>(1, std::min<int64_t>(n_series, DIAG_BATCH_ELEMS / mn));
+  return lowered_by_env("CLV_DIAG_BATCH", std::max<int64_t>(1, std::min<int64_t>(n_series, DIAG_BATCH_ELEMS / mn)));
 }
 
 // Walks the series of d_in (device, [chain * draw][n_series]) in batches of batch_series: each batch

@@ -15,6 +15,10 @@ Power: the same device outputs are compared with one thing wrong at a time in th
 at 2^20 - 1; the week index taken pass-relative; t >= b for t > b; gap slots from 15; the lifetime
 read from (z, w)); each must fail on at least 1 % of the lanes.
 
+Beyond one customer batch and one pass of the draw grid: the level-1 summary in batches of
+CLV_SUMMARY_BATCH customers (float64 keys and the "summary+pct" sink's float32 keys), and
+chain_total_loglik / weekly tracking at 2^20 + 3 draws, past the 2^20 workgroups their kernels launch.
+
 Measured on MI355X: see DESIGN.md §2 ("Predictive, tracking and generator draws").
 """
 import math
@@ -302,7 +306,16 @@ def test_level1_summary_edge_shapes(nd):
     """n_draws in {1, 2, 3, 40, 41, 257} x n in {1, 255, 257} x widths 4 and 5 x mu_cap in {0.05, 1e-300,
     inf}: percentiles bitwise np.percentile(method="linear"), means bitwise the sequential sum over
     draws / n_draws (the order spelled out with np.add.accumulate)."""
-    from mcmc_clv_model_amd.analysis import level1_summary
+    for n, w, a in _summary_cases(nd):
+        for cap in SUMMARY_CAPS:
+            _summary_check(a, cap, (nd, n, w, cap))
+
+
+SUMMARY_CAPS = (0.05, 1e-300, math.inf)
+
+
+def _summary_cases(nd):
+    """(n, w, level-1 array (nd, n, w)) of test_level1_summary_edge_shapes, from one generator in order."""
     rng = np.random.default_rng(1000 + nd)
     for n in (1, 255, 257):
         for w in (4, 5):
@@ -310,21 +323,68 @@ def test_level1_summary_edge_shapes(nd):
             for col in range(w):
                 a[..., col] = _summary_column(rng, nd, n)
             assert not np.isnan(a).any() and (a != 0).all()
-            mean = lambda v: np.add.accumulate(v, axis=0)[-1] / nd  # noqa: E731
-            for cap in (0.05, 1e-300, math.inf):
-                s = level1_summary(dict(level_1=[a]), mu_cap=cap)
-                want = dict(mean_lambda=mean(a[..., 0]), mean_mu=mean(a[..., 1]), mean_tau=mean(a[..., 2]),
-                            mean_z=mean(a[..., 3]), mean_mu_capped=mean(np.minimum(a[..., 1], cap)),
-                            lambda_p025=np.percentile(a[..., 0], 2.5, axis=0, method="linear"),
-                            lambda_p975=np.percentile(a[..., 0], 97.5, axis=0, method="linear"),
-                            mu_p025=np.percentile(a[..., 1], 2.5, axis=0, method="linear"),
-                            mu_p975=np.percentile(a[..., 1], 97.5, axis=0, method="linear"))
-                if w == 5:
-                    want["mean_eta"] = mean(a[..., 4])
-                assert set(want) == set(s.columns)
-                for k, v in want.items():
-                    bad = _bits(s[k].to_numpy()) != _bits(v)
-                    assert not bad.any(), (k, nd, n, w, cap, int(bad.sum()), np.flatnonzero(bad)[:5])
+            yield n, w, a
+
+
+def _summary_check(a, cap, label):
+    """level1_summary(a, cap): percentiles bitwise np.percentile(method="linear"), means bitwise the
+    sequential sum over draws / n_draws.  Returns the number of (column, customer) entries compared."""
+    from mcmc_clv_model_amd.analysis import level1_summary
+    nd, _, w = a.shape
+    mean = lambda v: np.add.accumulate(v, axis=0)[-1] / nd  # noqa: E731
+    s = level1_summary(dict(level_1=[a]), mu_cap=cap)
+    want = dict(mean_lambda=mean(a[..., 0]), mean_mu=mean(a[..., 1]), mean_tau=mean(a[..., 2]),
+                mean_z=mean(a[..., 3]), mean_mu_capped=mean(np.minimum(a[..., 1], cap)),
+                lambda_p025=np.percentile(a[..., 0], 2.5, axis=0, method="linear"),
+                lambda_p975=np.percentile(a[..., 0], 97.5, axis=0, method="linear"),
+                mu_p025=np.percentile(a[..., 1], 2.5, axis=0, method="linear"),
+                mu_p975=np.percentile(a[..., 1], 97.5, axis=0, method="linear"))
+    if w == 5:
+        want["mean_eta"] = mean(a[..., 4])
+    assert set(want) == set(s.columns)
+    for k, v in want.items():
+        bad = _bits(s[k].to_numpy()) != _bits(v)
+        assert not bad.any(), (k, label, int(bad.sum()), np.flatnonzero(bad)[:5])
+    return sum(v.size for v in want.values())
+
+
+@pytest.mark.parametrize("batch", [1, 100, 256])
+def test_level1_summary_customer_batches(monkeypatch, batch):
+    """summary_dev<double> with more than one customer batch (CLV_SUMMARY_BATCH; the natural batch is
+    2^27 / n_draws customers): the nd = 41, n = 257, width 5 case of test_level1_summary_edge_shapes in
+    batches of 1 (257 batches), 100 (100, 100, 57: SegSorter::sort with nc != filled, offsets refilled and
+    the temporary storage of the larger count reused) and 256 (a last batch of one).  i0 > 0 in
+    gather_kernel and row0 = i0 in launch_percentiles.  Same reference, bit for bit."""
+    from mcmc_clv_model_amd import _lib
+    n, w, a = list(_summary_cases(41))[-1]
+    assert (n, w) == (257, 5)
+    monkeypatch.setenv(_lib.SUMMARY_BATCH_ENV, str(batch))
+    count = sum(_summary_check(a, cap, (41, n, w, cap, batch)) for cap in SUMMARY_CAPS)
+    monkeypatch.delenv(_lib.SUMMARY_BATCH_ENV)
+    print(f"level1_summary CLV_SUMMARY_BATCH={batch}: {count} entries, 0 differ from numpy in any bit")
+
+
+def test_summary_pct_sink_customer_batches(monkeypatch):
+    """summary_dev<float> (the "summary+pct" sink's float32 keys, gather_q_kernel) at the D = 2
+    configuration of test_summary_pct_sink_matches_full_sink, n = 1500, in batches of 1 and 100 customers:
+    bitwise the same sampler's unbatched summary (which that test holds to the full sink)."""
+    from mcmc_clv_model_amd import _lib
+    from mcmc_clv_model_amd.sampler import HipSampler, build_problem
+    from tests.helpers import cdnow
+    p = build_problem(cdnow("abe", 1500), ["first_sales_scaled"], D=2)
+    with HipSampler(p, mcmc=301, burnin=40, thin=3, chains=3, seed=11, draw_sink="summary+pct") as s:
+        s.run(341)
+        whole = s.level1_summary(_lib.SUMMARY_MU_CAP)
+        assert whole.shape == (1500, len(_lib.L1_STATS)) and np.isfinite(whole).all()
+        lo, hi = whole[:, _lib.L1_STATS.index("lambda_p025")], whole[:, _lib.L1_STATS.index("lambda_p975")]
+        assert (lo < hi).all() and len(np.unique(lo)) > 1400          # per-customer values, not one row repeated
+        for batch in (1, 100):
+            monkeypatch.setenv(_lib.SUMMARY_BATCH_ENV, str(batch))
+            got = s.level1_summary(_lib.SUMMARY_MU_CAP)
+            monkeypatch.delenv(_lib.SUMMARY_BATCH_ENV)
+            diff = int((_bits(got) != _bits(whole)).sum())
+            print(f"summary+pct CLV_SUMMARY_BATCH={batch}: {diff} of {whole.size} entries differ from the unbatched summary")
+            assert diff == 0, batch
 
 
 @pytest.mark.parametrize("n", [1, 255, 257])
@@ -354,3 +414,76 @@ def test_chain_total_loglik_edge_shapes(n):
     got = chain_total_loglik([a], pd.DataFrame(dict(x=x, T_cal=T)))
     print(f"chain_total_loglik n = {n}: |got - ref| / sum |component| = {abs(got - ref) / mag:.2e}")
     assert abs(got - ref) <= A.RTOL * mag
+
+
+# ---------------------------------------------------------------------------------------------
+# more draws than workgroups: loglik_kernel and track_kernel launch min(n_draws, 2^20) workgroups and
+# stride over the draws
+# ---------------------------------------------------------------------------------------------
+STRIDE_GRID = 1 << 20
+STRIDE_DRAWS = STRIDE_GRID + 3
+
+
+def test_chain_total_loglik_draw_stride():
+    """2^20 + 3 draws, n = 2, width 4 (64 MiB): draws 2^20 .. 2^20 + 2 are reached only by the stride of
+    loglik_kernel.  Their lambda is 100 times larger, so that their share of the mean exceeds the
+    tolerance by orders of magnitude (asserted from the reference before the device runs).  Reference:
+    float64 per-draw totals (10 terms each) combined with math.fsum; tolerance RTOL * sum |component|
+    as in test_chain_total_loglik_edge_shapes."""
+    from mcmc_clv_model_amd.analysis import chain_total_loglik
+    rng = np.random.default_rng(2002)
+    nd, n = STRIDE_DRAWS, 2
+    x = rng.integers(0, 40, n)
+    x[::7] = 0
+    x[::5] = 10_000
+    T = rng.uniform(20.0, 40.0, n)
+    a = np.empty((nd, n, 4))
+    a[..., 0] = np.exp(rng.normal(-1.0, 2.0, (nd, n)))
+    a[..., 1] = np.exp(rng.normal(-3.0, 2.0, (nd, n)))
+    a[..., 2] = rng.uniform(0.0, 60.0, (nd, n))
+    a[..., 3] = rng.choice([0.0, 0.5, 0.75, 1.0], (nd, n))
+    a[STRIDE_GRID:, :, 0] *= 100.0
+    lam, mu, tau, z = a[..., 0], a[..., 1], a[..., 2], (a[..., 3] > 0.5).astype(np.float64)
+    w = z * T + (1 - z) * tau
+    comp = np.concatenate([x * np.log(lam), (1 - z) * np.log(mu), -(lam * w), -(mu * w),
+                           np.broadcast_to(-gammaln(x + 1.0), (nd, n))], axis=1)
+    assert comp.shape == (nd, 5 * n)
+    totals, mags = comp.sum(axis=1), np.abs(comp).sum(axis=1)
+    ref, mag = math.fsum(totals) / nd, math.fsum(mags) / nd
+    tol = A.RTOL * mag
+    # what the strided draws add to the mean, and what a kernel that left them at ordinary values would miss
+    strided = abs(math.fsum(totals[STRIDE_GRID:])) / nd
+    shift = abs(math.fsum(totals[STRIDE_GRID:]) - 3 * math.fsum(totals[:STRIDE_GRID]) / STRIDE_GRID) / nd
+    print(f"chain_total_loglik stride: the three strided draws carry {strided:.3e} of the mean "
+          f"({shift:.3e} more than three ordinary draws); tolerance {tol:.3e}")
+    assert strided >= 1e3 * tol and shift >= 1e3 * tol
+    got = chain_total_loglik([a], pd.DataFrame(dict(x=x, T_cal=T)))
+    print(f"chain_total_loglik n_draws = 2^20 + 3: |got - ref| / sum |component| = {abs(got - ref) / mag:.2e}")
+    assert abs(got - ref) <= tol
+
+
+def test_track_draw_stride():
+    """2^20 + 3 draws, n = 2, one week: tau = 0 everywhere (nobody is active, the rate and the increment
+    are exactly 0) but in draws {0, 2^20 - 1, 2^20, 2^20 + 2}, whose summed rate is about 600.  The mean
+    is the sum of those four Poisson draws of the model (counter (week 0, flat draw, attempt, 3)) over
+    n_draws, bit for bit; the two draws past 2^20 are reached only by the stride of track_kernel and
+    carry about half of it."""
+    nd, n = STRIDE_DRAWS, 2
+    special = np.array([0, STRIDE_GRID - 1, STRIDE_GRID, STRIDE_GRID + 2])
+    lam, tau = np.full((nd, n), 0.25), np.zeros((nd, n))
+    lam[special] = np.array([[280.0, 330.0], [295.5, 301.25], [310.0, 287.0], [305.75, 299.0]])
+    tau[special] = 5.0
+    c = dict(level1=A._l1_track(lam, tau), birth=np.zeros(n), times=np.array([1.0]))
+    rate = A.track_rates(c["level1"][special], c["birth"], c["times"])
+    others = np.array([1, STRIDE_GRID - 2, STRIDE_GRID + 1])
+    assert (A.track_rates(c["level1"][others], c["birth"], c["times"]) == 0.0).all()
+    assert rate.shape == (4, 1) and (rate > 550.0).all() and (rate < 650.0).all()
+    inc, margin = A.poisson(rate, A.SEED_HI, 0, special[:, None], 0, A.STREAM_TRACK)
+    assert (margin > A.RTOL).all() and (inc > 400).all()
+    want = np.add.accumulate(inc[:, 0].astype(np.float64))[-1] / nd
+    past = float(inc[2:, 0].sum()) / nd
+    assert 0.4 * want < past < 0.6 * want
+    got = _track_dev(c, A.SEED_HI)
+    print(f"track n_draws = 2^20 + 3: the four active draws {inc[:, 0].tolist()}, mean got {got[0]!r}, want {want!r} "
+          f"({past / want:.1%} of it past draw 2^20)")
+    assert got.shape == (1,) and _bits(got)[0] == _bits(np.array([want]))[0]

@@ -4,7 +4,12 @@ tests/golden/make_pnbd_goldens.py).  Neither mpmath nor a host fit is needed her
 
 Bound for a device value against the exact one, relative to max(1, |value|): 8 x the fixture's
 recorded error of the float64 numpy model (E_ref), floor 64 ulp.  The margin: the device log, lgamma
-and log1p each differ from glibc's by a few ulp, and log L adds about eight such terms."""
+and log1p each differ from glibc's by a few ulp, and log L adds about eight such terms.
+
+The block strides (more than PNBD_MAX_GRID = 2,048 blocks) and the lane stride of the final reduction
+(more than 256 block partials) are reached at n = 524,545 and 65,537; measured: DESIGN.md section 4e."""
+import math
+
 import numpy as np
 import pandas as pd
 import pytest
@@ -86,6 +91,47 @@ def test_block_edges_fixed_order_sums(abe, n):
     assert np.allclose(sw, sd, rtol=1e-13, atol=0)
 
 
+@pytest.mark.parametrize("n", [65_537, 524_545])
+def test_beyond_one_grid_and_one_reduction_pass(abe, n):
+    """The abe table tiled to n = 65,537 (nb = 257 block partials: lane 0 of pnbd_final_kernel takes
+    partials 0 and 256, the lane stride) and n = 524,545 (nb = 2,050 > PNBD_MAX_GRID = 2,048: the block
+    stride b += gridDim.x of pnbd_eval_kernel, the lane stride of pnbd_customers_kernel).  A strided
+    customer has the bits of the same row among the first 2,357; the sums are those of the fixed order
+    (tests/pnbd_ref.device_sum, whose second level tests/test_pnbd_cpu.py holds to math.fsum)."""
+    from mcmc_clv_model_amd.mle import PnbdData
+    idx = np.arange(n) % len(abe[0])
+    x, tx, T = (a[idx] for a in abe)
+    nb = -(-n // 256)
+    assert nb == {65_537: 257, 524_545: 2_050}[n]
+    with PnbdData(x, tx, T) as d:
+        cust = d.customers(NEAR_OPT, 39.0)
+        s1, u1 = d.eval(NEAR_OPT)
+        s2, u2 = d.eval(NEAR_OPT)
+    assert cust.shape == (n, 3) and not np.isnan(cust).any()
+    moved = (bits(cust) != bits(cust[:len(abe[0])][idx])).any(axis=1)
+    print(f"n = {n}: {int(moved.sum())} customers differ from their row among the first {len(abe[0])}")
+    assert not moved.any(), np.flatnonzero(moved)[:5]
+    assert u1 == 0 and u2 == 0 and np.array_equal(bits(s1), bits(s2))
+    assert bits(s1[0]) == bits(R.device_sum(cust[:, 0])) and s1[5] == float(n)
+    g = R.model_customers(*abe, NEAR_OPT)["grad"][idx]
+    want = np.array([math.fsum(g[:, j]) for j in range(4)])
+    scale = np.maximum(1.0, [math.fsum(np.abs(g[:, j])) for j in range(4)])
+    err = (np.abs(s1[1:5] - want) / scale).max()
+    print(f"n = {n} gradient sums: measured {err:.3g} of sum |terms|, bound 1e-12")
+    assert err <= 1e-12
+    # weights of 0 on all but the last 300 customers = the table of those 300: a strided block reads its own w
+    w = np.zeros(n)
+    w[-300:] = 1.0
+    with PnbdData(x, tx, T, w) as d:
+        sw, uw = d.eval(NEAR_OPT)
+    with PnbdData(x[-300:], tx[-300:], T[-300:]) as d:
+        s300, _ = d.eval(NEAR_OPT)
+    print(f"n = {n} weights: largest relative deviation from the 300-customer table "
+          f"{np.max(np.abs(sw[:5] / s300[:5] - 1.0)):.3g}")
+    assert sw[5] == 300.0 == s300[5] and uw == 0
+    assert np.allclose(sw[:5], s300[:5], rtol=1e-13, atol=0)
+
+
 @pytest.mark.parametrize("name", ["abe", "full"])
 def test_fit_reaches_the_golden_optimum(edge, name):
     from mcmc_clv_model_amd import ParetoNBDFitter
@@ -130,6 +176,23 @@ def test_weekly_tracking_curve():
     cum3 = pnbd_weekly_tracking(f, birth3, times)
     want3 = [f.expected_number_of_purchases_up_to_time(np.clip(t - birth3, 0, None)).sum() for t in times]
     assert np.allclose(cum3, want3, rtol=1e-13, atol=0) and (np.diff(cum3) >= 0).all()
+
+
+def test_weekly_tracking_beyond_one_grid():
+    """524,545 births (2,050 blocks > PNBD_MAX_GRID: the block stride of pnbd_track_kernel; 9 partials
+    per lane of pnbd_final_kernel) and 3 times, against the fixed-order sum of the float64 model."""
+    from mcmc_clv_model_amd import ParetoNBDFitter, pnbd_weekly_tracking
+    n = 524_545
+    birth = np.random.default_rng(12).integers(1, 91, n)
+    times = np.array([10.0, 40.0, 78.0])
+    f = ParetoNBDFitter()
+    f.params_ = pd.Series(NEAR_OPT, index=["r", "alpha", "s", "beta"])
+    cum = pnbd_weekly_tracking(f, birth, times)
+    rel_t = np.clip(times[:, None] - birth[None, :], 0, None).astype(np.float64)
+    want = np.array([R.device_sum(row) for row in R.model_expected_purchases(rel_t, NEAR_OPT)])
+    print(f"tracking n = {n}: largest relative deviation from the model's fixed-order sum {np.max(np.abs(cum / want - 1.0)):.3g}")
+    assert cum.shape == (3,) and (np.diff(cum) > 0).all() and cum[0] > 0
+    assert np.allclose(cum, want, rtol=1e-14, atol=0)
 
 
 def test_einval_paths_leave_the_handle_usable(abe):

@@ -140,6 +140,21 @@ def test_device_sum_order_model():
     assert R.device_sum(w) == R.tree256(w[None])[0]
 
 
+@pytest.mark.parametrize("n", [65_537, 524_545])
+def test_device_sum_second_level(n):
+    """More than 256 block partials (257: lane 0 adds partials 0 and 256; 2,050: up to 9 per lane): on
+    integers, whose every partial sum is exact, device_sum equals math.fsum — each value enters once."""
+    import math
+    assert -(-n // 256) == {65_537: 257, 524_545: 2_050}[n]
+    v = np.arange(1, n + 1, dtype=np.float64)
+    assert R.device_sum(v) == math.fsum(v) == n * (n + 1) / 2
+    w = np.random.default_rng(5).integers(-2 ** 20, 2 ** 20, n).astype(np.float64)     # signed, |sum| < 2^40
+    assert R.device_sum(w) == math.fsum(w)
+    one = np.zeros(n)
+    one[-1] = 3.0                                                                      # the last block's only customer
+    assert R.device_sum(one) == 3.0
+
+
 def test_create_validation_runs_before_any_device_call():
     """Every CLV_EINVAL path of clv_pnbd_create / clv_pnbd_track is host code: reachable without a GPU."""
     import ctypes
