@@ -697,6 +697,60 @@ int clv_debug_ppc(int32_t device, int32_t level, const double* level1, int32_t w
                   double* out_customers, int64_t* out_draws_int, double* out_draws_f, int64_t* out_x_rep,
                   double* out_tx_rep, int64_t batch_customers, int32_t grid);
 
+/* ---- The marginal likelihood and marginal WAIC / PSIS-LOO (csrc/marginal.hip) ----
+ * Nothing in the reference: it replaces az.loo / az.waic on a log-likelihood that is marginal over the
+ * customer's own parameters (Merkle, Furr & Rabe-Hesketh 2019), which needs a quadrature per
+ * (customer, level-2 record).  Per record r of level2 [n_records][D K + D (D + 1) / 2] (the layout of
+ * clv_score_customers) and customer i:
+ *   l_marg[r][i] = log int int L(x_i, t_x,i, T_i | lambda, mu) N2((log lambda, log mu); m_i, Sigma_12) dlog lambda dlog mu
+ * m_ij = sum_k X_ik beta_kj, k ascending, X_i0 = 1; cov [(K - 1)][n] (NULL for K = 1).  With log_s
+ * (D = 3 only) the integrand is multiplied by N(log_s_i; m_i3 + c (theta - m_i,12), v), c = Sigma_3,12
+ * Sigma_12^-1, v = Sigma_33 - c Sigma_12,3 + omega2: one observation log_s ~ N(log eta, omega2) with eta
+ * integrated out analytically.  With D = 3 and log_s NULL only beta's first two columns and Sigma's
+ * leading 2 x 2 block are read.  The dropped-out and the alive component of L (both log-concave in
+ * theta) are integrated separately and joined by logaddexp; each by CLV_MARGINAL_NEWTON damped Newton
+ * steps from m_i to its mode and the adaptive Gauss-Hermite rule of `nodes` points per dimension
+ * (8, 16, 24, 32; 0 = CLV_MARGINAL_DEFAULT_NODES) centred there and scaled by the Cholesky factor of
+ * the inverse negative Hessian (csrc/marginal.hip's header has every operation in order; no
+ * multiply-add is contracted).  out [n_records][n]: the (S, N) layout of clv_pointwise_loglik.  A
+ * record whose Sigma_12 is not positive definite (or whose v is not positive), or a non-finite
+ * input, gives NaN in that cell alone.  Each cell is a function of that customer and that record
+ * only: the bits depend neither on the grid nor on how the customers are batched or sharded.
+ * CLV_EINVAL before any device call: a null pointer, D not 2 or 3, K not 1 .. 9, cov not matching K,
+ * log_s with D = 2, omega2 not finite and > 0 with log_s, nodes not 0, 8, 16, 24 or 32, n_records or
+ * n < 1, n_records > 2^20, n > 2^31 - 1. */
+#define CLV_MARGINAL_DEFAULT_NODES 32
+#define CLV_MARGINAL_NEWTON 16
+int clv_marginal_loglik(int32_t device, const double* level2, int32_t D, int32_t K,
+                        const double* cov /* [K - 1][n] or NULL */, int64_t n_records, int64_t n, const int32_t* x,
+                        const double* t_x, const double* T_cal, const double* log_s /* NULL: no spend term */,
+                        double omega2, int32_t nodes, double* out);
+/* clv_marginal_loglik and clv_psis_loo fused (the same bits): the matrix stays on the device.  out
+ * [n][CLV_N_IC_STATS]; a customer with a NaN cell is NaN in all seven.  Also CLV_EINVAL: n_records
+ * outside clv_psis_loo's range of draws, reff not finite and > 0 or giving too long a tail. */
+int clv_marginal_information_criteria(int32_t device, const double* level2, int32_t D, int32_t K, const double* cov,
+                                      int64_t n_records, int64_t n, const int32_t* x, const double* t_x,
+                                      const double* T_cal, const double* log_s, double omega2, int32_t nodes,
+                                      double reff, double* out);
+/* From the level-2 records a sampler holds in HBM after its run and the data and covariates it was
+ * created with (CLV_ESTATE as clv_ppc_sampler at level 1; spend != 0 needs a trivariate sampler). */
+int clv_marginal_information_criteria_sampler(clv_sampler* s, int32_t spend, double omega2, double reff, int32_t nodes,
+                                              double* out);
+/* out[0 .. 3] the supported orders, out[4] the default, out[5] the Newton steps per component, out[6]
+ * customers per workgroup (256), out[7] the most records; of the kernel the calling thread's last
+ * clv_marginal* call launched (-1 before one): out[8] VGPRs and out[9] scratch bytes per lane
+ * (hipFuncGetAttributes), out[10] the device time of the call's quadrature kernels in ns. */
+int clv_marginal_info(int64_t* out);
+/* clv_marginal_loglik with batch_customers (> 0: customers per launch, rounded up to whole
+ * 256-customer blocks) and grid (> 0: the most workgroups per launch) overridden — the tests' knobs,
+ * the results do not depend on them — and out_centre (NULL or [n_records][n][12]): per component,
+ * the dropped-out one first, the centre (log lambda, log mu), the three entries L00, L10, L11 of the
+ * scale and the first Newton step that moved neither coordinate by 1e-9 (CLV_MARGINAL_NEWTON if none). */
+int clv_debug_marginal_loglik(int32_t device, const double* level2, int32_t D, int32_t K, const double* cov,
+                              int64_t n_records, int64_t n, const int32_t* x, const double* t_x, const double* T_cal,
+                              const double* log_s, double omega2, int32_t nodes, int64_t batch_customers, int32_t grid,
+                              double* out, double* out_centre);
+
 /* ---- Convergence diagnostics on device (csrc/diag.hip) ----
  * The reference checks convergence with ArviZ on its level-2 draws (bivariate/analysis_abe.py:
  * 651-706: az.summary, az.plot_autocorr).  Here a series is m chains x n draws (n >= 8) of one

@@ -31,6 +31,9 @@ number of holdout purchases, marginal over z and tau, with its mean, P(alive), q
 PIT and ranked probability score (forecast, forecast_pit, compare_forecasts, forecast_table).
 Posterior predictive checks of the calibration data, replicated per draw at the customer or at the
 population level: frequency histogram, p-values, per-customer PITs (posterior_predictive_check, ppc_pit).
+The marginal likelihood of a customer under each level-2 record — its own (lambda, mu) integrated out
+by adaptive Gauss-Hermite quadrature — and WAIC / PSIS-LOO and out-of-sample log scores from it
+(marginal_log_likelihood, marginal_information_criteria, marginal_log_score).
 
 The per-sweep work runs in hand-written HIP kernels for gfx950 (csrc/), bound through the C
 ABI in include/clvmcmc.h.  There is no CPU fallback.
@@ -42,7 +45,8 @@ from .analysis import (chain_total_loglik, compare_forecasts, compare_models, co
                        level2_summary, lifetime_value, lifetime_value_elasticities, pointwise_log_likelihood,
                        post_mean_lambdas, post_mean_mus, posterior_predictive_check, posterior_weekly_tracking, ppc_pit,
                        psis_loo, score_customers,
-                       summarize_level2, summary_rhat)
+                       summarize_level2, summary_rhat,
+                       marginal_information_criteria, marginal_log_likelihood, marginal_log_score)
 from .bivariate import mcmc_draw_parameters
 from .mle import ParetoNBDFitter, mape_aggregate, pnbd_weekly_tracking
 from .trivariate import mcmc_draw_parameters_rfm_m
@@ -55,5 +59,6 @@ __all__ = ["mcmc_draw_parameters", "mcmc_draw_parameters_rfm_m", "draw_future_tr
            "pnbd_weekly_tracking", "mape_aggregate", "lifetime_value", "customer_equity",
            "lifetime_value_elasticities", "pointwise_log_likelihood", "information_criteria", "psis_loo",
            "compare_models", "score_customers", "forecast", "forecast_pit", "compare_forecasts",
-           "forecast_table", "posterior_predictive_check", "ppc_pit"]
+           "forecast_table", "posterior_predictive_check", "ppc_pit", "marginal_log_likelihood",
+           "marginal_information_criteria", "marginal_log_score"]
 __version__ = "0.1.0"

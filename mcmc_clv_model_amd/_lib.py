@@ -181,6 +181,14 @@ def lib() -> ctypes.CDLL:
         "clv_debug_ppc": (c_int32, [c_int32, c_int32, dp, c_int32, dp, c_int32, c_int32, dp, c_int64, c_int64,
                                     POINTER(c_int32), dp, dp, c_int32, c_uint64, c_int64, dp, POINTER(c_int64), dp,
                                     POINTER(c_int64), dp, c_int64, c_int32]),
+        "clv_marginal_loglik": (c_int32, [c_int32, dp, c_int32, c_int32, dp, c_int64, c_int64, POINTER(c_int32), dp,
+                                          dp, dp, c_double, c_int32, dp]),
+        "clv_marginal_information_criteria": (c_int32, [c_int32, dp, c_int32, c_int32, dp, c_int64, c_int64,
+                                                        POINTER(c_int32), dp, dp, dp, c_double, c_int32, c_double, dp]),
+        "clv_marginal_information_criteria_sampler": (c_int32, [sp, c_int32, c_double, c_double, c_int32, dp]),
+        "clv_marginal_info": (c_int32, [POINTER(c_int64)]),
+        "clv_debug_marginal_loglik": (c_int32, [c_int32, dp, c_int32, c_int32, dp, c_int64, c_int64, POINTER(c_int32),
+                                                dp, dp, dp, c_double, c_int32, c_int64, c_int32, dp, dp]),
         "clv_diagnostics": (c_int32, [c_int32, dp, c_int32, c_int64, c_int64, c_int32, c_uint32, dp]),
         "clv_diagnostics_sampler": (c_int32, [sp, c_uint32, dp, dp]),
         "clv_autocorr": (c_int32, [c_int32, dp, c_int32, c_int64, c_int64, c_int32, dp]),
@@ -311,6 +319,24 @@ def ppc_info() -> dict:
     check(lib().clv_ppc_info(out))
     keys = ("block", "max_k", "batch_doubles", "vgprs", "scratch_bytes", "kernel_ns")
     return {k: int(v) for k, v in zip(keys, out)}
+
+
+# The limits of csrc/marginal.hip (clv_marginal_info reports the library's own; tests/test_marginal_cpu.py
+# compares): the supported Gauss-Hermite orders and the default, the Newton steps per component,
+# customers per workgroup, the most level-2 records, the doubles of one (record, customer) centre.
+MARGINAL_ORDERS, MARGINAL_DEFAULT_NODES, MARGINAL_NEWTON, MARGINAL_BLOCK, MARGINAL_MAX_RECORDS, MARGINAL_CENTRE = (
+    (8, 16, 24, 32), 32, 16, 256, 1 << 20, 12)
+
+
+def marginal_info() -> dict:
+    """clv_marginal_info: the limits of csrc/marginal.hip and, of the quadrature kernel this thread's
+    last marginal-likelihood call launched (-1 before one), VGPRs and scratch bytes per lane and the
+    device time of the call's quadrature kernels in ns."""
+    out = (c_int64 * 11)()
+    check(lib().clv_marginal_info(out))
+    return dict(orders=tuple(int(v) for v in out[0:4]), default_nodes=int(out[4]), newton=int(out[5]),
+                block=int(out[6]), max_records=int(out[7]), vgprs=int(out[8]), scratch_bytes=int(out[9]),
+                kernel_ns=int(out[10]))
 
 
 def exported_symbols():

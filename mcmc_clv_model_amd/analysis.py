@@ -34,6 +34,9 @@ Reference functions mirrored (same names, arguments, defaults and return layout)
   ``az.from_dict`` objects never get: the calibration data replicated per draw at the customer or at
   the population level (``csrc/ppc.hip``), the actual-vs-replicated frequency histogram, posterior
   predictive p-values and per-customer calibration PITs.
+* ``marginal_log_likelihood``, ``marginal_information_criteria``, ``marginal_log_score`` — ``az.loo`` on a
+  likelihood that is marginal over the customer's own (lambda, mu) (``csrc/marginal.hip``): one 2-D
+  adaptive Gauss-Hermite quadrature per (customer, level-2 record), the statistics of ``csrc/ic.hip``.
 
 The per-customer / per-draw work runs in ``csrc/analysis.hip`` through the C ABI (``clv_predict``,
 ``clv_track``, ``clv_level1_summary``, ``clv_chain_total_loglik``); the host only reshapes and
@@ -59,7 +62,8 @@ __all__ = ["draw_future_transactions", "draw_future_transactions_rfm_m", "post_m
            "summary_rhat", "level1_rank_diagnostics", "level2_rank_diagnostics", "level2_summary",
            "lifetime_value", "customer_equity", "lifetime_value_elasticities",
            "pointwise_log_likelihood", "information_criteria", "psis_loo", "compare_models", "score_customers",
-           "forecast", "forecast_pit", "compare_forecasts", "forecast_table", "posterior_predictive_check", "ppc_pit"]
+           "forecast", "forecast_pit", "compare_forecasts", "forecast_table", "posterior_predictive_check", "ppc_pit",
+           "marginal_log_likelihood", "marginal_information_criteria", "marginal_log_score"]
 
 
 def _stacked_level1(level1_chains) -> np.ndarray:
@@ -716,11 +720,19 @@ def compare_models(models: Dict[str, Dict[str, Any]], criterion: str = "loo") ->
     one row per model, best first, with rank, elpd, p, ``elpd_diff`` = the best model's elpd minus
     this one's, ``dse = sqrt(N var(elpd_i - elpd_best,i, ddof 0))`` — the standard error of that
     difference from the paired per-customer values — se, n_bad_k and warning.  Host numpy on the
-    frames of :func:`information_criteria`; ValueError on unequal customer counts."""
+    frames of :func:`information_criteria`; ValueError on unequal customer counts.  Entries of
+    :func:`marginal_information_criteria` (and ``ParetoNBDFitter.information_criteria``) carry
+    ``"kind": "marginal"``; entries without the key are conditional, and a mix of the two kinds is
+    refused with a ValueError that names both: their pointwise terms are different likelihoods."""
     if criterion not in ("loo", "waic"):
         raise ValueError(f"criterion must be 'loo' or 'waic' (got {criterion!r})")
     if not models:
         raise ValueError("no model to compare")
+    kinds = {k: m.get("kind", "conditional") for k, m in models.items()}
+    if len(set(kinds.values())) > 1:
+        groups = {kind: sorted(k for k in kinds if kinds[k] == kind) for kind in sorted(set(kinds.values()))}
+        raise ValueError("marginal and conditional criteria are not comparable (the pointwise terms are different "
+                         f"likelihoods): {groups}")
     col = "elpd_" + criterion
     point = {k: m["pointwise"][col].to_numpy() for k, m in models.items()}
     sizes = {len(v) for v in point.values()}
@@ -738,6 +750,139 @@ def compare_models(models: Dict[str, Dict[str, Any]], criterion: str = "loo") ->
                          dse=float(np.sqrt(n * np.var(diff))), se=float(tot["se"]), n_bad_k=int(tot["n_bad_k"]),
                          warning=bool(tot["warning"])))
     return pd.DataFrame(rows, index=pd.Index(order, name="model"))
+
+
+# ---- the marginal likelihood and marginal WAIC / PSIS-LOO (csrc/marginal.hip) ------------------
+def marginal_nodes(nodes) -> int:
+    """``nodes`` of the marginal-likelihood functions as the C ABI's argument: None or 0 the default
+    order, else one of _lib.MARGINAL_ORDERS (ValueError)."""
+    if nodes is None:
+        return 0
+    q = int(nodes)
+    if q != nodes or q not in (0,) + tuple(_lib.MARGINAL_ORDERS):
+        raise ValueError(f"nodes must be None or one of {_lib.MARGINAL_ORDERS} (got {nodes!r})")
+    return q
+
+
+def marginal_problem(draws, cbs: pd.DataFrame, covariates, spend: bool, omega2):
+    """(level2 [R][width], D, K, x, t_x, T_cal, cov, log_s or None, omega2) of a marginal-likelihood
+    call: the chains' records stacked in order, the columns :func:`score_problem` takes (log_s only
+    with ``spend=True``), validated on the host (ValueError)."""
+    l2 = score_level2(draws)
+    level2 = np.ascontiguousarray(l2.reshape(-1, l2.shape[2]))
+    spend = bool(spend)
+    covariates = list(covariates or [])
+    K = 1 + len(covariates)
+    D = {2 * K + 3: 2, 3 * K + 6: 3}.get(int(level2.shape[1]))
+    if spend and D == 2:
+        raise ValueError("spend=True needs the trivariate model's records")
+    frame = cbs if (D != 3 or "log_s" in cbs) else cbs.assign(log_s=0.0)   # the column is read with spend only
+    D, K, x, t_x, T_cal, cov, log_s = score_problem(frame, covariates, level2.shape[1])
+    if spend and "log_s" not in cbs:
+        raise ValueError("spend=True needs a log_s column in cbs")
+    w2 = 1.0
+    if spend:
+        if omega2 is None:
+            if len(log_s) < 2:
+                raise ValueError("spend=True needs omega2 or at least two customers' log_s for its default")
+            omega2 = np.var(log_s, ddof=1)
+        w2 = float(omega2)
+        if not (np.isfinite(w2) and w2 > 0.0):
+            raise ValueError(f"omega2 must be finite and > 0 (got {omega2!r})")
+    elif omega2 is not None:
+        raise ValueError("omega2 belongs to the spend term (spend=True)")
+    if level2.shape[0] > _lib.MARGINAL_MAX_RECORDS:
+        raise ValueError(f"{level2.shape[0]} level-2 records: the marginal likelihood takes at most "
+                         f"{_lib.MARGINAL_MAX_RECORDS}")
+    return level2, D, K, x, t_x, T_cal, cov, (log_s if spend else None), w2
+
+
+def marginal_log_likelihood(draws, cbs: pd.DataFrame, covariates=None, *, spend: bool = False, omega2=None,
+                            nodes=None, device: int = -1) -> np.ndarray:
+    """The log of the marginal likelihood of every customer under every level-2 record, on the GPU
+    (``csrc/marginal.hip``, ``clv_marginal_loglik``): float64 (R, N), R the records of all chains
+    stacked in order — the layout of :func:`pointwise_log_likelihood`, so :func:`psis_loo` reads it.
+
+        p(y_i | beta, Sigma) = int int L(x_i, t_x,i, T_i | lambda, mu) N2((log lambda, log mu); beta' d_i, Sigma_12)
+
+    The customer's own (lambda, mu) is integrated out against the record's population distribution,
+    so no level-1 draws are needed and ``cbs`` may hold the fit's own customers or new ones (the
+    columns :func:`score_customers` takes: x, t_x, T_cal, the ``covariates``).  ``spend=True``
+    (trivariate records, a log_s column) multiplies in one observation log_s ~ N(log eta, omega2) with
+    eta integrated out analytically; ``omega2`` defaults to ``var(cbs["log_s"], ddof=1)``.
+    ``spend=False`` on trivariate records reads the transaction block alone, comparable with a
+    bivariate fit.
+
+    ``nodes``: the points per dimension of the adaptive Gauss-Hermite rule, one of 8, 16, 24, 32
+    (None: the default, _lib.MARGINAL_DEFAULT_NODES).  DESIGN.md section 4k records the quadrature
+    error each order reaches against the exact integral: the default, 32, is the smallest order within
+    1e-6 of it on every customer of the fixture under CDNOW-like population distributions (24 reaches
+    2.9e-6); under much wider ones (Sigma_11 = 3, Sigma_22 = 6) no supported order reaches 1e-6 on
+    every edge customer (32 reaches 1.2e-5).
+    A record whose Sigma_12 is not positive definite gives NaN in its row; a non-finite t_x or T_cal
+    in that customer's column.  Arguments are checked before any device is touched."""
+    level2, D, K, x, t_x, T_cal, cov, log_s, w2 = marginal_problem(draws, cbs, covariates, spend, omega2)
+    q = marginal_nodes(nodes)
+    L = _L()
+    out = np.empty((level2.shape[0], x.shape[0]), np.float64)
+    check(L.clv_marginal_loglik(int(device), dptr(level2), D, K, dptr(cov), level2.shape[0], x.shape[0], _i32p(x),
+                                dptr(t_x), dptr(T_cal), dptr(log_s), w2, q, dptr(out)))
+    return out
+
+
+def marginal_frames(stats: np.ndarray, n_samples: int) -> dict:
+    """:func:`ic_frames` of marginal criteria: the same dict plus ``"kind": "marginal"``."""
+    out = ic_frames(stats, n_samples)
+    out["kind"] = "marginal"
+    return out
+
+
+def marginal_information_criteria(draws, cbs: pd.DataFrame, covariates=None, *, spend: bool = False, omega2=None,
+                                  reff: float = 1.0, nodes=None, device: int = -1) -> Dict[str, Any]:
+    """WAIC and PSIS-LOO of a fit from the marginal likelihood (:func:`marginal_log_likelihood`)
+    instead of the likelihood conditional on each customer's own (lambda, mu), on the GPU
+    (``clv_marginal_information_criteria``: the matrix never leaves the device; the same bits as
+    :func:`psis_loo` of it).  With one observation and one parameter pair per customer the conditional
+    importance ratios of :func:`information_criteria` have no usable tail (Vehtari et al. 2017,
+    section 2.4; Merkle, Furr & Rabe-Hesketh 2019); leaving a customer out of the marginal
+    likelihood perturbs only the posterior of (beta, Sigma).
+
+    Returns the dict of :func:`ic_frames` plus ``"kind": "marginal"``, which :func:`compare_models`
+    takes as it is — among marginal entries only (``ParetoNBDFitter.information_criteria`` is one)."""
+    level2, D, K, x, t_x, T_cal, cov, log_s, w2 = marginal_problem(draws, cbs, covariates, spend, omega2)
+    q = marginal_nodes(nodes)
+    par = ic_params(False, None, reff)
+    R, n = level2.shape[0], x.shape[0]
+    _ic_shape(R, n, 4, False, par["reff"])
+    L = _L()
+    out = np.empty((n, len(_lib.IC_STATS)), np.float64)
+    check(L.clv_marginal_information_criteria(int(device), dptr(level2), D, K, dptr(cov), R, n, _i32p(x), dptr(t_x),
+                                              dptr(T_cal), dptr(log_s), w2, q, par["reff"], dptr(out)))
+    return marginal_frames(out, R)
+
+
+def marginal_log_score(draws, cbs_new: pd.DataFrame, covariates=None, *, spend: bool = False, omega2=None,
+                       nodes=None, device: int = -1) -> Dict[str, Any]:
+    """The out-of-sample log score of customers the fit has not seen, without running any MH: per
+    customer ``log_score = logsumexp_r l_marg[r] - log R`` over the R level-2 records (the maximum
+    over the records, then the terms added in record order) — the log of the posterior predictive
+    density of that customer's (x, t_x [, log_s]) — and in total with its standard error
+    ``sqrt(N var(., ddof 0))``, both through :func:`fixed_order_sum`.
+
+    Returns ``{"pointwise": DataFrame(log_score), "total": one-row DataFrame (log_score, se,
+    n_records, n_customers)}``."""
+    lm = marginal_log_likelihood(draws, cbs_new, covariates, spend=spend, omega2=omega2, nodes=nodes, device=device)
+    R, n = lm.shape
+    m = lm.max(axis=0)
+    acc = np.zeros(n)
+    for r in range(R):
+        acc = acc + np.exp(lm[r] - m)
+    score = (m + np.log(acc)) - np.log(float(R))
+    total = fixed_order_sum(score)
+    dev = score - total / n
+    se = float(np.sqrt(n * (fixed_order_sum(dev * dev) / n)))
+    return dict(pointwise=pd.DataFrame(dict(log_score=score)),
+                total=pd.DataFrame([dict(log_score=total, se=se, n_records=int(R), n_customers=int(n))]))
 
 
 # ---- the closed-form holdout forecast and its scores (csrc/forecast.hip) ---------------------

@@ -40,6 +40,10 @@ line and return layout (bivariate/mcmc.py:437-504); the sweeps run on the GPU
   or at the population level, with the frequency histogram, posterior predictive p-values and
   per-customer PIT columns, from the draws still in HBM (``csrc/ppc.hip``; ``draw_sink="full"`` only).
   None changes nothing.
+* ``marginal_information_criteria``: True, or a dict of ``analysis.marginal_information_criteria``'s
+  keywords (``spend``, ``omega2``, ``reff``, ``nodes``), adds ``out["marginal_information_criteria"]``: WAIC
+  and PSIS-LOO from the likelihood marginal over each customer's own (lambda, mu), from the level-2
+  records still in HBM (``csrc/marginal.hip``; ``draw_sink="full"`` only).  None changes nothing.
 """
 from __future__ import annotations
 
@@ -57,7 +61,7 @@ def mcmc_draw_parameters(cal_cbs, covariates: Optional[Sequence[str]] = None, mc
                          rng: str = "philox", device: int = -1, replay_tape=None,
                          replay_sweeps: Optional[int] = None, devices: Optional[Sequence[int]] = None,
                          shard: str = "auto", exchange: str = "auto", diagnostics=False, lifetime_value=None,
-                         information_criteria=None, forecast=None, ppc=None):
+                         information_criteria=None, forecast=None, ppc=None, marginal_information_criteria=None):
     """Run the Abe (2009) Gibbs/MH sampler on calibration CBS (bivariate/mcmc.py:437).
 
     Returns dict(level_1=[(n_draws, N, 4) per chain: lambda, mu, tau, z],
@@ -77,4 +81,5 @@ def mcmc_draw_parameters(cal_cbs, covariates: Optional[Sequence[str]] = None, mc
                replay_tape=replay_tape, replay_sweeps=replay_sweeps, devices=devices, shard=shard,
                exchange=exchange, diagnostics=diagnostics, lifetime_value=lifetime_value,
                information_criteria=information_criteria,
-               forecast=forecast_kwargs(forecast, draw_sink, cal_cbs), ppc=ppc)
+               forecast=forecast_kwargs(forecast, draw_sink, cal_cbs), ppc=ppc,
+               marginal_information_criteria=marginal_information_criteria)

@@ -34,6 +34,12 @@ inline int64_t lowered_by_env(const char* name, int64_t per) {
   return per;
 }
 
+// The statistics of clv_psis_loo from a matrix [n_draws][n] already on the device (ic.hip; marginal.hip
+// feeds it its own): ic_matrix_check is what needs no data (CLV_EINVAL before any device call),
+// ic_matrix_dev queues the work on st, copies out [n][CLV_N_IC_STATS] to the host and synchronises.
+int ic_matrix_check(int64_t n_draws, int64_t n, double reff);
+int ic_matrix_dev(const double* d_loglik, int64_t n_draws, int64_t n, double reff, double* out, hipStream_t st);
+
 // off[c] = c * len for c = 0 .. nc: the segment boundaries of nc segments of len keys.
 template <class Off>
 __global__ void seg_offsets_kernel(int64_t nc, int64_t len, Off* off) {

@@ -451,6 +451,22 @@ int ic_host(int32_t device, const double* level1, int64_t n_draws, int64_t n, in
 
 }  // namespace
 
+namespace clv {
+
+int ic_matrix_check(int64_t n_draws, int64_t n, double reff) {
+  int rc = check_shape(n_draws, n);
+  if (rc) return rc;
+  return check_reff(n_draws, reff);
+}
+
+int ic_matrix_dev(const double* d_loglik, int64_t n_draws, int64_t n, double reff, double* out, hipStream_t st) {
+  IcArgs A = make_args(n_draws, n, 0, false, 1.0);
+  A.ll = d_loglik;
+  return ic_dev(A, reff, 0, 0, out, st);
+}
+
+}  // namespace clv
+
 extern "C" {
 
 int clv_ic_info(int64_t* out) {
@@ -495,11 +511,9 @@ int clv_psis_loo(int32_t device, const double* loglik, int64_t n_draws, int64_t 
   if (rc) return rc;
   if (!loglik || !out) return fail(CLV_EINVAL, "null argument");
   DeviceScope ds(device);
-  IcArgs A = make_args(n_draws, n, 0, false, 1.0);
   DevBuf bl;
   if ((rc = upload(bl, loglik, (size_t)n_draws * n, nullptr))) return rc;
-  A.ll = (const double*)bl.p;
-  return ic_dev(A, reff, 0, 0, out, nullptr);
+  return ic_matrix_dev((const double*)bl.p, n_draws, n, reff, out, nullptr);
 }
 
 int clv_information_criteria(int32_t device, const double* level1, int64_t n_draws, int64_t n, int32_t width,

@@ -246,10 +246,52 @@ class ParetoNBDFitter:
     def conditional_probability_alive(self, frequency, recency, T) -> np.ndarray:
         return self._customers(0.0, frequency, recency, T)[:, 1].copy()
 
+    def pointwise_log_likelihood(self, frequency, recency, T) -> np.ndarray:
+        """log L per customer at the fitted parameters (column 0 of ``clv_pnbd_customers``): marginal
+        over the gamma heterogeneity of lambda and mu."""
+        return self._customers(0.0, frequency, recency, T)[:, 0].copy()
+
+    def information_criteria(self, frequency, recency, T) -> dict:
+        """The fitted model as an entry of ``analysis.compare_models`` beside the HB models'
+        ``analysis.marginal_information_criteria`` (:func:`mle_information_criteria` of
+        :meth:`pointwise_log_likelihood`).  The entry is IN-SAMPLE: elpd is the log-likelihood of the
+        customers the four parameters were fitted to, with the AIC-style penalty p = 4 spread evenly
+        (4 / N per customer) — no customer is left out, so it flatters the MLE by what four
+        parameters can overfit N customers, and pareto_k is NaN."""
+        return mle_information_criteria(self.pointwise_log_likelihood(frequency, recency, T))
+
     def expected_number_of_purchases_up_to_time(self, t):
         """E[X(t)] = r beta / alpha phi(s - 1, log((beta + t) / beta)), elementwise (host numpy)."""
         r, a, s, b = self._fitted()
         return r * b / a * phi(s - 1.0, np.log1p(np.asarray(t, np.float64) / b))
+
+
+def mle_information_criteria(loglik, n_params: int = 4) -> dict:
+    """An ``analysis.ic_frames``-shaped dict with ``"kind": "marginal"`` from the in-sample pointwise
+    log-likelihood of a maximum-likelihood fit: per customer lppd = log L_i, p_waic = p_loo =
+    n_params / N, elpd_waic = elpd_loo = log L_i - n_params / N, pareto_k and tail_len NaN; the totals
+    as ic_frames forms them (elpd = log L - n_params), n_samples = 1."""
+    from . import _lib
+    from .analysis import ic_frames
+    ll = np.asarray(loglik, np.float64).reshape(-1)
+    n = ll.shape[0]
+    if n < 1:
+        raise ValueError("no customer")
+    stats = np.full((n, len(_lib.IC_STATS)), np.nan)
+    pen = float(n_params) / n
+    for k, name in enumerate(_lib.IC_STATS):
+        if name == "lppd":
+            stats[:, k] = ll
+        elif name in ("p_waic", "p_loo"):
+            stats[:, k] = pen
+        elif name in ("elpd_waic", "elpd_loo"):
+            stats[:, k] = ll - pen
+    out = ic_frames(stats, 2)             # the count only sets the k threshold, and every k is NaN
+    for key in ("waic", "loo"):
+        out[key]["n_samples"] = 1
+        out[key]["warning"] = False    # no importance sampling, no pointwise variance: nothing to warn of
+    out["kind"] = "marginal"
+    return out
 
 
 def pnbd_weekly_tracking(fitter: ParetoNBDFitter, birth_week, times, *, device: int = -1) -> np.ndarray:

@@ -470,6 +470,23 @@ class HipSampler:
                                                        dptr(out)))
         return A.ic_frames(out, self.chains * self.n_draws)
 
+    def marginal_information_criteria(self, *, spend: bool = False, omega2=None, reff: float = 1.0,
+                                      nodes=None) -> dict:
+        """clv_marginal_information_criteria_sampler: analysis.marginal_information_criteria (WAIC and
+        PSIS-LOO from the likelihood marginal over each customer's own (lambda, mu)) of the level-2
+        records this sampler holds in HBM, with the data and covariates it was created with; the same
+        bits as the host-array route."""
+        from . import analysis as A
+        if spend and self.D != 3:
+            raise ValueError("spend=True needs the trivariate model (D = 3)")
+        par = A.ic_params(spend, omega2, reff, self.p.log_s)
+        A._ic_shape(self.chains * self.n_draws, self.n, self.D + 2, par["spend"], par["reff"])
+        out = np.empty((self.n, len(_lib.IC_STATS)), np.float64)
+        check(self._L.clv_marginal_information_criteria_sampler(
+            self.h, 1 if par["spend"] else 0, par["omega2"] if par["spend"] else 1.0, par["reff"],
+            A.marginal_nodes(nodes), dptr(out)))
+        return A.marginal_frames(out, self.chains * self.n_draws)
+
     def score_customers(self, cbs_new, covariates=None, *, inner_sweeps: int = 10, warmup: int = 50,
                         n_mh_steps: int = 20, seed: Optional[int] = 0, sink: str = "full", init=None,
                         customer_offset: int = 0, sweep_first: int = 1) -> dict:
@@ -638,7 +655,7 @@ def fit(p: Problem, *, mcmc: int, burnin: int, thin: int, chains: int, seed, tra
         draw_sink: str = "full", rng: str = "philox", device: int = -1, replay_tape=None,
         replay_sweeps: Optional[int] = None, devices: Optional[Sequence[int]] = None, shard: str = "auto",
         exchange: str = "auto", diagnostics=False, lifetime_value=None, information_criteria=None,
-        forecast=None, ppc=None) -> dict:
+        forecast=None, ppc=None, marginal_information_criteria=None) -> dict:
     """Run all chains of one problem in one batched launch sequence and return the reference's
     output layout (bi:499-504).  ``devices`` (two or more): the run is spread over those devices
     in this process (:func:`fit_multi`).  ``diagnostics``: also out["diagnostics"] = {"level_1",
@@ -657,7 +674,10 @@ def fit(p: Problem, *, mcmc: int, burnin: int, thin: int, chains: int, seed, tra
     routed the same way.
     ``ppc``: True or a dict of analysis.posterior_predictive_check's keywords (level, k_hist, seed,
     replicates) adds out["ppc"] (posterior predictive checks of the calibration data; full sink
-    only), routed the same way."""
+    only), routed the same way.
+    ``marginal_information_criteria``: True or a dict of analysis.marginal_information_criteria's
+    keywords (spend, omega2, reff, nodes) adds out["marginal_information_criteria"] (WAIC and PSIS-LOO
+    from the marginal likelihood; full sink only), routed the same way."""
     if chains < 1:
         raise ValueError("chains must be >= 1")
     if thin < 1:
@@ -670,6 +690,7 @@ def fit(p: Problem, *, mcmc: int, burnin: int, thin: int, chains: int, seed, tra
     ic_kw = information_criteria_kwargs(information_criteria, draw_sink, p.D)
     fc_kw = forecast_kwargs(forecast, draw_sink, n=p.N)
     ppc_kw = ppc_kwargs(ppc, draw_sink)
+    mic_kw = marginal_information_criteria_kwargs(marginal_information_criteria, draw_sink, p.D)
     if devices is not None:
         devices = [int(d) for d in devices]
         if not devices:
@@ -680,7 +701,8 @@ def fit(p: Problem, *, mcmc: int, burnin: int, thin: int, chains: int, seed, tra
             out = fit_multi(p, mcmc=mcmc, burnin=burnin, thin=thin, chains=chains, seed=seed, trace=trace,
                             n_mh_steps=n_mh_steps, draw_sink=draw_sink, devices=devices, shard=shard,
                             exchange=exchange, lifetime_value=lifetime_value,
-                            information_criteria=information_criteria, forecast=forecast, ppc=ppc)
+                            information_criteria=information_criteria, forecast=forecast, ppc=ppc,
+                            marginal_information_criteria=marginal_information_criteria)
             if diagnostics:
                 from . import analysis as A
                 out["diagnostics"] = dict(level_1=A.level1_diagnostics(out, device=devices[0]),
@@ -718,6 +740,8 @@ def fit(p: Problem, *, mcmc: int, burnin: int, thin: int, chains: int, seed, tra
             out["forecast"] = s.forecast(**fc_kw)
         if ppc_kw is not None:
             out["ppc"] = s.posterior_predictive_check(**ppc_kw)
+        if mic_kw is not None:
+            out["marginal_information_criteria"] = s.marginal_information_criteria(**mic_kw)
         return out
     finally:
         s.close()
@@ -769,6 +793,22 @@ def information_criteria_kwargs(information_criteria, draw_sink: str, D: int):
     return kw
 
 
+def marginal_information_criteria_kwargs(marginal_information_criteria, draw_sink: str, D: int):
+    """The ``marginal_information_criteria=`` keyword of the fit functions as
+    analysis.marginal_information_criteria's keywords (None: not asked for), validated before the run
+    starts."""
+    kw = analysis_kwargs("marginal_information_criteria", marginal_information_criteria, draw_sink,
+                         ("spend", "omega2", "reff", "nodes"))
+    if kw is None:
+        return None
+    from . import analysis as A
+    if kw.get("spend") and D != 3:
+        raise ValueError("spend=True needs the trivariate model (D = 3)")
+    A.ic_params(kw.get("spend", False), kw.get("omega2", 1.0 if kw.get("spend") else None), kw.get("reff", 1.0))
+    A.marginal_nodes(kw.get("nodes"))
+    return kw
+
+
 def forecast_kwargs(forecast, draw_sink: str, cbs=None, n=None):
     """The ``forecast=`` keyword of the fit functions as analysis.forecast's keywords (None: not asked
     for), validated before the run starts; an ``x_star`` given as a column name is taken from
@@ -815,7 +855,8 @@ def multi_plan(chains: int, n_dev: int, draw_sink: str, shard: str = "auto"):
 
 def fit_multi(p: Problem, *, mcmc: int, burnin: int, thin: int, chains: int, seed, trace: int, n_mh_steps: int,
               draw_sink: str, devices: Sequence[int], shard: str = "auto", exchange: str = "auto",
-              lifetime_value=None, information_criteria=None, forecast=None, ppc=None) -> dict:
+              lifetime_value=None, information_criteria=None, forecast=None, ppc=None,
+              marginal_information_criteria=None) -> dict:
     """One run over several devices of this process (SURVEY §8b ``devices=``), same output as the
     single-device run, bit for bit:
 
@@ -829,13 +870,14 @@ def fit_multi(p: Problem, *, mcmc: int, burnin: int, thin: int, chains: int, see
     * ``"auto"``: chains when they divide evenly over the devices (and the sink is not
       "summary+pct", whose percentiles pool all chains), else customers.
 
-    ``lifetime_value``, ``information_criteria``, ``forecast``, ``ppc``: as :func:`fit`, computed from the returned arrays
-    on ``devices[0]``."""
+    ``lifetime_value``, ``information_criteria``, ``forecast``, ``ppc``, ``marginal_information_criteria``: as
+    :func:`fit`, computed from the returned arrays on ``devices[0]``."""
     import threading
     ltv_kw = lifetime_value_kwargs(lifetime_value, draw_sink)
     ic_kw = information_criteria_kwargs(information_criteria, draw_sink, p.D)
     fc_kw = forecast_kwargs(forecast, draw_sink, n=p.N)
     ppc_kw = ppc_kwargs(ppc, draw_sink)
+    mic_kw = marginal_information_criteria_kwargs(marginal_information_criteria, draw_sink, p.D)
 
     def finish(out):
         if ltv_kw is not None:
@@ -864,6 +906,17 @@ def fit_multi(p: Problem, *, mcmc: int, burnin: int, thin: int, chains: int, see
             if p.log_s is not None:
                 cbs["log_s"] = p.log_s
             out["ppc"] = A.posterior_predictive_check(out, pd.DataFrame(cbs), names, device=int(devices[0]), **ppc_kw)
+        if mic_kw is not None:
+            from . import analysis as A
+            import pandas as pd
+            cbs = dict(x=p.x, t_x=p.t_x, T_cal=p.T_cal)
+            names = [f"cov{k}" for k in range(1, p.K)]
+            for k, nm in enumerate(names):
+                cbs[nm] = p.cov[k]
+            if p.log_s is not None:
+                cbs["log_s"] = p.log_s
+            out["marginal_information_criteria"] = A.marginal_information_criteria(
+                out, pd.DataFrame(cbs), names, device=int(devices[0]), **mic_kw)
         return out
 
     n_dev = len(devices)

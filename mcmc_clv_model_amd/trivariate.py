@@ -21,7 +21,7 @@ def mcmc_draw_parameters_rfm_m(cal_cbs, covariates: Optional[Sequence[str]] = No
                                replay_tape=None, replay_sweeps: Optional[int] = None,
                                devices: Optional[Sequence[int]] = None, shard: str = "auto", exchange: str = "auto",
                                diagnostics=False, lifetime_value=None, information_criteria=None, forecast=None,
-                               ppc=None):
+                               ppc=None, marginal_information_criteria=None):
     """3-dimensional HB Pareto/NBD + spend sampler (trivariate/mcmc.py:580).
 
     Returns {"level_1": [(n_draws, N, 5) per chain: lambda, mu, tau, z, eta],
@@ -35,6 +35,7 @@ def mcmc_draw_parameters_rfm_m(cal_cbs, covariates: Optional[Sequence[str]] = No
               replay_tape=replay_tape, replay_sweeps=replay_sweeps, devices=devices, shard=shard,
               exchange=exchange, diagnostics=diagnostics, lifetime_value=lifetime_value,
               information_criteria=information_criteria,
-              forecast=forecast_kwargs(forecast, draw_sink, cal_cbs), ppc=ppc)
+              forecast=forecast_kwargs(forecast, draw_sink, cal_cbs), ppc=ppc,
+               marginal_information_criteria=marginal_information_criteria)
     out["log_likelihood"] = float(out["log_likelihood"])  # tri:652 returns a Python float
     return out
