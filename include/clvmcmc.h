@@ -881,6 +881,53 @@ int clv_pnbd_customers(clv_pnbd* h, const double* params, double t_star, double*
 int clv_pnbd_track(int32_t device, int64_t n, const double* birth_week, const double* times, int32_t n_times,
                    const double* params, double* cum);
 
+/* ---- Many small fits in one launch (csrc/batch.hip) ----
+ * Replaces a host loop of whole runs, bi:346-431 / tri:465-574 once per fit and chain: n_fits
+ * independent problems of one (D, K), each with its own customers, prior constants and seed, are
+ * uploaded together, run by ONE kernel launch and read back; no handle outlives the call.  One
+ * 256-thread workgroup per (fit, chain) runs that chain from the initial state (bi:367-379,
+ * tri:488-504) through all burnin + mcmc sweeps: per sweep it walks the fit's tiles of CLV_BLOCK
+ * customers in order (z bi:388, tau bi:390, level-1 MH bi:396, eta tri:524-526, storage
+ * bi:402-428), writes each tile's block partial, and draws level 2 (bi:393, tri:529) from the
+ * partials summed in the fixed order of every other path — so fit j's outputs are, bit for bit,
+ * those of clv_create + clv_run + clv_read_draws / clv_read_summary on fit j alone with
+ * chain_first = 0 (production Philox mode).  No workgroup waits for another.
+ * Per fit (clv_batch_item, host pointers): n in [1, 512 CLV_BLOCK], seed, the CBS columns,
+ * covariates [(K - 1)][n] (NULL for K = 1), log_s (D = 3 only), the prior; outputs level1
+ * [chain][n_draws][n][D + 2] (CLV_SINK_FULL), level2 [chain][n_draws][D K + D (D + 1) / 2], loglik
+ * [chain][n_draws], sums [chain][CLV_N_SUM_STATS][n] (CLV_SINK_SUMMARY; all n_draws stored draws
+ * are in them), and, optional, the final state state_lam / state_mu [chain][n].
+ * draw_sink: CLV_SINK_FULL, CLV_SINK_SUMMARY or CLV_SINK_NONE.  *kernel_ms (may be NULL): the
+ * kernel's device time by hipEvents.  CLV_EINVAL before any allocation when the buffers of the
+ * sink exceed the free device memory (hipMemGetInfo); the message names the bytes needed.
+ * clv_batch_plan (host only): seg_offsets [n_fits + 1] customers before each fit in the
+ * concatenated arrays, tiles [n_fits], wg_map [n_fits * n_chains][2] = (fit, chain) of every
+ * workgroup, fits with the most tiles first (stable).
+ * clv_batch_info: out[5] = VGPRs, scratch bytes per lane, workgroups per CU of the (D, K)
+ * instance, slots = CUs x workgroups per CU, CUs (of the current device). */
+typedef struct clv_batch_item {
+  int64_t n;
+  uint64_t seed;
+  const int32_t* x;
+  const double* t_x;
+  const double* T_cal;
+  const double* covariates;
+  const double* log_s;
+  const clv_prior* prior;
+  double* level1;
+  double* level2;
+  double* loglik;
+  double* sums;
+  double* state_lam;
+  double* state_mu;
+} clv_batch_item;
+int clv_batch_fit(int32_t device, int32_t D, int32_t K, int32_t n_mh_steps, int32_t n_chains, int32_t burnin,
+                  int32_t mcmc, int32_t thin, int32_t draw_sink, int64_t n_fits, const clv_batch_item* fits,
+                  double* kernel_ms);
+int clv_batch_plan(int64_t n_fits, const int64_t* n, int32_t n_chains, int64_t* seg_offsets, int32_t* tiles,
+                   int32_t* wg_map);
+int clv_batch_info(int32_t D, int32_t K, int64_t* out);
+
 #ifdef __cplusplus
 }
 #endif

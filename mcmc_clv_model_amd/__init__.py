@@ -34,6 +34,10 @@ population level: frequency histogram, p-values, per-customer PITs (posterior_pr
 The marginal likelihood of a customer under each level-2 record — its own (lambda, mu) integrated out
 by adaptive Gauss-Hermite quadrature — and WAIC / PSIS-LOO and out-of-sample log scores from it
 (marginal_log_likelihood, marginal_information_criteria, marginal_log_score).
+Many small fits at once — the training sets of a cross-validation, fits per cohort, bootstrap or
+simulation studies — run in one kernel launch with the single calls' bits (mcmc_draw_parameters_many,
+mcmc_draw_parameters_rfm_m_many), and exact K-fold cross-validation on top of them
+(kfold_cross_validation).
 
 The per-sweep work runs in hand-written HIP kernels for gfx950 (csrc/), bound through the C
 ABI in include/clvmcmc.h.  There is no CPU fallback.
@@ -47,6 +51,7 @@ from .analysis import (chain_total_loglik, compare_forecasts, compare_models, co
                        psis_loo, score_customers,
                        summarize_level2, summary_rhat,
                        marginal_information_criteria, marginal_log_likelihood, marginal_log_score)
+from .batch import kfold_cross_validation, mcmc_draw_parameters_many, mcmc_draw_parameters_rfm_m_many
 from .bivariate import mcmc_draw_parameters
 from .mle import ParetoNBDFitter, mape_aggregate, pnbd_weekly_tracking
 from .trivariate import mcmc_draw_parameters_rfm_m
@@ -60,5 +65,6 @@ __all__ = ["mcmc_draw_parameters", "mcmc_draw_parameters_rfm_m", "draw_future_tr
            "lifetime_value_elasticities", "pointwise_log_likelihood", "information_criteria", "psis_loo",
            "compare_models", "score_customers", "forecast", "forecast_pit", "compare_forecasts",
            "forecast_table", "posterior_predictive_check", "ppc_pit", "marginal_log_likelihood",
-           "marginal_information_criteria", "marginal_log_score"]
+           "marginal_information_criteria", "marginal_log_score", "mcmc_draw_parameters_many",
+           "mcmc_draw_parameters_rfm_m_many", "kfold_cross_validation"]
 __version__ = "0.1.0"

@@ -58,6 +58,16 @@ class ClvPrior(ctypes.Structure):
     ]
 
 
+class ClvBatchItem(ctypes.Structure):
+    """clv_batch_item: one fit of clv_batch_fit (host pointers; outputs it does not want are None)."""
+    _fields_ = [
+        ("n", c_int64), ("seed", c_uint64), ("x", c_void_p), ("t_x", c_void_p), ("T_cal", c_void_p),
+        ("covariates", c_void_p), ("log_s", c_void_p), ("prior", POINTER(ClvPrior)),
+        ("level1", c_void_p), ("level2", c_void_p), ("loglik", c_void_p), ("sums", c_void_p),
+        ("state_lam", c_void_p), ("state_mu", c_void_p),
+    ]
+
+
 _lib = None
 
 
@@ -206,6 +216,11 @@ def lib() -> ctypes.CDLL:
         "clv_pnbd_eval": (c_int32, [sp, dp, dp, POINTER(c_int64)]),
         "clv_pnbd_customers": (c_int32, [sp, dp, c_double, dp]),
         "clv_pnbd_track": (c_int32, [c_int32, c_int64, dp, dp, c_int32, dp, dp]),
+        "clv_batch_fit": (c_int32, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                    c_int64, POINTER(ClvBatchItem), dp]),
+        "clv_batch_plan": (c_int32, [c_int64, POINTER(c_int64), c_int32, POINTER(c_int64), POINTER(c_int32),
+                                     POINTER(c_int32)]),
+        "clv_batch_info": (c_int32, [c_int32, c_int32, POINTER(c_int64)]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)
@@ -337,6 +352,21 @@ def marginal_info() -> dict:
     return dict(orders=tuple(int(v) for v in out[0:4]), default_nodes=int(out[4]), newton=int(out[5]),
                 block=int(out[6]), max_records=int(out[7]), vgprs=int(out[8]), scratch_bytes=int(out[9]),
                 kernel_ns=int(out[10]))
+
+
+# Many fits in one launch (csrc/batch.hip): the most 256-customer tiles of a fit the batch kernel takes
+# (one block per unit, as clv_default_blocks_per_unit gives up to here), and the most tiles at which
+# mcmc_draw_parameters_many routes a fit to it by default: the largest T of the tile sweep of
+# tools/profile_batch.py at which the full-card batch beat the loop of single fits by 2 in wall time
+# (profiles/batch_fits.json).  Measured on one MI355X, bivariate K = 2, 4 chains,
+# 2,000 sweeps, summary sink; ratio = wall time of the loop of single calls / wall time of the one call:
+#   tiles per fit            1     2     4     8    16    32    64
+#   256 fits (full card)  22.3  18.1  12.7   8.4   4.7   2.7   1.7
+#   4 fits                 2.25  1.55  0.98  0.56  0.30  0.16  0.10
+# 32 is the largest with the full-card ratio >= 2; with 4 fits the batch loses there by 6 x (the rule
+# looks at one fit at a time: pass max_blocks for a short list of large fits).
+BATCH_TILE_LIMIT = 512
+BATCH_MAX_BLOCKS = 32
 
 
 def exported_symbols():

@@ -64,6 +64,15 @@ hipError_t launch_score(const SweepArgs& a, const ScoreArgs& e, bool summary, hi
                         hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
 hipError_t score_resources(int D, int K, bool summary, int* vgprs, size_t* scratch_bytes);
 
+// Many small fits in one launch (kernels.hip batch_fit_kernel; host side in batch.hip).
+// launch_batch_fit: one workgroup per entry of wg_map [(fit, chain)], fits / wg_map / init_bs on the
+// device, sweeps 1 .. n_sweeps, optional events around the kernel.  batch_fit_resources: VGPRs and
+// scratch bytes per lane and workgroups per CU of the (D, K) instance.
+hipError_t launch_batch_fit(int D, int K, const SweepArgs* fits, const int2* wg_map, const double* init_bs,
+                            int64_t n_wgs, int64_t n_sweeps, hipStream_t st, hipEvent_t e0 = nullptr,
+                            hipEvent_t e1 = nullptr);
+hipError_t batch_fit_resources(int D, int K, int* vgprs, size_t* scratch_bytes, int* blocks_per_cu);
+
 template <class T>
 hipError_t dalloc(T** p, size_t count) {
   *p = nullptr;

@@ -3644,6 +3644,122 @@ __global__ __launch_bounds__(BLOCK) void score_kernel(SweepArgs a, ScoreArgs e) 
 }
 
 // ---------------------------------------------------------------------------------------------
+// Many small fits in one launch (batch.hip): one 256-thread workgroup per (fit,
+// chain) runs that chain from its initial state to its last sweep.  Per sweep the workgroup walks
+// the fit's tiles of 256 customers in order — the launch-per-sweep kernel's customer path (cust_load
+// .. cust_finish, block_reduce_gen, the block partial into slot b, cust_store) — then draws level 2
+// itself with hyper_body (mode 2: no sweep counter), which sums the partials in hyper_sum_units'
+// fixed order: the same partials, the same order, so the same bits as every single-fit path.
+// Nothing here waits for another workgroup: no ticket, no poll, no residency precondition.  The
+// only cross-lane traffic is the workgroup's LDS and its own partial slots and hyper block, written
+// before a barrier (stores drained) and read after it with write-through loads.
+// fits: one SweepArgs per fit (g.nb_local tiles, blocks_per_unit = 1, units_per_rank =
+// blocks_per_rank = n_units_global = nb_local, world_size 1, h filled, h.hvar null), read through
+// the pointer where used (wave-uniform scalar loads, not held across the sweep loop).
+// wg_map: [workgroup] -> (fit, chain), longest fits first.  init_bs (D = 3): [fit][K D + D D], the
+// (beta, Sigma) of sweep 1 (tri:504).  Inactive lanes of a fit's last tile run a clamped row's
+// loads only: their statistics are exact zeros and they store nothing.
+// ---------------------------------------------------------------------------------------------
+template <int D, int K>
+__global__ __launch_bounds__(BLOCK) void batch_fit_kernel(const SweepArgs* __restrict__ fits,
+                                                          const int2* __restrict__ wg_map,
+                                                          const double* __restrict__ init_bs, int64_t n_sweeps) {
+  constexpr int NT = BLOCK;
+  constexpr int NS = K * D + D * (D + 1) / 2 + 1;
+  constexpr bool CL = CovLds<D, K>::value;
+  __shared__ double red[BLOCK / 64][NS];
+  __shared__ double tot[NS];
+  __shared__ __attribute__((aligned(16))) double exp_tab[D == 3 ? FAST_TAB_N3 : FAST_TAB_N];
+  __shared__ double cov_s[CL ? (K - 1) * BLOCK : 1];
+  __shared__ double Hs[HS];
+  __shared__ double var_iw[4], var_chi[4], var_noise[32];
+  __shared__ L2Scratch l2;
+  const int tid = threadIdx.x;
+  const int2 fc = wg_map[blockIdx.x];
+  const int f = __builtin_amdgcn_readfirstlane(fc.x), c = __builtin_amdgcn_readfirstlane(fc.y);
+  const SweepArgs& a = fits[f];
+  uint32_t k0, k1;
+  chain_key(a.r.seed, (int64_t)a.r.chain_first + c, &k0, &k1);
+  fast_tab_fill(exp_tab, tid, BLOCK, D == 3);
+  auto store_partial = [&](int b) {  // statistic-major [chain][stride][blocks_per_rank], as the sweep kernel
+    if (tid < NS)
+      __hip_atomic_store(a.blockpart + ((int64_t)c * a.g.stride + tid) * a.g.blocks_per_rank + b, tot[tid],
+                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  };
+  auto publish = [&]() {  // this wave's stores have landed; then every wave's
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+  };
+
+  // ---- prologue: bi:368-370 / tri:489-491 (sweep_body at a.init) over the fit's tiles
+  for (int b = 0; b < a.g.nb_local; ++b) {
+    const Geometry& g = a.g;
+    const int64_t i = (int64_t)b * BLOCK + tid;
+    StatGen<D, K> st{};
+    if (i < g.n) {
+      const double tx = a.tx[i];
+      const double lam = a.lam_init;
+      const double mu = 1.0 / (tx + 0.5 / a.lam_init);
+      st.xr[0] = 1.0;
+#pragma unroll
+      for (int k = 1; k < K; ++k) st.xr[k] = a.cov[(int64_t)(k - 1) * g.n + i];
+      st.Y[0] = log(lam);
+      st.Y[1] = log(mu);
+      if constexpr (D == 3) st.Y[2] = 0.0;
+      st.on = true;
+      const int64_t ci = (int64_t)c * g.n + i;
+      a.lam[ci] = lam;
+      a.mu[ci] = mu;
+    }
+    block_reduce_gen<NS, SWEEP_REDUCE_CHUNK>(st, red, tot);
+    store_partial(b);
+  }
+  publish();
+  if constexpr (D == 2) {  // the draw of sweep 1 (bi:393) from the initial statistics
+    hyper_body<D, K, false, NS, NT>(a.h, c, 0, 1, a.blockpart, red, tot, var_iw, var_chi, var_noise, &l2);
+  } else if (tid == 0) {  // tri:504, as set_hyper_kernel
+    const double* in = init_bs + (int64_t)f * (K * D + D * D);
+    double Sig[D][D];
+    for (int p = 0; p < D; ++p)
+      for (int q = 0; q < D; ++q) Sig[p][q] = in[K * D + p * D + q];
+    finalize_hyper<D, K, false, CLV_L2_NR != 0>(in, Sig, a.h.omega2, a.h.hyper + (int64_t)c * HS);
+  }
+  publish();
+  if (tid < HS) Hs[tid] = ld_wt(a.hyper + (int64_t)c * HS + tid);
+  __syncthreads();
+
+  for (int64_t s = 1; s <= n_sweeps; ++s) {
+    const bool stored = is_stored(s, a.g);
+    for (int b = 0; b < a.g.nb_local; ++b) {
+      const Geometry& g = a.g;
+      Cust<D, K, CL> cu;
+      cu.cl = cov_s + tid;
+      {
+        const int64_t i = (int64_t)b * BLOCK + tid;
+        cu.active = i < g.n;
+        cu.i = cu.active ? i : g.n - 1;
+      }
+      cust_load(cu, a, c);  // inactive lanes load a clamped valid row
+      StatGen<D, K> st{};
+      CustOut<D> out{};
+      if (cu.active) {
+        cust_prepare<D, K, false>(cu, a, c, s, Hs, k0, k1, nullptr, exp_tab);
+        mh_run(cu, SlotPhilox(k0, k1, cu.gi, (uint32_t)s), Hs[H_S00], Hs[H_S11], g.S, exp_tab);
+        out = cust_finish<D, K, false>(cu, a, s, stored, Hs, k0, k1, nullptr, exp_tab, st);
+      }
+      block_reduce_gen<NS, SWEEP_REDUCE_CHUNK>(st, red, tot);
+      store_partial(b);
+      if (cu.active) cust_store<D, K>(cu, out, a, c, s, stored, true);
+    }
+    publish();
+    hyper_body<D, K, false, NS, NT>(a.h, c, s, 2, a.blockpart, red, tot, var_iw, var_chi, var_noise, &l2);
+    publish();
+    if (tid < HS) Hs[tid] = ld_wt(a.hyper + (int64_t)c * HS + tid);
+    __syncthreads();
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
 // Debug / test kernels
 // ---------------------------------------------------------------------------------------------
 __global__ void debug_philox_kernel(uint32_t k0, uint32_t k1, const uint32_t* ctr, int64_t n, uint32_t* out) {
@@ -4099,6 +4215,41 @@ hipError_t score_resources(int D, int K, bool summary, int* vgprs, size_t* scrat
   CLV_FOR_K(CLV_CASE, 3, false)
   CLV_FOR_K(CLV_CASE, 2, true)
   CLV_FOR_K(CLV_CASE, 3, true)
+#undef CLV_CASE
+  return hipErrorInvalidValue;
+}
+
+// Many small fits in one launch: grid = n_wgs (fit, chain) pairs; e0 / e1 (optional): events around
+// the kernel.
+hipError_t launch_batch_fit(int D, int K, const SweepArgs* fits, const int2* wg_map, const double* init_bs,
+                            int64_t n_wgs, int64_t n_sweeps, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
+  const dim3 grid((unsigned)n_wgs);
+#define CLV_CASE(DD, KK, RR)                                                                                       \
+  if (D == DD && K == KK) {                                                                                        \
+    if (e0) hipExtLaunchKernelGGL((batch_fit_kernel<DD, KK>), grid, dim3(BLOCK), 0, st, e0, e1, 0, fits, wg_map,   \
+                                  init_bs, n_sweeps);                                                              \
+    else hipLaunchKernelGGL((batch_fit_kernel<DD, KK>), grid, dim3(BLOCK), 0, st, fits, wg_map, init_bs, n_sweeps); \
+    return hipGetLastError();                                                                                      \
+  }
+  CLV_FOR_K(CLV_CASE, 2, false)
+  CLV_FOR_K(CLV_CASE, 3, false)
+#undef CLV_CASE
+  return hipErrorInvalidValue;
+}
+
+// VGPRs, scratch bytes per lane and workgroups per CU of a batch-fit instance.
+hipError_t batch_fit_resources(int D, int K, int* vgprs, size_t* scratch_bytes, int* blocks_per_cu) {
+  hipFuncAttributes fa{};
+#define CLV_CASE(DD, KK, RR)                                                                                   \
+  if (D == DD && K == KK) {                                                                                    \
+    hipError_t err = hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(&batch_fit_kernel<DD, KK>));      \
+    if (err != hipSuccess) return err;                                                                         \
+    *vgprs = fa.numRegs;                                                                                       \
+    *scratch_bytes = fa.localSizeBytes;                                                                        \
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, batch_fit_kernel<DD, KK>, BLOCK, 0);    \
+  }
+  CLV_FOR_K(CLV_CASE, 2, false)
+  CLV_FOR_K(CLV_CASE, 3, false)
 #undef CLV_CASE
   return hipErrorInvalidValue;
 }
