@@ -881,6 +881,66 @@ int clv_pnbd_customers(clv_pnbd* h, const double* params, double t_star, double*
 int clv_pnbd_track(int32_t device, int64_t n, const double* birth_week, const double* times, int32_t n_times,
                    const double* params, double* cum);
 
+/* ---- Pareto/NBD with time-invariant covariates (csrc/pnbd.hip) ----
+ * Fader & Hardie (2007), "Incorporating time-invariant covariates into the Pareto/NBD and BG/NBD
+ * models", equations (1) and (2): alpha_i = alpha0 exp(-gamma1' z1_i), beta_i = beta0
+ * exp(-gamma2' z2_i); the likelihood of customer i is the Pareto/NBD L above at (r, alpha_i, s,
+ * beta_i) (their equation 3).  params = (r, alpha0, s, beta0, gamma1[k1], gamma2[k2]): the first
+ * four > 0 and finite, the coefficients finite (CLV_EINVAL otherwise).
+ * clv_pnbd_set_covariates copies z1 [k1][n] and z2 [k2][n] (row k = covariate k of every customer,
+ * the sampler's layout) into the handle; 0 <= k1, k2 <= 8, every value finite (CLV_EINVAL
+ * otherwise, and the handle keeps what it had).  k1 = k2 = 0 is allowed.  The _cov entries are
+ * CLV_EINVAL on a handle without covariates.
+ * clv_pnbd_eval_cov: sums[6 + k1 + k2] = the six sums of clv_pnbd_eval, then sum_i w_i g_logalpha,i
+ * (-z1[k][i]) for k < k1 and sum_i w_i g_logbeta,i (-z2[k][i]) for k < k2: d sum w log L / d gamma
+ * by the chain rule, g the score with respect to log alpha_i and log beta_i.  Every sum in the fixed
+ * order of clv_pnbd_eval; with every gamma = 0 (or k1 = k2 = 0) the first six are its bits.
+ * clv_pnbd_customers_cov: out[n][7] = log L_i, P(alive), E[Y(t_star) | x, t_x, T, z_i] (the three
+ * columns of clv_pnbd_customers at (r, alpha_i, s, beta_i)) and the score d log L_i / d log(r,
+ * alpha_i, s, beta_i).
+ * clv_pnbd_track_cov: cum[j] = sum_i E[X(max(times[j] - birth_week[i], 0)) | z_i], E[X(t) | z_i] =
+ * r beta_i / alpha_i (1 - (beta_i / (beta_i + t))^(s-1)) / (s - 1) (Fader & Hardie 2007, the
+ * Pareto/NBD expectation at alpha_i, beta_i), in the fixed order of clv_pnbd_track. */
+int clv_pnbd_set_covariates(clv_pnbd* h, int32_t k1, const double* z1, int32_t k2, const double* z2);
+int clv_pnbd_eval_cov(clv_pnbd* h, const double* params, double* sums, int64_t* n_unconverged);
+int clv_pnbd_customers_cov(clv_pnbd* h, const double* params, double t_star, double* out);
+int clv_pnbd_track_cov(int32_t device, int64_t n, const double* birth_week, const double* times, int32_t n_times,
+                       const double* params, int32_t k1, const double* z1, int32_t k2, const double* z2, double* cum);
+
+/* Discounted expected residual transactions (Fader, Hardie & Lee 2005, "RFM and CLV", equation 14,
+ * with Psi(s, s; z) z^(s-1) written as e^z E_s(z) and a finite horizon):
+ *   DERT_i = P(alive)_i (r + x_i) / (alpha_i + T_i) J_i,
+ *   J_i = int_0^H exp(-delta t) (B_i / (B_i + t))^s dt,  B_i = beta_i + T_i,
+ * at params as clv_pnbd_eval_cov takes them (a handle without covariates: four parameters).  J is
+ * integrated itself, by 16-point Gauss-Legendre panels of a positive integrand (DESIGN.md section
+ * 4m): no difference of two E_s, no series in s.  delta >= 0 and finite, horizon > 0 or +inf; an
+ * infinite horizon needs delta > 0 (CLV_EINVAL otherwise).  out[n][2] = P(alive), DERT.
+ * clv_dert_integral evaluates J alone for n rows of (s, B, delta, horizon): the kernel's device
+ * function under test. */
+int clv_pnbd_dert(clv_pnbd* h, const double* params, double delta, double horizon, double* out);
+int clv_dert_integral(int32_t device, int64_t n, const double* s, const double* B, const double* delta,
+                      const double* horizon, double* out);
+
+/* ---- Gamma-Gamma spend model by maximum likelihood (csrc/gg.hip) ----
+ * Fader, Hardie & Lee (2005), "RFM and CLV", and Fader & Hardie (2013), "The Gamma-Gamma model of
+ * monetary value", equation (1a): customer i with mean spend m_i > 0 over n_i >= 1 transactions,
+ *   log L_i = lnGamma(p n + q) - lnGamma(p n) - lnGamma(q) + q ln gamma + (p n - 1) ln m + p n ln n
+ *             - (p n + q) ln(gamma + n m),
+ * params = (p, q, gamma), all > 0 and finite.  clv_gg_create is CLV_EINVAL on n_i < 1, m_i <= 0 or a
+ * negative or non-finite weight.  clv_gg_eval: sums[5] = sum w log L, its derivatives with respect
+ * to log(p, q, gamma), sum w, in the fixed order of clv_pnbd_eval.  clv_gg_customers: out[n][4] =
+ * log L_i and d log L_i / d log(p, q, gamma).  lnGamma(p n + q) - lnGamma(p n) and psi(p n + q) -
+ * psi(p n) are each one function (Stirling's series differenced term by term from 32 on), so a
+ * heavy buyer loses no digits.  clv_digamma evaluates the device digamma (upward shift to 10, then
+ * the asymptotic series) on n positive arguments: the kernel's device function under test. */
+typedef struct clv_gg clv_gg;
+int clv_gg_create(int32_t device, int64_t n, const int32_t* frequency, const double* monetary, const double* weights,
+                  clv_gg** out);
+void clv_gg_destroy(clv_gg* h);
+int clv_gg_eval(clv_gg* h, const double* params, double* sums);
+int clv_gg_customers(clv_gg* h, const double* params, double* out);
+int clv_digamma(int32_t device, int64_t n, const double* x, double* out);
+
 /* ---- Many small fits in one launch (csrc/batch.hip) ----
  * Replaces a host loop of whole runs, bi:346-431 / tri:465-574 once per fit and chain: n_fits
  * independent problems of one (D, K), each with its own customers, prior constants and seed, are

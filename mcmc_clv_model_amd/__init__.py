@@ -38,6 +38,12 @@ Many small fits at once — the training sets of a cross-validation, fits per co
 simulation studies — run in one kernel launch with the single calls' bits (mcmc_draw_parameters_many,
 mcmc_draw_parameters_rfm_m_many), and exact K-fold cross-validation on top of them
 (kfold_cross_validation).
+The classical baseline completed: the Pareto/NBD with time-invariant covariates of
+Fader & Hardie (2007) (ParetoNBDFitter.fit(covariates=...), the fair opponent of a covariate HB
+model), standard errors, a Wald summary and likelihood-ratio tests of a fit (standard_errors=True,
+likelihood_ratio_test), the Gamma-Gamma spend model (GammaGammaFitter), DERT and the classical CLV
+that stands beside lifetime_value (ParetoNBDFitter.discounted_expected_transactions,
+classical_lifetime_value).
 
 The per-sweep work runs in hand-written HIP kernels for gfx950 (csrc/), bound through the C
 ABI in include/clvmcmc.h.  There is no CPU fallback.
@@ -53,7 +59,8 @@ from .analysis import (chain_total_loglik, compare_forecasts, compare_models, co
                        marginal_information_criteria, marginal_log_likelihood, marginal_log_score)
 from .batch import kfold_cross_validation, mcmc_draw_parameters_many, mcmc_draw_parameters_rfm_m_many
 from .bivariate import mcmc_draw_parameters
-from .mle import ParetoNBDFitter, mape_aggregate, pnbd_weekly_tracking
+from .mle import (GammaGammaFitter, ParetoNBDFitter, classical_lifetime_value, likelihood_ratio_test, mape_aggregate,
+                  pnbd_weekly_tracking)
 from .trivariate import mcmc_draw_parameters_rfm_m
 
 __all__ = ["mcmc_draw_parameters", "mcmc_draw_parameters_rfm_m", "draw_future_transactions",
@@ -66,5 +73,6 @@ __all__ = ["mcmc_draw_parameters", "mcmc_draw_parameters_rfm_m", "draw_future_tr
            "compare_models", "score_customers", "forecast", "forecast_pit", "compare_forecasts",
            "forecast_table", "posterior_predictive_check", "ppc_pit", "marginal_log_likelihood",
            "marginal_information_criteria", "marginal_log_score", "mcmc_draw_parameters_many",
-           "mcmc_draw_parameters_rfm_m_many", "kfold_cross_validation"]
+           "mcmc_draw_parameters_rfm_m_many", "kfold_cross_validation", "GammaGammaFitter",
+           "classical_lifetime_value", "likelihood_ratio_test"]
 __version__ = "0.1.0"

@@ -216,6 +216,17 @@ def lib() -> ctypes.CDLL:
         "clv_pnbd_eval": (c_int32, [sp, dp, dp, POINTER(c_int64)]),
         "clv_pnbd_customers": (c_int32, [sp, dp, c_double, dp]),
         "clv_pnbd_track": (c_int32, [c_int32, c_int64, dp, dp, c_int32, dp, dp]),
+        "clv_pnbd_set_covariates": (c_int32, [sp, c_int32, dp, c_int32, dp]),
+        "clv_pnbd_eval_cov": (c_int32, [sp, dp, dp, POINTER(c_int64)]),
+        "clv_pnbd_customers_cov": (c_int32, [sp, dp, c_double, dp]),
+        "clv_pnbd_track_cov": (c_int32, [c_int32, c_int64, dp, dp, c_int32, dp, c_int32, dp, c_int32, dp, dp]),
+        "clv_pnbd_dert": (c_int32, [sp, dp, c_double, c_double, dp]),
+        "clv_dert_integral": (c_int32, [c_int32, c_int64, dp, dp, dp, dp, dp]),
+        "clv_gg_create": (c_int32, [c_int32, c_int64, POINTER(c_int32), dp, dp, POINTER(sp)]),
+        "clv_gg_destroy": (None, [sp]),
+        "clv_gg_eval": (c_int32, [sp, dp, dp]),
+        "clv_gg_customers": (c_int32, [sp, dp, dp]),
+        "clv_digamma": (c_int32, [c_int32, c_int64, dp, dp]),
         "clv_batch_fit": (c_int32, [c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
                                     c_int64, POINTER(ClvBatchItem), dp]),
         "clv_batch_plan": (c_int32, [c_int64, POINTER(c_int64), c_int32, POINTER(c_int64), POINTER(c_int32),

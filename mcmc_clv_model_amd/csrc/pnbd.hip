@@ -6,6 +6,9 @@
 //   clv_pnbd_eval                sum w log L and its gradient with respect to log(r, alpha, s, beta)
 //   clv_pnbd_customers           per customer log L, P(alive), E[Y(t*) | x, t_x, T]
 //   clv_pnbd_track               cum[j] = sum_i E[X(max(times[j] - birth_week[i], 0))]
+//   clv_pnbd_set_covariates      time-invariant covariates (Fader & Hardie 2007) resident in the handle
+//   clv_pnbd_eval_cov / _customers_cov / _track_cov   the same three with alpha_i = alpha0 exp(-gamma1' z_i),
+//                                beta_i = beta0 exp(-gamma2' z_i): DESIGN.md section 4m
 //
 // Per customer, with theta = (r, alpha, s, beta), a = r + s + x, M = max(alpha, beta) and
 // z(t) = |alpha - beta| / (M + t) in [0, 1):
@@ -31,7 +34,9 @@
 #include <string>
 #include <vector>
 
+#include "gauss_legendre.h"
 #include "internal.h"
+#include "pnbd_sum.h"
 
 using namespace clv;
 
@@ -42,6 +47,12 @@ struct clv_pnbd {
   double *d_tx = nullptr, *d_T = nullptr, *d_w = nullptr;
   double* d_part = nullptr;  // [nb][PNBD_NS] block partials
   double* d_out = nullptr;   // [PNBD_NS]
+  // covariates (clv_pnbd_set_covariates): [k][n] each, a wavefront reads a covariate row coalesced
+  bool has_cov = false;
+  int32_t k1 = 0, k2 = 0;
+  double *d_z1 = nullptr, *d_z2 = nullptr;
+  double* d_partc = nullptr;  // [nb][PNBD_NS + k1 + k2]
+  double* d_outc = nullptr;   // [PNBD_NS + k1 + k2]
 };
 
 namespace {
@@ -50,6 +61,8 @@ constexpr int PNBD_NS = 7;            // sum w log L, 4 gradient sums, sum w, un
 constexpr int PNBD_TERM_CAP = 2048;   // series terms after u_0 (reaches z of about 0.98)
 constexpr double PNBD_EPS = 0x1p-53;  // relative remainder at which the series stops
 constexpr int PNBD_MAX_GRID = 2048;
+constexpr int PNBD_MAX_COV = 8;       // covariate columns per process
+constexpr int PNBD_COV_GROUP = 8;     // covariate sums reduced per pass over the LDS tile
 
 struct Params {
   double r, a, s, b;
@@ -179,17 +192,6 @@ __host__ __device__ inline double pnbd_expected(double t, const Params& p) {
   return p.r * p.b / p.a * pnbd_phi(p.s - 1.0, log1p(t / p.b));
 }
 
-// red[k][0] = sum over the 256 lanes of red[k][lane], tree offsets 128, 64, ..., 1.
-template <int NSUM>
-__device__ __forceinline__ void tree256(double (*red)[256]) {
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
-    if ((int)threadIdx.x < off)
-      for (int k = 0; k < NSUM; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + off];
-    __syncthreads();
-  }
-}
-
 __global__ __launch_bounds__(256) void pnbd_eval_kernel(const int32_t* x, const double* tx, const double* T,
                                                         const double* w, int64_t n, int64_t nb, Params p,
                                                         double* part /*[nb][PNBD_NS]*/) {
@@ -210,18 +212,6 @@ __global__ __launch_bounds__(256) void pnbd_eval_kernel(const int32_t* x, const 
     if (threadIdx.x < PNBD_NS) part[b * PNBD_NS + threadIdx.x] = red[threadIdx.x][0];
     __syncthreads();
   }
-}
-
-// out[row][k] = fixed-order sum over b < nb of part[(row * nb + b) * ns + k]; grid (ns, rows).
-__global__ __launch_bounds__(256) void pnbd_final_kernel(const double* part, int64_t nb, int ns, double* out) {
-  __shared__ double red[1][256];
-  const int k = blockIdx.x;
-  const int64_t row = blockIdx.y;
-  double acc = 0.0;
-  for (int64_t b = threadIdx.x; b < nb; b += 256) acc += part[(row * nb + b) * ns + k];
-  red[0][threadIdx.x] = acc;
-  tree256<1>(red);
-  if (threadIdx.x == 0) out[row * ns + k] = red[0][0];
 }
 
 __global__ __launch_bounds__(256) void pnbd_customers_kernel(const int32_t* x, const double* tx, const double* T,
@@ -251,6 +241,178 @@ __global__ __launch_bounds__(256) void pnbd_track_kernel(const double* birth, co
   }
 }
 
+// theta of the covariate model: the four baseline parameters and the coefficients of each process.
+struct CovParams {
+  double r, a0, s, b0;
+  int32_t k1, k2;
+  double g1[PNBD_MAX_COV], g2[PNBD_MAX_COV];
+};
+
+// (r, alpha_i, s, beta_i) of customer i: alpha_i = alpha0 exp(-gamma1' z1_i), beta_i = beta0 exp(-gamma2' z2_i)
+// (Fader & Hardie 2007, equations 1 and 2).  gamma = 0 or no column: exp(-0) = 1, the baseline bits.
+__device__ inline Params pnbd_cov_params(const CovParams& c, const double* z1, const double* z2, int64_t n,
+                                         int64_t i) {
+  double e1 = 0.0, e2 = 0.0;
+  for (int k = 0; k < c.k1; ++k) e1 += c.g1[k] * z1[(int64_t)k * n + i];
+  for (int k = 0; k < c.k2; ++k) e2 += c.g2[k] * z2[(int64_t)k * n + i];
+  return Params{c.r, c.a0 * exp(-e1), c.s, c.b0 * exp(-e2)};
+}
+
+// tree256 over the first m rows of the tile: per row the additions of tree256, whatever m is.
+__device__ __forceinline__ void tree256n(double (*red)[256], int m) {
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) {
+    if ((int)threadIdx.x < off)
+      for (int k = 0; k < m; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + off];
+    __syncthreads();
+  }
+}
+
+// part[b][0..7) as pnbd_eval_kernel; part[b][7 + k] = tree sum of w g_logalpha,i (-z1[k][i]) for k < k1 and
+// of w g_logbeta,i (-z2[k - k1][i]) after them.  The covariate sums go through the tile in groups of
+// PNBD_COV_GROUP rows; a row's tree does not see the other rows, so the grouping is not in the bits.
+__global__ __launch_bounds__(256) void pnbd_eval_cov_kernel(const int32_t* x, const double* tx, const double* T,
+                                                            const double* w, const double* z1, const double* z2,
+                                                            int64_t n, int64_t nb, CovParams c,
+                                                            double* part /*[nb][PNBD_NS + k1 + k2]*/) {
+  static_assert(PNBD_COV_GROUP >= PNBD_NS, "the tile holds the seven baseline sums");
+  __shared__ double red[PNBD_COV_GROUP][256];
+  const int nc = c.k1 + c.k2, ns = PNBD_NS + nc;
+  for (int64_t b = blockIdx.x; b < nb; b += gridDim.x) {
+    const int64_t i = b * 256 + threadIdx.x;
+    double v[PNBD_NS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (i < n) {
+      const Params p = pnbd_cov_params(c, z1, z2, n, i);
+      const Point q = pnbd_point(x[i], tx[i], T[i], p);
+      const double wi = w ? w[i] : 1.0;
+      v[0] = wi * q.logL;
+      for (int j = 0; j < 4; ++j) v[1 + j] = wi * q.g[j];
+      v[5] = wi;
+      v[6] = q.conv ? 0.0 : 1.0;
+    }
+    for (int k = 0; k < PNBD_NS; ++k) red[k][threadIdx.x] = v[k];
+    tree256<PNBD_NS>(red);
+    if (threadIdx.x < PNBD_NS) part[b * ns + threadIdx.x] = red[threadIdx.x][0];
+    __syncthreads();
+    for (int k0 = 0; k0 < nc; k0 += PNBD_COV_GROUP) {
+      const int m = nc - k0 < PNBD_COV_GROUP ? nc - k0 : PNBD_COV_GROUP;
+      for (int j = 0; j < m; ++j) {
+        const int k = k0 + j;
+        double t = 0.0;
+        if (i < n) t = k < c.k1 ? v[2] * -z1[(int64_t)k * n + i] : v[4] * -z2[(int64_t)(k - c.k1) * n + i];
+        red[j][threadIdx.x] = t;
+      }
+      tree256n(red, m);
+      if ((int)threadIdx.x < m) part[b * ns + PNBD_NS + k0 + threadIdx.x] = red[threadIdx.x][0];
+      __syncthreads();
+    }
+  }
+}
+
+// out[i] = log L, P(alive), E[Y(t*) | x, t_x, T, z_i] and the score components d log L_i /
+// d log(r, alpha_i, s, beta_i); the first three as pnbd_customers_kernel writes them.
+__global__ __launch_bounds__(256) void pnbd_customers_cov_kernel(const int32_t* x, const double* tx, const double* T,
+                                                                 const double* z1, const double* z2, int64_t n,
+                                                                 CovParams c, double t_star, double* out /*[n][7]*/) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const Params p = pnbd_cov_params(c, z1, z2, n, i);
+    const Point q = pnbd_point(x[i], tx[i], T[i], p);
+    const double Ti = T[i];
+    out[i * 7 + 0] = q.logL;
+    out[i * 7 + 1] = q.p_alive;
+    out[i * 7 + 2] = q.p_alive * (p.r + (double)x[i]) * (p.b + Ti) / (p.a + Ti) *
+                     pnbd_phi(p.s - 1.0, log1p(t_star / (p.b + Ti)));
+    for (int j = 0; j < 4; ++j) out[i * 7 + 3 + j] = q.g[j];
+  }
+}
+
+// pnbd_track_kernel with E[X(t) | z_i] = r beta_i / alpha_i phi(s - 1, log((beta_i + t) / beta_i)).
+__global__ __launch_bounds__(256) void pnbd_track_cov_kernel(const double* birth, const double* times,
+                                                             const double* z1, const double* z2, int64_t n, int64_t nb,
+                                                             CovParams c, double* part /*[n_times][nb]*/) {
+  __shared__ double red[1][256];
+  const double tj = times[blockIdx.y];
+  for (int64_t b = blockIdx.x; b < nb; b += gridDim.x) {
+    const int64_t i = b * 256 + threadIdx.x;
+    double e = 0.0;
+    if (i < n) e = pnbd_expected(fmax(tj - birth[i], 0.0), pnbd_cov_params(c, z1, z2, n, i));
+    red[0][threadIdx.x] = e;
+    tree256<1>(red);
+    if (threadIdx.x == 0) part[(int64_t)blockIdx.y * nb + b] = red[0][0];
+    __syncthreads();
+  }
+}
+
+// sum_j w_j f(x_j) over one 16-point Gauss-Legendre panel [lo, hi].
+template <class F>
+__host__ __device__ inline double pnbd_gl16(double lo, double hi, F f) {
+  constexpr double X[CLV_GL_Q] = CLV_GL_X_INIT, W[CLV_GL_Q] = CLV_GL_W_INIT;
+  const double mid = 0.5 * (lo + hi), half = 0.5 * (hi - lo);
+  double acc = 0.0;
+#pragma unroll
+  for (int j = 0; j < CLV_GL_Q; ++j) acc += W[j] * f(mid + half * X[j]);
+  return acc * half;
+}
+
+constexpr double DERT_U_SPLIT = 4.0;   // u = delta (B + t) at which the panels change from log to linear
+constexpr double DERT_D_SPAN = 64.0;   // the linear panels stop exp(-64) below their start
+
+// J = int_0^H exp(-delta t) (B / (B + t))^s dt = B int_0^V exp(-z v) (1 + v)^-s dv, z = delta B, V = H / B.
+// The integrand has two scales, 1 / z for the exponential and 1 + v for the power, so the panels follow
+// u = z (1 + v): while u <= 4 they are uniform in y = log(1 + v), at most 1/2 wide, with the integrand
+// exp(-z expm1(y) + (1 - s) y) (entire in y); beyond, uniform in d = z v, at most 1 wide, with the
+// integrand exp(-d - s log1p(d / z)) / z (the pole u = 0 is nine half-widths away), cut where exp(-d) has
+// fallen by exp(-64).  Every term is positive: nothing cancels for any s, and a short horizon is one
+// short panel.  H = inf needs z > 0 (the caller's check).
+__host__ __device__ inline double pnbd_dert_integral(double s, double B, double delta, double H) {
+  if (!(B > 0.0) || !(B < INFINITY)) return std::numeric_limits<double>::quiet_NaN();  // beta_i under- or overflowed
+  const double z = delta * B, V = H / B;
+  const double Y = log1p(V);                                    // inf with V
+  const double yb = z < DERT_U_SPLIT ? log(DERT_U_SPLIT / z) : 0.0;  // inf at z = 0
+  const double Yl = fmin(Y, yb);
+  double acc = 0.0;
+  if (Yl > 0.0) {
+    const int np = (int)ceil(Yl / 0.5);
+    const double wd = Yl / np;
+    for (int k = 0; k < np; ++k)
+      acc += pnbd_gl16(k * wd, k + 1 == np ? Yl : (k + 1) * wd,
+                       [=](double y) { return exp(-z * expm1(y) + (1.0 - s) * y); });
+  }
+  if (Y > yb) {
+    const double d0 = z < DERT_U_SPLIT ? DERT_U_SPLIT - z : 0.0;
+    const double d1 = fmin(z * V, d0 + DERT_D_SPAN);
+    if (d1 > d0) {
+      const int np = (int)ceil(d1 - d0);
+      const double wd = (d1 - d0) / np;
+      double lin = 0.0;
+      for (int k = 0; k < np; ++k)
+        lin += pnbd_gl16(d0 + k * wd, k + 1 == np ? d1 : d0 + (k + 1) * wd,
+                         [=](double d) { return exp(-d - s * log1p(d / z)); });
+      acc += lin / z;
+    }
+  }
+  return B * acc;
+}
+
+// out[i] = P(alive), DERT = P(alive) (r + x) / (alpha_i + T) J(s, beta_i + T, delta, H).
+__global__ __launch_bounds__(256) void pnbd_dert_kernel(const int32_t* x, const double* tx, const double* T,
+                                                        const double* z1, const double* z2, int64_t n, CovParams c,
+                                                        double delta, double H, double* out /*[n][2]*/) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    const Params p = pnbd_cov_params(c, z1, z2, n, i);
+    const double Ti = T[i];
+    const Point q = pnbd_point(x[i], tx[i], Ti, p);
+    out[i * 2 + 0] = q.p_alive;
+    out[i * 2 + 1] = q.p_alive * (p.r + (double)x[i]) / (p.a + Ti) * pnbd_dert_integral(p.s, p.b + Ti, delta, H);
+  }
+}
+
+__global__ __launch_bounds__(256) void pnbd_dert_integral_kernel(const double* s, const double* B, const double* delta,
+                                                                 const double* H, int64_t n, double* out) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+    out[i] = pnbd_dert_integral(s[i], B[i], delta[i], H[i]);
+}
+
 int check_params(const double* params, Params* p) {
   if (!params) return fail(CLV_EINVAL, "pnbd: null params");
   for (int j = 0; j < 4; ++j)
@@ -261,6 +423,31 @@ int check_params(const double* params, Params* p) {
 }
 
 unsigned grid_for(int64_t nb) { return (unsigned)std::min<int64_t>(nb, PNBD_MAX_GRID); }
+
+// params = (r, alpha0, s, beta0, gamma1[k1], gamma2[k2]).
+int check_cov_params(const double* params, int32_t k1, int32_t k2, CovParams* c) {
+  Params p;
+  int rc = check_params(params, &p);
+  if (rc) return rc;
+  for (int k = 0; k < k1 + k2; ++k)
+    if (!std::isfinite(params[4 + k])) return fail(CLV_EINVAL, "pnbd: covariate coefficients must be finite");
+  *c = CovParams{};
+  c->r = p.r, c->a0 = p.a, c->s = p.s, c->b0 = p.b, c->k1 = k1, c->k2 = k2;
+  for (int k = 0; k < k1; ++k) c->g1[k] = params[4 + k];
+  for (int k = 0; k < k2; ++k) c->g2[k] = params[4 + k1 + k];
+  return CLV_OK;
+}
+
+int check_covariates(int64_t n, int32_t k1, const double* z1, int32_t k2, const double* z2) {
+  if (k1 < 0 || k2 < 0 || k1 > PNBD_MAX_COV || k2 > PNBD_MAX_COV)
+    return fail(CLV_EINVAL, "pnbd: 0..8 covariate columns per process");
+  if ((k1 > 0 && !z1) || (k2 > 0 && !z2)) return fail(CLV_EINVAL, "pnbd: null covariates");
+  for (int64_t j = 0; j < (int64_t)k1 * n; ++j)
+    if (!std::isfinite(z1[j])) return fail(CLV_EINVAL, "pnbd: non-finite purchase covariate");
+  for (int64_t j = 0; j < (int64_t)k2 * n; ++j)
+    if (!std::isfinite(z2[j])) return fail(CLV_EINVAL, "pnbd: non-finite dropout covariate");
+  return CLV_OK;
+}
 
 }  // namespace
 
@@ -320,6 +507,10 @@ void clv_pnbd_destroy(clv_pnbd* h) {
     (void)hipFree(h->d_w);
     (void)hipFree(h->d_part);
     (void)hipFree(h->d_out);
+    (void)hipFree(h->d_z1);
+    (void)hipFree(h->d_z2);
+    (void)hipFree(h->d_partc);
+    (void)hipFree(h->d_outc);
   }
   delete h;
 }
@@ -381,6 +572,171 @@ int clv_pnbd_track(int32_t device, int64_t n, const double* birth_week, const do
   CLV_HIP(hipMemcpy(bt.p, times, sizeof(double) * (size_t)n_times, hipMemcpyHostToDevice));
   hipLaunchKernelGGL(pnbd_track_kernel, dim3(grid_for(nb), (unsigned)n_times), dim3(256), 0, nullptr,
                      bb.as<const double>(), bt.as<const double>(), n, nb, p, bp.as<double>());
+  CLV_HIP(hipGetLastError());
+  hipLaunchKernelGGL(pnbd_final_kernel, dim3(1, (unsigned)n_times), dim3(256), 0, nullptr, bp.as<const double>(), nb, 1,
+                     bo.as<double>());
+  CLV_HIP(hipGetLastError());
+  CLV_HIP(hipMemcpy(cum, bo.p, sizeof(double) * (size_t)n_times, hipMemcpyDeviceToHost));
+  return CLV_OK;
+}
+
+int clv_pnbd_set_covariates(clv_pnbd* h, int32_t k1, const double* z1, int32_t k2, const double* z2) {
+  if (!h) return fail(CLV_EINVAL, "pnbd: null handle");
+  int rc = check_covariates(h->n, k1, z1, k2, z2);
+  if (rc) return rc;
+  DeviceScope ds(h->device);
+  double *n1 = nullptr, *n2 = nullptr, *np = nullptr, *no = nullptr;
+  const size_t ns = (size_t)(PNBD_NS + k1 + k2);
+  rc = [&]() -> int {
+    if (k1) CLV_HIP(dalloc(&n1, (size_t)k1 * (size_t)h->n));
+    if (k2) CLV_HIP(dalloc(&n2, (size_t)k2 * (size_t)h->n));
+    CLV_HIP(dalloc(&np, (size_t)h->nb * ns));
+    CLV_HIP(dalloc(&no, ns));
+    if (k1) CLV_HIP(hipMemcpy(n1, z1, sizeof(double) * (size_t)k1 * (size_t)h->n, hipMemcpyHostToDevice));
+    if (k2) CLV_HIP(hipMemcpy(n2, z2, sizeof(double) * (size_t)k2 * (size_t)h->n, hipMemcpyHostToDevice));
+    return CLV_OK;
+  }();
+  if (rc != CLV_OK) {  // the handle keeps what it had
+    (void)hipFree(n1);
+    (void)hipFree(n2);
+    (void)hipFree(np);
+    (void)hipFree(no);
+    return rc;
+  }
+  (void)hipFree(h->d_z1);
+  (void)hipFree(h->d_z2);
+  (void)hipFree(h->d_partc);
+  (void)hipFree(h->d_outc);
+  h->d_z1 = n1, h->d_z2 = n2, h->d_partc = np, h->d_outc = no;
+  h->k1 = k1, h->k2 = k2, h->has_cov = true;
+  return CLV_OK;
+}
+
+int clv_pnbd_eval_cov(clv_pnbd* h, const double* params, double* sums, int64_t* n_unconverged) {
+  if (!h || !sums) return fail(CLV_EINVAL, "pnbd: null handle or sums");
+  if (!h->has_cov) return fail(CLV_EINVAL, "pnbd: the handle has no covariates (clv_pnbd_set_covariates)");
+  CovParams c;
+  int rc = check_cov_params(params, h->k1, h->k2, &c);
+  if (rc) return rc;
+  const int nc = h->k1 + h->k2, ns = PNBD_NS + nc;
+  DeviceScope ds(h->device);
+  hipLaunchKernelGGL(pnbd_eval_cov_kernel, dim3(grid_for(h->nb)), dim3(256), 0, nullptr, (const int32_t*)h->d_x,
+                     (const double*)h->d_tx, (const double*)h->d_T, (const double*)h->d_w, (const double*)h->d_z1,
+                     (const double*)h->d_z2, h->n, h->nb, c, h->d_partc);
+  CLV_HIP(hipGetLastError());
+  hipLaunchKernelGGL(pnbd_final_kernel, dim3((unsigned)ns, 1), dim3(256), 0, nullptr, (const double*)h->d_partc, h->nb,
+                     ns, h->d_outc);
+  CLV_HIP(hipGetLastError());
+  double res[PNBD_NS + 2 * PNBD_MAX_COV];
+  CLV_HIP(hipMemcpy(res, h->d_outc, sizeof(double) * (size_t)ns, hipMemcpyDeviceToHost));
+  for (int k = 0; k < 6; ++k) sums[k] = res[k];
+  for (int k = 0; k < nc; ++k) sums[6 + k] = res[PNBD_NS + k];
+  if (n_unconverged) *n_unconverged = (int64_t)res[6];
+  return CLV_OK;
+}
+
+int clv_pnbd_customers_cov(clv_pnbd* h, const double* params, double t_star, double* out) {
+  if (!h || !out) return fail(CLV_EINVAL, "pnbd: null handle or output");
+  if (!h->has_cov) return fail(CLV_EINVAL, "pnbd: the handle has no covariates (clv_pnbd_set_covariates)");
+  CovParams c;
+  int rc = check_cov_params(params, h->k1, h->k2, &c);
+  if (rc) return rc;
+  if (!(t_star >= 0.0) || !std::isfinite(t_star)) return fail(CLV_EINVAL, "pnbd: t_star must be >= 0 and finite");
+  DeviceScope ds(h->device);
+  DevBuf bo;
+  CLV_HIP(hipMalloc(&bo.p, sizeof(double) * 7 * (size_t)h->n));
+  hipLaunchKernelGGL(pnbd_customers_cov_kernel, dim3(grid_for(h->nb)), dim3(256), 0, nullptr, (const int32_t*)h->d_x,
+                     (const double*)h->d_tx, (const double*)h->d_T, (const double*)h->d_z1, (const double*)h->d_z2, h->n,
+                     c, t_star, bo.as<double>());
+  CLV_HIP(hipGetLastError());
+  CLV_HIP(hipMemcpy(out, bo.p, sizeof(double) * 7 * (size_t)h->n, hipMemcpyDeviceToHost));
+  return CLV_OK;
+}
+
+int clv_pnbd_dert(clv_pnbd* h, const double* params, double delta, double horizon, double* out) {
+  if (!h || !out) return fail(CLV_EINVAL, "pnbd: null handle or output");
+  CovParams c;
+  int rc = check_cov_params(params, h->k1, h->k2, &c);  // k1 = k2 = 0 on a handle without covariates
+  if (rc) return rc;
+  if (!(delta >= 0.0) || !std::isfinite(delta)) return fail(CLV_EINVAL, "pnbd: delta must be >= 0 and finite");
+  if (!(horizon > 0.0)) return fail(CLV_EINVAL, "pnbd: horizon must be > 0 (+inf for an infinite one)");
+  if (std::isinf(horizon) && delta == 0.0)
+    return fail(CLV_EINVAL, "pnbd: an infinite horizon needs a discount rate > 0");
+  DeviceScope ds(h->device);
+  DevBuf bo;
+  CLV_HIP(hipMalloc(&bo.p, sizeof(double) * 2 * (size_t)h->n));
+  hipLaunchKernelGGL(pnbd_dert_kernel, dim3(grid_for(h->nb)), dim3(256), 0, nullptr, (const int32_t*)h->d_x,
+                     (const double*)h->d_tx, (const double*)h->d_T, (const double*)h->d_z1, (const double*)h->d_z2, h->n,
+                     c, delta, horizon, bo.as<double>());
+  CLV_HIP(hipGetLastError());
+  CLV_HIP(hipMemcpy(out, bo.p, sizeof(double) * 2 * (size_t)h->n, hipMemcpyDeviceToHost));
+  return CLV_OK;
+}
+
+int clv_dert_integral(int32_t device, int64_t n, const double* s, const double* B, const double* delta,
+                      const double* horizon, double* out) {
+  if (n <= 0) return fail(CLV_EINVAL, "dert: n must be >= 1");
+  if (!s || !B || !delta || !horizon || !out) return fail(CLV_EINVAL, "dert: null argument");
+  for (int64_t i = 0; i < n; ++i) {
+    if (!(s[i] > 0.0) || !std::isfinite(s[i]) || !(B[i] > 0.0) || !std::isfinite(B[i]))
+      return fail(CLV_EINVAL, "dert: s and B must be positive and finite");
+    if (!(delta[i] >= 0.0) || !std::isfinite(delta[i])) return fail(CLV_EINVAL, "dert: delta must be >= 0 and finite");
+    if (!(horizon[i] > 0.0)) return fail(CLV_EINVAL, "dert: horizon must be > 0 (+inf for an infinite one)");
+    if (std::isinf(horizon[i]) && delta[i] == 0.0)
+      return fail(CLV_EINVAL, "dert: an infinite horizon needs a discount rate > 0");
+  }
+  int count = 0;
+  if (hipGetDeviceCount(&count) != hipSuccess || count < 1) return fail(CLV_EHIP, "no HIP device visible");
+  if (device >= count) return fail(CLV_EINVAL, "dert: no such device");
+  DeviceScope ds(device);
+  DevBuf bi, bo;
+  const size_t bytes = sizeof(double) * (size_t)n;
+  CLV_HIP(hipMalloc(&bi.p, 4 * bytes));
+  CLV_HIP(hipMalloc(&bo.p, bytes));
+  double* in = bi.as<double>();
+  CLV_HIP(hipMemcpy(in, s, bytes, hipMemcpyHostToDevice));
+  CLV_HIP(hipMemcpy(in + n, B, bytes, hipMemcpyHostToDevice));
+  CLV_HIP(hipMemcpy(in + 2 * n, delta, bytes, hipMemcpyHostToDevice));
+  CLV_HIP(hipMemcpy(in + 3 * n, horizon, bytes, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(pnbd_dert_integral_kernel, dim3(grid_for((n + 255) / 256)), dim3(256), 0, nullptr,
+                     (const double*)in, (const double*)(in + n), (const double*)(in + 2 * n),
+                     (const double*)(in + 3 * n), n, bo.as<double>());
+  CLV_HIP(hipGetLastError());
+  CLV_HIP(hipMemcpy(out, bo.p, bytes, hipMemcpyDeviceToHost));
+  return CLV_OK;
+}
+
+int clv_pnbd_track_cov(int32_t device, int64_t n, const double* birth_week, const double* times, int32_t n_times,
+                       const double* params, int32_t k1, const double* z1, int32_t k2, const double* z2, double* cum) {
+  if (n <= 0 || n_times < 1 || n_times > 65535) return fail(CLV_EINVAL, "pnbd: n must be >= 1 and n_times in 1..65535");
+  if (!birth_week || !times || !cum) return fail(CLV_EINVAL, "pnbd: null argument");
+  int rc = check_covariates(n, k1, z1, k2, z2);
+  if (rc) return rc;
+  CovParams c;
+  rc = check_cov_params(params, k1, k2, &c);
+  if (rc) return rc;
+  for (int64_t i = 0; i < n; ++i)
+    if (!std::isfinite(birth_week[i])) return fail(CLV_EINVAL, "pnbd: non-finite birth_week");
+  for (int32_t j = 0; j < n_times; ++j)
+    if (!std::isfinite(times[j])) return fail(CLV_EINVAL, "pnbd: non-finite time");
+  int count = 0;
+  if (hipGetDeviceCount(&count) != hipSuccess || count < 1) return fail(CLV_EHIP, "no HIP device visible");
+  DeviceScope ds(device);
+  const int64_t nb = (n + 255) / 256;
+  DevBuf bb, bt, b1, b2, bp, bo;
+  CLV_HIP(hipMalloc(&bb.p, sizeof(double) * (size_t)n));
+  CLV_HIP(hipMalloc(&bt.p, sizeof(double) * (size_t)n_times));
+  if (k1) CLV_HIP(hipMalloc(&b1.p, sizeof(double) * (size_t)k1 * (size_t)n));
+  if (k2) CLV_HIP(hipMalloc(&b2.p, sizeof(double) * (size_t)k2 * (size_t)n));
+  CLV_HIP(hipMalloc(&bp.p, sizeof(double) * (size_t)n_times * (size_t)nb));
+  CLV_HIP(hipMalloc(&bo.p, sizeof(double) * (size_t)n_times));
+  CLV_HIP(hipMemcpy(bb.p, birth_week, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
+  CLV_HIP(hipMemcpy(bt.p, times, sizeof(double) * (size_t)n_times, hipMemcpyHostToDevice));
+  if (k1) CLV_HIP(hipMemcpy(b1.p, z1, sizeof(double) * (size_t)k1 * (size_t)n, hipMemcpyHostToDevice));
+  if (k2) CLV_HIP(hipMemcpy(b2.p, z2, sizeof(double) * (size_t)k2 * (size_t)n, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(pnbd_track_cov_kernel, dim3(grid_for(nb), (unsigned)n_times), dim3(256), 0, nullptr,
+                     bb.as<const double>(), bt.as<const double>(), b1.as<const double>(), b2.as<const double>(), n, nb, c,
+                     bp.as<double>());
   CLV_HIP(hipGetLastError());
   hipLaunchKernelGGL(pnbd_final_kernel, dim3(1, (unsigned)n_times), dim3(256), 0, nullptr, bp.as<const double>(), nb, 1,
                      bo.as<double>());

@@ -12,6 +12,18 @@ full_analysis.py:245, :437):
 The likelihood, its analytic gradient and the per-customer quantities are HIP kernels
 (csrc/pnbd.hip, one lane per customer, fixed-order sums); the optimiser is a small numpy BFGS on
 theta = log(r, alpha, s, beta).  There is no CPU fallback for the likelihood.  DESIGN.md §4e.
+
+The rest of the classical baseline:
+
+    pnbd_mle.fit(..., covariates=cbs[["first_sales_scaled"]], standard_errors=True)   # Fader & Hardie (2007)
+    pnbd_mle.summary_; likelihood_ratio_test(plain_fit, pnbd_mle)
+    gg = GammaGammaFitter().fit(frequency=n, monetary_value=m)                        # spend per transaction
+    pnbd_mle.discounted_expected_transactions(cbs["x"], cbs["t_x"], cbs["T_cal"], discount_rate=0.15)
+    classical_lifetime_value(pnbd_mle, gg, cbs, monetary_frequency=n, monetary_value=m)
+
+alpha_i = alpha0 exp(-gamma1' z_i) and beta_i = beta0 exp(-gamma2' z_i) are formed on the device per
+customer (the covariates stay in the handle); the Hessian is a central difference of the device
+gradient; the Gamma-Gamma likelihood (csrc/gg.hip) and the DERT integral are HIP kernels too.
 """
 from __future__ import annotations
 
@@ -100,17 +112,205 @@ def minimize_bfgs(value_and_grad: Callable, theta0, tol: float = 1e-7, max_iter:
 
 
 # ---------------------------------------------------------------------------------------------
+# Uncertainty of a fit: Hessian by central differences of the gradient, Wald summary, tests
+# ---------------------------------------------------------------------------------------------
+# The step of central_hessian on theta (logs of the positive parameters, coefficients as they are).
+# The device gradient is good to about 1e-14 of sum |terms|, so rounding is about 1e-14 / h and
+# truncation about h^2: tests/golden/make_mle_ext_goldens.py scans h against the exact Hessian
+# (DESIGN.md §4m): the error is smallest, 2e-10 of sum |terms|, at 2^-15.
+HESSIAN_STEP = 2.0 ** -15
+
+
+def central_hessian(grad: Callable, theta, step: float = HESSIAN_STEP) -> np.ndarray:
+    """The Jacobian of ``grad`` at theta by central differences, column j = (grad(theta + h e_j) -
+    grad(theta - h e_j)) / 2h, then symmetrised: 2 P gradient evaluations."""
+    theta = np.asarray(theta, np.float64).reshape(-1)
+    h = float(step)
+    if not (np.isfinite(h) and h > 0.0):
+        raise ValueError("step must be positive and finite")
+    P = theta.size
+    H = np.empty((P, P))
+    for j in range(P):
+        e = np.zeros(P)
+        e[j] = h
+        up, dn = theta + e, theta - e
+        H[:, j] = (np.asarray(grad(up), np.float64) - np.asarray(grad(dn), np.float64)) / (up[j] - dn[j])
+    return 0.5 * (H + H.T)
+
+
+def chi2_sf(x, df: int) -> float:
+    """P(chi2_df > x) from erfc and exp alone: Q(1/2, y) = erfc(sqrt y), Q(1, y) = exp(-y) and
+    Q(a + 1, y) = Q(a, y) + y^a e^-y / Gamma(a + 1) with y = x / 2, a = df / 2: positive terms only."""
+    import math
+    df = int(df)
+    if df < 1:
+        raise ValueError("df must be a positive integer")
+    x = float(x)
+    if math.isnan(x):
+        return float("nan")
+    if x <= 0.0:
+        return 1.0
+    y = 0.5 * x
+    if df % 2:
+        a, q = 0.5, math.erfc(math.sqrt(y))
+    else:
+        a, q = 1.0, math.exp(-y)
+    while a < 0.5 * df - 0.25:
+        q += math.exp(a * math.log(y) - y - math.lgamma(a + 1.0))
+        a += 1.0
+    return min(q, 1.0)
+
+
+def likelihood_ratio_test(restricted, full) -> dict:
+    """2 (log L_full - log L_restricted) against chi2 with df = the difference in parameter counts.
+    Both are fitted models (``log_likelihood_`` and ``params_``) of which ``restricted`` is nested in
+    ``full``; returns dict(statistic, df, p_value)."""
+    ll0, ll1 = float(restricted.log_likelihood_), float(full.log_likelihood_)
+    df = len(full.params_) - len(restricted.params_)
+    if df < 1:
+        raise ValueError("the full model must have more parameters than the restricted one")
+    stat = 2.0 * (ll1 - ll0)
+    return dict(statistic=stat, df=int(df), p_value=chi2_sf(stat, df))
+
+
+def delta_standard_errors(theta, cov_theta, n_log: int) -> np.ndarray:
+    """Standard errors on the natural scale from the covariance of theta: exp(theta_j) se(theta_j)
+    for the first n_log (log-scale) entries by the delta method, se(theta_j) for the rest."""
+    theta = np.asarray(theta, np.float64).reshape(-1)
+    with np.errstate(invalid="ignore"):
+        se = np.sqrt(np.diag(np.asarray(cov_theta, np.float64)))
+    out = se.copy()
+    out[:n_log] = np.exp(theta[:n_log]) * se[:n_log]
+    return out
+
+
+_Z975 = 1.959963984540054          # the 0.975 quantile of the standard normal
+
+
+def wald_summary(theta, cov_theta, names, n_log: int) -> pd.DataFrame:
+    """estimate, se, z, p and the 95 % Wald interval per parameter.  The first n_log parameters are
+    positive and theta holds their logs: their row is built on the log scale (z = theta / se(theta),
+    which tests the parameter against 1; interval exp(theta -+ 1.96 se(theta))) and reports estimate
+    and se on the natural scale (delta method).  The other rows are direct: z tests against 0."""
+    import math
+    theta = np.asarray(theta, np.float64).reshape(-1)
+    with np.errstate(invalid="ignore"):
+        se_t = np.sqrt(np.diag(np.asarray(cov_theta, np.float64)))
+    est = theta.copy()
+    est[:n_log] = np.exp(theta[:n_log])
+    with np.errstate(invalid="ignore", divide="ignore"):
+        z = theta / se_t
+    p = np.array([math.erfc(abs(v) / math.sqrt(2.0)) if np.isfinite(v) else np.nan for v in z])
+    lo, hi = theta - _Z975 * se_t, theta + _Z975 * se_t
+    lo[:n_log], hi[:n_log] = np.exp(lo[:n_log]), np.exp(hi[:n_log])
+    return pd.DataFrame(dict(estimate=est, se=delta_standard_errors(theta, cov_theta, n_log), z=z, p=p,
+                             ci_lower=lo, ci_upper=hi), index=list(names))
+
+
+class _WaldMixin:
+    """covariance_, standard_errors_ and summary_ of a maximum-likelihood fit from the Hessian of
+    sum w log L in theta, shared by ParetoNBDFitter and GammaGammaFitter.  ``_N_LOG`` leading
+    parameters are positive and optimised on their logs."""
+    _N_LOG = 0
+
+    def _theta_names(self):
+        names = list(self.params_.index)
+        return [f"log {n}" for n in names[:self._N_LOG]] + names[self._N_LOG:]
+
+    def _theta(self) -> np.ndarray:
+        t = self.params_.to_numpy(dtype=np.float64).copy()
+        t[:self._N_LOG] = np.log(t[:self._N_LOG])
+        return t
+
+    def _set_uncertainty(self, H, scores=None, theta=None):
+        """covariance_ = (-H)^-1 on theta, or the sandwich H^-1 (sum s_i s_i') H^-1 with ``scores``
+        [N][P].  A -H that is not positive definite: NaN everywhere and one RuntimeWarning."""
+        H = np.asarray(H, np.float64)
+        P = H.shape[0]
+        theta, names = self._theta() if theta is None else np.asarray(theta, np.float64), self._theta_names()
+        cov = np.full((P, P), np.nan)
+        ok = bool(np.isfinite(H).all())
+        if ok:
+            try:
+                np.linalg.cholesky(-H)
+            except np.linalg.LinAlgError:
+                ok = False
+        if ok:
+            cov = np.linalg.inv(-H)
+            if scores is not None:
+                S = np.asarray(scores, np.float64)
+                cov = cov @ (S.T @ S) @ cov
+            cov = 0.5 * (cov + cov.T)
+        else:
+            warnings.warn(f"{type(self).__name__}: the Hessian of the log-likelihood is not negative definite "
+                          "(a boundary or a fit that did not converge): the standard errors are NaN",
+                          RuntimeWarning, stacklevel=3)
+        self.hessian_ = H
+        self.covariance_ = pd.DataFrame(cov, index=names, columns=names)
+        self.standard_errors_ = pd.Series(delta_standard_errors(theta, cov, self._N_LOG), index=list(self.params_.index))
+        self.summary_ = wald_summary(theta, cov, list(self.params_.index), self._N_LOG)
+        return self
+
+
+# ---------------------------------------------------------------------------------------------
 # Device handle
 # ---------------------------------------------------------------------------------------------
+MAX_COVARIATES = 8
+
+
 def _params_array(params) -> np.ndarray:
     p = np.ascontiguousarray(np.asarray(params, np.float64).reshape(4))
     return p
 
 
+def covariate_matrix(cov, n: int, what: str = "covariates", names=None):
+    """(z [K][n] C-contiguous float64, names) of an (n, K) array or DataFrame: the device layout, a
+    covariate per row.  ValueError on a wrong shape, more than 8 columns or a non-finite value."""
+    cols = None
+    if isinstance(cov, pd.DataFrame):
+        cols = [str(c) for c in cov.columns]
+        a = cov.to_numpy(dtype=np.float64)
+    else:
+        a = np.asarray(cov, dtype=np.float64)
+        if a.ndim == 1 and a.size == n and n > 0:
+            a = a.reshape(n, 1)
+    if a.ndim != 2 or a.shape[0] != n:
+        raise ValueError(f"{what} must have shape (N, K) with N = {n} customers; got {a.shape}")
+    K = a.shape[1]
+    if K > MAX_COVARIATES:
+        raise ValueError(f"{what}: at most {MAX_COVARIATES} columns per process; got {K}")
+    if not np.isfinite(a).all():
+        raise ValueError(f"{what} must be finite")
+    if names is not None:
+        names = [str(c) for c in names]
+        if len(names) != K:
+            raise ValueError(f"{what}: {len(names)} names for {K} columns")
+    else:
+        names = cols if cols is not None else [f"z{k}" for k in range(K)]
+    return np.ascontiguousarray(a.T), names
+
+
+def _cov_pair(covariates, covariates_dropout, n: int, names=None):
+    """((z1, names1), (z2, names2)); the dropout process takes the purchase matrix unless it has its own."""
+    z1, n1 = covariate_matrix(covariates, n, "covariates", names)
+    if covariates_dropout is None:
+        return (z1, n1), (z1, list(n1))
+    same = not isinstance(covariates_dropout, pd.DataFrame) and names is not None and \
+        np.ndim(covariates_dropout) == 2 and np.shape(covariates_dropout)[1] == len(n1)
+    return (z1, n1), covariate_matrix(covariates_dropout, n, "covariates_dropout", names if same else None)
+
+
 class PnbdData:
     """The CBS columns resident on the device for the evaluations of a fit (clv_pnbd_create)."""
 
-    def __init__(self, frequency, recency, T, weights=None, *, device: int = -1):
+    def __init__(self, frequency, recency, T, weights=None, *, device: int = -1, covariates=None,
+                 covariates_dropout=None):
+        self.k1 = self.k2 = None          # None: no covariates in the handle
+        cov = None
+        if covariates is not None:
+            cov = _cov_pair(covariates, covariates_dropout, int(np.asarray(frequency).reshape(-1).shape[0]))
+        elif covariates_dropout is not None:
+            raise ValueError("covariates_dropout without covariates: pass covariates with zero columns")
         L = _lib.lib()
         if _lib.device_count() < 1:
             raise _lib.ClvError("no HIP device visible; the Pareto/NBD likelihood has no CPU fallback")
@@ -134,6 +334,60 @@ class PnbdData:
         self._h = ctypes.c_void_p()
         check(L.clv_pnbd_create(int(device), self.n, self.x.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
                                 dptr(self.t_x), dptr(self.T), dptr(self.w), ctypes.byref(self._h)))
+        if cov is not None:
+            try:
+                self.set_covariates(cov[0][0], cov[1][0])
+            except Exception:
+                self.close()
+                raise
+
+    def set_covariates(self, z1, z2):
+        """Covariates into the handle (clv_pnbd_set_covariates): z1 [K1][n] for the purchase process,
+        z2 [K2][n] for the dropout process, a covariate per row."""
+        z1 = np.ascontiguousarray(np.asarray(z1, np.float64).reshape(-1, self.n))
+        z2 = np.ascontiguousarray(np.asarray(z2, np.float64).reshape(-1, self.n))
+        check(self._L.clv_pnbd_set_covariates(self._h, z1.shape[0], dptr(z1) if z1.size else None, z2.shape[0],
+                                              dptr(z2) if z2.size else None))
+        self.k1, self.k2 = int(z1.shape[0]), int(z2.shape[0])
+        self.z1, self.z2 = z1, z2
+
+    def _cov_params(self, params) -> np.ndarray:
+        if self.k1 is None:
+            self.set_covariates(np.empty((0, self.n)), np.empty((0, self.n)))
+        return np.ascontiguousarray(np.asarray(params, np.float64).reshape(4 + self.k1 + self.k2))
+
+    def eval_cov(self, params):
+        """(sums[6 + K1 + K2], n_unconverged) at params = (r, alpha0, s, beta0, gamma1, gamma2): the six
+        sums of :meth:`eval`, then d sum w log L / d gamma1 and / d gamma2 (clv_pnbd_eval_cov).  A handle
+        without covariates takes K1 = K2 = 0."""
+        p = self._cov_params(params)
+        sums = np.empty(6 + self.k1 + self.k2)
+        nu = ctypes.c_int64(0)
+        check(self._L.clv_pnbd_eval_cov(self._h, dptr(p), dptr(sums), ctypes.byref(nu)))
+        return sums, int(nu.value)
+
+    def customers_cov(self, params, t_star: float = 0.0) -> np.ndarray:
+        """[n][7]: log L, P(alive), E[Y(t_star) | x, t_x, T, z] and the score with respect to
+        log(r, alpha_i, s, beta_i) (clv_pnbd_customers_cov)."""
+        p = self._cov_params(params)
+        out = np.empty((self.n, 7))
+        check(self._L.clv_pnbd_customers_cov(self._h, dptr(p), float(t_star), dptr(out)))
+        return out
+
+    def scores(self, params) -> np.ndarray:
+        """[n][4 + K1 + K2]: w_i d log L_i / d theta, theta = (log r, log alpha0, log s, log beta0,
+        gamma1, gamma2), from the per-customer score of :meth:`customers_cov` by the chain rule."""
+        g = self.customers_cov(params)[:, 3:7]
+        s = np.concatenate([g, -self.z1.T * g[:, 1:2], -self.z2.T * g[:, 3:4]], axis=1)
+        return s if self.w is None else s * self.w[:, None]
+
+    def dert(self, params, delta: float, horizon: float) -> np.ndarray:
+        """[n][2]: P(alive) and the discounted expected residual transactions (clv_pnbd_dert)."""
+        k = 0 if self.k1 is None else self.k1 + self.k2
+        p = np.ascontiguousarray(np.asarray(params, np.float64).reshape(4 + k))
+        out = np.empty((self.n, 2))
+        check(self._L.clv_pnbd_dert(self._h, dptr(p), float(delta), float(horizon), dptr(out)))
+        return out
 
     def eval(self, params):
         """(sums[6], n_unconverged): sum w log L, its derivatives with respect to
@@ -178,15 +432,52 @@ def phi(k: float, ell):
 # ---------------------------------------------------------------------------------------------
 # Fitter
 # ---------------------------------------------------------------------------------------------
-class ParetoNBDFitter:
+class ParetoNBDFitter(_WaldMixin):
     """Pareto/NBD by maximum likelihood (Schmittlein, Morrison & Colombo 1987; the likelihood as in
     Fader & Hardie 2005).  ``penalizer_coef`` adds penalizer_coef * sum(params^2) to the
-    per-customer mean negative log-likelihood."""
+    per-customer mean negative log-likelihood.
+
+    With ``covariates`` the model is Fader & Hardie (2007)'s: alpha_i = alpha0 exp(-gamma1' z_i),
+    beta_i = beta0 exp(-gamma2' z_i); ``params_`` then holds r, alpha (= alpha0), s, beta (= beta0),
+    ``purchase:<name>`` per column of ``covariates`` and ``dropout:<name>`` per column of
+    ``covariates_dropout`` (the same matrix unless given), and the penalty gains
+    penalizer_coef * sum(gamma^2)."""
+    _N_LOG = 4
 
     def __init__(self, penalizer_coef: float = 0.0):
         self.penalizer_coef = float(penalizer_coef)
         self.params_: Optional[pd.Series] = None
         self._device = -1
+        self._k = None                # (K1, K2) of a covariate fit
+        self._shared_dropout = True
+
+    def _objective_cov(self, data: PnbdData):
+        pen = self.penalizer_coef
+
+        def f(theta):
+            with np.errstate(over="ignore"):
+                p = np.concatenate([np.exp(theta[:4]), theta[4:]])
+            if not (np.isfinite(p).all() and (p[:4] > 0.0).all()):
+                return np.nan, np.full(theta.size, np.nan)
+            sums, _ = data.eval_cov(p)
+            val = -sums[0] / sums[5] + pen * float((p ** 2).sum())
+            g = -np.concatenate([sums[1:5], sums[6:]]) / sums[5]
+            g[:4] += 2.0 * pen * p[:4] ** 2
+            g[4:] += 2.0 * pen * p[4:]
+            return val, g
+        return f
+
+    @staticmethod
+    def _gradient(data: PnbdData):
+        """theta -> d sum w log L / d theta on the device (the covariate entry point when the handle
+        has covariates, clv_pnbd_eval otherwise)."""
+        def g(theta):
+            p = np.concatenate([np.exp(theta[:4]), theta[4:]])
+            if data.k1 is None:
+                return data.eval(p)[0][1:5]
+            s = data.eval_cov(p)[0]
+            return np.concatenate([s[1:5], s[6:]])
+        return g
 
     def _objective(self, data: PnbdData):
         pen = self.penalizer_coef
@@ -202,24 +493,126 @@ class ParetoNBDFitter:
         return f
 
     def fit(self, frequency, recency, T, weights=None, initial_params=None, tol: float = 1e-7, max_iter: int = 200,
-            *, device: int = -1):
-        p0 = np.ones(4) if initial_params is None else np.asarray(initial_params, np.float64).reshape(4)
-        if not (np.isfinite(p0).all() and (p0 > 0.0).all()):
-            raise ValueError("initial_params must be four positive finite numbers")
+            *, device: int = -1, covariates=None, covariates_dropout=None, covariate_names=None,
+            standard_errors: bool = False, robust: bool = False):
+        """``covariates`` (N, K1) array or DataFrame for the purchase process, ``covariates_dropout``
+        (N, K2) for the dropout process (default: the same matrix; K2 = 0 allowed), at most 8 columns
+        each.  ``standard_errors=True`` fills covariance_, standard_errors_ and summary_ from 2 P more
+        gradient evaluations (``robust=True``: the sandwich covariance)."""
+        if covariates is None:
+            if covariates_dropout is not None:
+                raise ValueError("covariates_dropout without covariates: pass covariates with zero columns")
+            p0 = np.ones(4) if initial_params is None else np.asarray(initial_params, np.float64).reshape(4)
+            if not (np.isfinite(p0).all() and (p0 > 0.0).all()):
+                raise ValueError("initial_params must be four positive finite numbers")
+            with PnbdData(frequency, recency, T, weights, device=device) as data:
+                self.fit_objective(self._objective(data), p0, tol, max_iter)
+                sums, nu = data.eval(self.params_.to_numpy())
+                self._k, self._shared_dropout = None, True
+                if standard_errors:
+                    self._uncertainty(data, robust)
+            self.log_likelihood_ = float(sums[0])
+            self.n_unconverged_ = nu
+            self._device = int(device)
+            return self
+        n = int(np.asarray(frequency).reshape(-1).shape[0])
+        (z1, n1), (z2, n2) = _cov_pair(covariates, covariates_dropout, n, covariate_names)
+        names = list(PARAM_NAMES) + [f"purchase:{c}" for c in n1] + [f"dropout:{c}" for c in n2]
+        P = len(names)
+        if initial_params is None:
+            p0 = None          # below: the plain optimum with gamma = 0, so the nested fit can only gain
+        else:
+            p0 = np.asarray(initial_params, np.float64).reshape(-1)
+            if p0.size == 4:
+                p0 = np.concatenate([p0, np.zeros(P - 4)])
+        if p0 is not None and (p0.size != P or not (np.isfinite(p0).all() and (p0[:4] > 0.0).all())):
+            raise ValueError(f"initial_params must be four positive finite numbers, or those and the {P - 4} "
+                             "finite covariate coefficients")
         with PnbdData(frequency, recency, T, weights, device=device) as data:
-            self.fit_objective(self._objective(data), p0, tol, max_iter)
-            sums, nu = data.eval(self.params_.to_numpy())
+            data.set_covariates(z1, z2)
+            n_plain = 0
+            if p0 is None:
+                with warnings.catch_warnings():
+                    warnings.simplefilter("ignore", RuntimeWarning)
+                    self.fit_objective(self._objective(data), np.ones(4), tol, max_iter)
+                p0, n_plain = np.concatenate([self.params_.to_numpy(), np.zeros(P - 4)]), self.n_eval_
+            self.fit_objective(self._objective_cov(data), p0, tol, max_iter, names=names)
+            self.n_eval_ += n_plain
+            sums, nu = data.eval_cov(self.params_.to_numpy())
+            self._k, self._shared_dropout = (len(n1), len(n2)), covariates_dropout is None
+            if standard_errors:
+                self._uncertainty(data, robust)
         self.log_likelihood_ = float(sums[0])
         self.n_unconverged_ = nu
         self._device = int(device)
         return self
 
-    def fit_objective(self, value_and_grad: Callable, initial_params, tol: float = 1e-7, max_iter: int = 200):
-        """The optimiser half of fit() for any ``value_and_grad(log params)``: sets params_,
-        converged_, n_iter_, n_eval_, grad_norm_ and warns when tol was not met.  fit() calls it
-        with the device objective; the CPU tests call it with the numpy model."""
-        res = minimize_bfgs(value_and_grad, np.log(np.asarray(initial_params, np.float64).reshape(4)), tol, max_iter)
-        self.params_ = pd.Series(np.exp(res.x), index=list(PARAM_NAMES))
+    def _uncertainty(self, data: PnbdData, robust: bool, theta=None, step: float = HESSIAN_STEP):
+        theta = self._theta() if theta is None else theta
+        H = central_hessian(self._gradient(data), theta, step)
+        scores = data.scores(np.concatenate([np.exp(theta[:4]), theta[4:]])) if robust else None
+        return self._set_uncertainty(H, scores, theta)
+
+    def _data(self, frequency, recency, T, weights, covariates, covariates_dropout) -> PnbdData:
+        """The handle for a call after the fit; a covariate fit requires its covariates (ValueError
+        before any device call), a plain fit refuses them."""
+        if self._k is None:
+            if covariates is not None or covariates_dropout is not None:
+                raise ValueError("the model was fitted without covariates")
+            return PnbdData(frequency, recency, T, weights, device=self._device)
+        if covariates is None:
+            raise ValueError("the model was fitted with covariates: pass covariates=")
+        if np.shape(covariates)[0] != int(np.asarray(frequency).reshape(-1).shape[0]):
+            raise ValueError("covariates must have one row per customer")
+        z1, z2 = self._customer_matrices(covariates, covariates_dropout)
+        data = PnbdData(frequency, recency, T, weights, device=self._device)
+        try:
+            data.set_covariates(z1, z2)
+        except Exception:
+            data.close()
+            raise
+        return data
+
+    def hessian(self, frequency, recency, T, weights=None, *, covariates=None, covariates_dropout=None, theta=None,
+                step: float = HESSIAN_STEP, robust: bool = False) -> np.ndarray:
+        """The Hessian of sum w log L in theta = (log r, log alpha0, log s, log beta0, gamma1, gamma2)
+        by central differences of the device gradient (2 P evaluations, symmetrised), at the fitted
+        theta or at ``theta``.  Also sets covariance_, standard_errors_ and summary_ from it (NaN and
+        one warning where -H is not positive definite).  On a model that was not fitted, ``theta`` is
+        required and is adopted as its parameters."""
+        if self.params_ is None and theta is not None:
+            n = int(np.asarray(frequency).reshape(-1).shape[0])
+            names = list(PARAM_NAMES)
+            if covariates is not None:
+                (_, n1), (_, n2) = _cov_pair(covariates, covariates_dropout, n)
+                names += [f"purchase:{c}" for c in n1] + [f"dropout:{c}" for c in n2]
+                self._k, self._shared_dropout = (len(n1), len(n2)), covariates_dropout is None
+            t = np.asarray(theta, np.float64).reshape(-1)
+            if t.size != len(names) or not np.isfinite(t).all():
+                raise ValueError(f"theta must hold {len(names)} finite numbers")
+            self.params_ = pd.Series(np.concatenate([np.exp(t[:4]), t[4:]]), index=names)
+        theta = self._theta() if theta is None else np.asarray(theta, np.float64).reshape(-1)
+        if theta.size != len(self._fitted()) or not np.isfinite(theta).all():
+            raise ValueError(f"theta must hold {len(self._fitted())} finite numbers")
+        with self._data(frequency, recency, T, weights, covariates, covariates_dropout) as data:
+            self._uncertainty(data, robust, theta, step)
+        return self.hessian_.copy()
+
+    def scores(self, frequency, recency, T, weights=None, *, covariates=None, covariates_dropout=None) -> np.ndarray:
+        """[N][P]: w_i d log L_i / d theta at the fitted parameters: the rows of the sandwich covariance."""
+        with self._data(frequency, recency, T, weights, covariates, covariates_dropout) as data:
+            return data.scores(self._fitted())
+
+    def fit_objective(self, value_and_grad: Callable, initial_params, tol: float = 1e-7, max_iter: int = 200,
+                      *, names=None):
+        """The optimiser half of fit() for any ``value_and_grad(theta)``, theta = the logs of the first
+        four parameters and the covariate coefficients as they are: sets params_, converged_, n_iter_,
+        n_eval_, grad_norm_ and warns when tol was not met.  fit() calls it with the device objective;
+        the CPU tests call it with the numpy model."""
+        names = list(PARAM_NAMES) if names is None else list(names)
+        p0 = np.asarray(initial_params, np.float64).reshape(len(names))
+        res = minimize_bfgs(value_and_grad, np.concatenate([np.log(p0[:4]), p0[4:]]), tol, max_iter)
+        self.params_ = pd.Series(np.concatenate([np.exp(res.x[:4]), res.x[4:]]), index=names)
         self.converged_ = bool(res.converged)
         self.n_iter_, self.n_eval_ = int(res.n_iter), int(res.n_eval)
         self.grad_norm_ = float(res.grad_norm)
@@ -235,35 +628,320 @@ class ParetoNBDFitter:
             raise RuntimeError("fit() has not been called")
         return self.params_.to_numpy(dtype=np.float64)
 
-    def _customers(self, t, frequency, recency, T) -> np.ndarray:
-        with PnbdData(frequency, recency, T, device=self._device) as data:
-            return data.customers(self._fitted(), t)
+    def _customers(self, t, frequency, recency, T, covariates=None, covariates_dropout=None) -> np.ndarray:
+        p = self._fitted()
+        if self._k is None and covariates is None and covariates_dropout is None:
+            with PnbdData(frequency, recency, T, device=self._device) as data:
+                return data.customers(p, t)
+        with self._data(frequency, recency, T, None, covariates, covariates_dropout) as data:
+            return data.customers_cov(p, t)
 
-    def conditional_expected_number_of_purchases_up_to_time(self, t, frequency, recency, T) -> np.ndarray:
-        """E[Y(t) | x, t_x, T] per customer (t a scalar)."""
-        return self._customers(float(t), frequency, recency, T)[:, 2].copy()
+    def conditional_expected_number_of_purchases_up_to_time(self, t, frequency, recency, T, *, covariates=None,
+                                                            covariates_dropout=None) -> np.ndarray:
+        """E[Y(t) | x, t_x, T] per customer (t a scalar); a covariate fit requires ``covariates``."""
+        return self._customers(float(t), frequency, recency, T, covariates, covariates_dropout)[:, 2].copy()
 
-    def conditional_probability_alive(self, frequency, recency, T) -> np.ndarray:
-        return self._customers(0.0, frequency, recency, T)[:, 1].copy()
+    def conditional_probability_alive(self, frequency, recency, T, *, covariates=None,
+                                      covariates_dropout=None) -> np.ndarray:
+        return self._customers(0.0, frequency, recency, T, covariates, covariates_dropout)[:, 1].copy()
 
-    def pointwise_log_likelihood(self, frequency, recency, T) -> np.ndarray:
+    def pointwise_log_likelihood(self, frequency, recency, T, *, covariates=None, covariates_dropout=None) -> np.ndarray:
         """log L per customer at the fitted parameters (column 0 of ``clv_pnbd_customers``): marginal
         over the gamma heterogeneity of lambda and mu."""
-        return self._customers(0.0, frequency, recency, T)[:, 0].copy()
+        return self._customers(0.0, frequency, recency, T, covariates, covariates_dropout)[:, 0].copy()
 
-    def information_criteria(self, frequency, recency, T) -> dict:
+    def _dert(self, frequency, recency, T, discount_rate, periods_per_year, horizon, covariates,
+              covariates_dropout) -> np.ndarray:
+        from .analysis import ltv_params
+        p = self._fitted()
+        lp = ltv_params(discount_rate, periods_per_year, horizon)
+        if np.isinf(lp["horizon"]) and lp["delta"] == 0.0:
+            raise ValueError("an infinite horizon needs discount_rate > 0")
+        with self._data(frequency, recency, T, None, covariates, covariates_dropout) as data:
+            return data.dert(p, lp["delta"], lp["horizon"])
+
+    def discounted_expected_transactions(self, frequency, recency, T, *, discount_rate=0.15, periods_per_year=52.0,
+                                         horizon=None, covariates=None, covariates_dropout=None) -> np.ndarray:
+        """DERT per customer (Fader, Hardie & Lee 2005): P(alive) (r + x) / (alpha + T) int_0^H exp(-delta t)
+        ((beta + T) / (beta + T + t))^s dt, delta = log1p(discount_rate) / periods_per_year as
+        ``analysis.ltv_params`` forms it for ``lifetime_value``; ``horizon`` in periods, None = infinite
+        (which needs discount_rate > 0)."""
+        return self._dert(frequency, recency, T, discount_rate, periods_per_year, horizon, covariates,
+                          covariates_dropout)[:, 1].copy()
+
+    def _information_criteria_cov(self,frequency, recency, T, covariates, covariates_dropout) -> dict:
+        ll = self.pointwise_log_likelihood(frequency, recency, T, covariates=covariates,
+                                           covariates_dropout=covariates_dropout)
+        out = mle_information_criteria(ll, n_params=len(self._fitted()))
+        out["n_params"] = len(self._fitted())
+        return out
+
+    def information_criteria(self, frequency, recency, T, *, covariates=None, covariates_dropout=None) -> dict:
         """The fitted model as an entry of ``analysis.compare_models`` beside the HB models'
         ``analysis.marginal_information_criteria`` (:func:`mle_information_criteria` of
         :meth:`pointwise_log_likelihood`).  The entry is IN-SAMPLE: elpd is the log-likelihood of the
         customers the four parameters were fitted to, with the AIC-style penalty p = 4 spread evenly
         (4 / N per customer) — no customer is left out, so it flatters the MLE by what four
-        parameters can overfit N customers, and pareto_k is NaN."""
+        parameters can overfit N customers, and pareto_k is NaN.  A covariate fit is penalised by its
+        4 + K1 + K2 parameters and reports them as ``n_params``."""
+        if self._k is not None or covariates is not None or covariates_dropout is not None:
+            return self._information_criteria_cov(frequency, recency, T, covariates, covariates_dropout)
         return mle_information_criteria(self.pointwise_log_likelihood(frequency, recency, T))
 
-    def expected_number_of_purchases_up_to_time(self, t):
-        """E[X(t)] = r beta / alpha phi(s - 1, log((beta + t) / beta)), elementwise (host numpy)."""
-        r, a, s, b = self._fitted()
-        return r * b / a * phi(s - 1.0, np.log1p(np.asarray(t, np.float64) / b))
+    def expected_number_of_purchases_up_to_time(self, t, covariates=None, covariates_dropout=None):
+        """E[X(t)] = r beta / alpha phi(s - 1, log((beta + t) / beta)), elementwise (host numpy).  With
+        covariates (N rows): E[X(t) | z_i] at alpha_i, beta_i, one row per customer, shape (N,) + t.shape."""
+        p = self._fitted()
+        r, a, s, b = p[:4]
+        t = np.asarray(t, np.float64)
+        if self._k is None:
+            if covariates is not None or covariates_dropout is not None:
+                raise ValueError("the model was fitted without covariates")
+            return r * b / a * phi(s - 1.0, np.log1p(t / b))
+        if covariates is None:
+            raise ValueError("the model was fitted with covariates: pass covariates=")
+        ai, bi = self._customer_scales(covariates, covariates_dropout)
+        shape = (-1,) + (1,) * t.ndim
+        ai, bi = ai.reshape(shape), bi.reshape(shape)
+        return r * bi / ai * phi(s - 1.0, np.log1p(t[None] / bi))
+
+    def _customer_matrices(self, covariates, covariates_dropout):
+        n = int(np.shape(covariates)[0])
+        if covariates_dropout is None and not self._shared_dropout:
+            if self._k[1] > 0:
+                raise ValueError("the model was fitted with covariates_dropout: pass covariates_dropout=")
+            covariates_dropout = np.empty((n, 0))
+        (z1, _), (z2, _) = _cov_pair(covariates, covariates_dropout, n)
+        if (z1.shape[0], z2.shape[0]) != self._k:
+            raise ValueError(f"the model was fitted with {self._k[0]} purchase and {self._k[1]} dropout covariates; "
+                             f"got {z1.shape[0]} and {z2.shape[0]}")
+        return z1, z2
+
+    def _customer_scales(self, covariates, covariates_dropout):
+        """(alpha_i, beta_i) per customer at the fitted coefficients (host numpy)."""
+        z1, z2 = self._customer_matrices(covariates, covariates_dropout)
+        p = self._fitted()
+        k1 = self._k[0]
+        return p[1] * np.exp(-(p[4:4 + k1] @ z1)), p[3] * np.exp(-(p[4 + k1:] @ z2))
+
+
+# ---------------------------------------------------------------------------------------------
+# Gamma-Gamma spend model
+# ---------------------------------------------------------------------------------------------
+GG_PARAM_NAMES = ("p", "q", "gamma")
+
+
+def _gg_columns(frequency, monetary_value, allow_zero: bool = False):
+    """(n int32, m float64) validated on the host: integer n >= 1 and finite m > 0 (n = 0 rows pass
+    with ``allow_zero``, whatever their m)."""
+    f = np.asarray(frequency, np.float64).reshape(-1)
+    m = np.asarray(monetary_value, np.float64).reshape(-1)
+    if f.shape != m.shape:
+        raise ValueError("frequency and monetary_value must have the same length")
+    if f.size and not (np.isfinite(f).all() and np.all(f == np.round(f)) and f.max() <= 2 ** 31 - 1):
+        raise ValueError("frequency must hold integer transaction counts")
+    zero = f == 0
+    if (f < 0).any() or (zero.any() and not allow_zero):
+        raise ValueError("frequency must be >= 1: filter the customers without a transaction")
+    bad = ~zero & ~((m > 0.0) & np.isfinite(m))
+    if bad.any():
+        raise ValueError("monetary_value must be > 0 and finite: filter the other customers")
+    return np.ascontiguousarray(f, dtype=np.int32), np.ascontiguousarray(m)
+
+
+class GgData:
+    """Frequency, mean spend and weights resident on the device for a Gamma-Gamma fit (clv_gg_create)."""
+
+    def __init__(self, frequency, monetary_value, weights=None, *, device: int = -1):
+        self.nn, self.m = _gg_columns(frequency, monetary_value)
+        self.n = int(self.nn.shape[0])
+        self.w = None
+        if weights is not None:
+            self.w = np.ascontiguousarray(np.asarray(weights, np.float64).reshape(-1))
+            if self.w.shape[0] != self.n:
+                raise ValueError("weights must have the length of frequency")
+        L = _lib.lib()
+        if _lib.device_count() < 1:
+            raise _lib.ClvError("no HIP device visible; the Gamma-Gamma likelihood has no CPU fallback")
+        self._L = L
+        self._h = ctypes.c_void_p()
+        check(L.clv_gg_create(int(device), self.n, self.nn.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), dptr(self.m),
+                              dptr(self.w), ctypes.byref(self._h)))
+
+    def eval(self, params) -> np.ndarray:
+        """sums[5]: sum w log L, its derivatives with respect to log(p, q, gamma), sum w."""
+        p = np.ascontiguousarray(np.asarray(params, np.float64).reshape(3))
+        sums = np.empty(5)
+        check(self._L.clv_gg_eval(self._h, dptr(p), dptr(sums)))
+        return sums
+
+    def customers(self, params) -> np.ndarray:
+        """[n][4]: log L and its gradient with respect to log(p, q, gamma)."""
+        p = np.ascontiguousarray(np.asarray(params, np.float64).reshape(3))
+        out = np.empty((self.n, 4))
+        check(self._L.clv_gg_customers(self._h, dptr(p), dptr(out)))
+        return out
+
+    def scores(self, params) -> np.ndarray:
+        s = self.customers(params)[:, 1:4]
+        return s if self.w is None else s * self.w[:, None]
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.clv_gg_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def device_digamma(x, *, device: int = -1) -> np.ndarray:
+    """psi(x) for positive x as the Gamma-Gamma kernel computes it (clv_digamma)."""
+    a = np.ascontiguousarray(np.asarray(x, np.float64).reshape(-1))
+    L = _lib.lib()
+    if _lib.device_count() < 1:
+        raise _lib.ClvError("no HIP device visible")
+    out = np.empty(a.shape[0])
+    check(L.clv_digamma(int(device), a.shape[0], dptr(a), dptr(out)))
+    return out.reshape(np.shape(x))
+
+
+def device_dert_integral(s, B, delta, horizon, *, device: int = -1) -> np.ndarray:
+    """J = int_0^H exp(-delta t) (B / (B + t))^s dt per row, as the DERT kernel integrates it
+    (clv_dert_integral); horizon may be inf where delta > 0."""
+    a = [np.ascontiguousarray(v, dtype=np.float64) for v in np.broadcast_arrays(
+        *(np.asarray(v, np.float64).reshape(-1) for v in (s, B, delta, horizon)))]
+    L = _lib.lib()
+    if _lib.device_count() < 1:
+        raise _lib.ClvError("no HIP device visible")
+    out = np.empty(a[0].shape[0])
+    check(L.clv_dert_integral(int(device), a[0].shape[0], dptr(a[0]), dptr(a[1]), dptr(a[2]), dptr(a[3]), dptr(out)))
+    return out
+
+
+class GammaGammaFitter(_WaldMixin):
+    """The Gamma-Gamma model of spend per transaction by maximum likelihood (Fader, Hardie & Lee 2005;
+    Fader & Hardie 2013): mean spend m_i over n_i transactions, params_ = (p, q, gamma).
+    ``penalizer_coef`` adds penalizer_coef * sum(params^2) to the per-customer mean negative
+    log-likelihood.  The likelihood and its gradient are HIP kernels (csrc/gg.hip)."""
+    _N_LOG = 3
+
+    def __init__(self, penalizer_coef: float = 0.0):
+        self.penalizer_coef = float(penalizer_coef)
+        self.params_: Optional[pd.Series] = None
+        self._device = -1
+
+    def _objective(self, data: GgData):
+        pen = self.penalizer_coef
+
+        def f(theta):
+            with np.errstate(over="ignore"):
+                p = np.exp(theta)
+            if not (np.isfinite(p).all() and (p > 0.0).all()):
+                return np.nan, np.full(3, np.nan)
+            sums = data.eval(p)
+            return -sums[0] / sums[4] + pen * float((p ** 2).sum()), -sums[1:4] / sums[4] + 2.0 * pen * p ** 2
+        return f
+
+    def fit(self, frequency, monetary_value, weights=None, initial_params=None, tol: float = 1e-7, max_iter: int = 200,
+            *, device: int = -1, standard_errors: bool = False, robust: bool = False):
+        p0 = np.ones(3) if initial_params is None else np.asarray(initial_params, np.float64).reshape(3)
+        if not (np.isfinite(p0).all() and (p0 > 0.0).all()):
+            raise ValueError("initial_params must be three positive finite numbers")
+        with GgData(frequency, monetary_value, weights, device=device) as data:
+            self.fit_objective(self._objective(data), p0, tol, max_iter)
+            sums = data.eval(self.params_.to_numpy())
+            if standard_errors:
+                self._uncertainty(data, robust)
+        self.log_likelihood_ = float(sums[0])
+        self._device = int(device)
+        return self
+
+    def fit_objective(self, value_and_grad: Callable, initial_params, tol: float = 1e-7, max_iter: int = 200):
+        """The optimiser half of fit() for any ``value_and_grad(log params)``, as
+        :meth:`ParetoNBDFitter.fit_objective`."""
+        res = minimize_bfgs(value_and_grad, np.log(np.asarray(initial_params, np.float64).reshape(3)), tol, max_iter)
+        self.params_ = pd.Series(np.exp(res.x), index=list(GG_PARAM_NAMES))
+        self.converged_ = bool(res.converged)
+        self.n_iter_, self.n_eval_ = int(res.n_iter), int(res.n_eval)
+        self.grad_norm_ = float(res.grad_norm)
+        self.message_ = res.message
+        if not res.converged:
+            warnings.warn(f"GammaGammaFitter did not converge: {res.message} "
+                          f"(max |gradient| = {res.grad_norm:.3g} after {res.n_eval} evaluations)", RuntimeWarning,
+                          stacklevel=3)
+        return self
+
+    def _fitted(self) -> np.ndarray:
+        if self.params_ is None:
+            raise RuntimeError("fit() has not been called")
+        return self.params_.to_numpy(dtype=np.float64)
+
+    def _uncertainty(self, data: GgData, robust: bool, theta=None, step: float = HESSIAN_STEP):
+        theta = self._theta() if theta is None else theta
+        H = central_hessian(lambda t: data.eval(np.exp(t))[1:4], theta, step)
+        return self._set_uncertainty(H, data.scores(np.exp(theta)) if robust else None, theta)
+
+    def hessian(self, frequency, monetary_value, weights=None, *, theta=None, step: float = HESSIAN_STEP,
+                robust: bool = False) -> np.ndarray:
+        """The Hessian of sum w log L in theta = log(p, q, gamma) by central differences of the device
+        gradient; sets covariance_, standard_errors_ and summary_ as :meth:`ParetoNBDFitter.hessian`."""
+        if self.params_ is None and theta is not None:
+            self.params_ = pd.Series(np.exp(np.asarray(theta, np.float64).reshape(3)), index=list(GG_PARAM_NAMES))
+        theta = self._theta() if theta is None else np.asarray(theta, np.float64).reshape(3)
+        if not np.isfinite(theta).all():
+            raise ValueError("theta must hold three finite numbers")
+        with GgData(frequency, monetary_value, weights, device=self._device) as data:
+            self._uncertainty(data, robust, theta, step)
+        return self.hessian_.copy()
+
+    def pointwise_log_likelihood(self, frequency, monetary_value) -> np.ndarray:
+        with GgData(frequency, monetary_value, device=self._device) as data:
+            return data.customers(self._fitted())[:, 0].copy()
+
+    def conditional_expected_average_profit(self, frequency=None, monetary_value=None) -> np.ndarray:
+        """E[M | n, m] = p (gamma + n m) / (p n + q - 1) per customer; a customer with n = 0 gets the
+        population mean p gamma / (q - 1), which is also what no argument returns.  NaN where the
+        denominator is not positive (q <= 1 at n = 0).  Host numpy: one division per customer."""
+        p, q, g = self._fitted()
+        if frequency is None:
+            frequency, monetary_value = [0], [0.0]
+        nn, m = _gg_columns(frequency, monetary_value, allow_zero=True)
+        n = nn.astype(np.float64)
+        nm = np.where(nn == 0, 0.0, n * np.where(nn == 0, 0.0, m))
+        den = p * n + q - 1.0
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where(den > 0.0, p * (g + nm) / den, np.nan)
+
+
+def classical_lifetime_value(pnbd: ParetoNBDFitter, gg: GammaGammaFitter, cbs: pd.DataFrame, *, monetary_frequency,
+                             monetary_value, discount_rate=0.15, periods_per_year=52.0, horizon=None, covariates=None,
+                             covariates_dropout=None) -> pd.DataFrame:
+    """The classical CLV of Fader, Hardie & Lee (2005) per customer of ``cbs`` (columns x, t_x, T_cal):
+    p_alive and dert from the fitted Pareto/NBD (:meth:`ParetoNBDFitter.discounted_expected_transactions`),
+    expected_spend from the fitted Gamma-Gamma at (monetary_frequency, monetary_value) — arrays or
+    column names of ``cbs`` — and clv = dert * expected_spend.  The frame stands beside
+    ``lifetime_value(draws)["customers"]``; the discount keywords are ``lifetime_value``'s."""
+    for c in ("x", "t_x", "T_cal"):
+        if c not in cbs.columns:
+            raise ValueError(f"cbs missing required column {c!r}")
+    mf = cbs[monetary_frequency] if isinstance(monetary_frequency, str) else monetary_frequency
+    mv = cbs[monetary_value] if isinstance(monetary_value, str) else monetary_value
+    spend = gg.conditional_expected_average_profit(mf, mv)
+    if spend.shape[0] != len(cbs):
+        raise ValueError("monetary_frequency and monetary_value must have one entry per customer of cbs")
+    d = pnbd._dert(cbs["x"].to_numpy(), cbs["t_x"].to_numpy(np.float64), cbs["T_cal"].to_numpy(np.float64), discount_rate,
+                   periods_per_year, horizon, covariates, covariates_dropout)
+    return pd.DataFrame(dict(p_alive=d[:, 0], dert=d[:, 1], expected_spend=spend, clv=d[:, 1] * spend), index=cbs.index)
 
 
 def mle_information_criteria(loglik, n_params: int = 4) -> dict:
@@ -294,9 +972,13 @@ def mle_information_criteria(loglik, n_params: int = 4) -> dict:
     return out
 
 
-def pnbd_weekly_tracking(fitter: ParetoNBDFitter, birth_week, times, *, device: int = -1) -> np.ndarray:
+def pnbd_weekly_tracking(fitter: ParetoNBDFitter, birth_week, times, *, device: int = -1, covariates=None,
+                         covariates_dropout=None) -> np.ndarray:
     """cum[j] = sum_i E[X(max(times[j] - birth_week[i], 0))]: the "Pareto/NBD (MLE)" curve of the
-    reference's Figure 2 (bivariate/analysis_abe.py:434-438), summed on the device."""
+    reference's Figure 2 (bivariate/analysis_abe.py:434-438), summed on the device.  A covariate fit
+    takes the customers' ``covariates`` and sums E[X(t) | z_i] (clv_pnbd_track_cov)."""
+    if fitter._k is not None or covariates is not None or covariates_dropout is not None:
+        return _pnbd_weekly_tracking_cov(fitter, birth_week, times, device, covariates, covariates_dropout)
     L = _lib.lib()
     if _lib.device_count() < 1:
         raise _lib.ClvError("no HIP device visible; the tracking kernel has no CPU fallback")
@@ -305,6 +987,26 @@ def pnbd_weekly_tracking(fitter: ParetoNBDFitter, birth_week, times, *, device: 
     p = _params_array(fitter._fitted())
     out = np.empty(t.shape[0])
     check(L.clv_pnbd_track(int(device), b.shape[0], dptr(b), dptr(t), t.shape[0], dptr(p), dptr(out)))
+    return out
+
+
+def _pnbd_weekly_tracking_cov(fitter, birth_week, times, device, covariates, covariates_dropout) -> np.ndarray:
+    if fitter._k is None:
+        raise ValueError("the model was fitted without covariates")
+    if covariates is None:
+        raise ValueError("the model was fitted with covariates: pass covariates=")
+    b = np.ascontiguousarray(np.asarray(birth_week, np.float64).reshape(-1))
+    t = np.ascontiguousarray(np.asarray(times, np.float64).reshape(-1))
+    if np.shape(covariates)[0] != b.shape[0]:
+        raise ValueError("covariates must have one row per birth_week entry")
+    z1, z2 = fitter._customer_matrices(covariates, covariates_dropout)
+    p = np.ascontiguousarray(fitter._fitted())
+    L = _lib.lib()
+    if _lib.device_count() < 1:
+        raise _lib.ClvError("no HIP device visible; the tracking kernel has no CPU fallback")
+    out = np.empty(t.shape[0])
+    check(L.clv_pnbd_track_cov(int(device), b.shape[0], dptr(b), dptr(t), t.shape[0], dptr(p), z1.shape[0],
+                               dptr(z1) if z1.size else None, z2.shape[0], dptr(z2) if z2.size else None, dptr(out)))
     return out
 
 
