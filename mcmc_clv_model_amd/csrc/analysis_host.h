@@ -1,6 +1,6 @@
 // Host pipeline shared by the posterior-analysis translation units (analysis.hip, ltv.hip, ic.hip,
-// forecast.hip, diag.hip, score.hip): staging a host array on the device, the exact
-// per-segment sort and the percentile kernel that reads its output.  Not part of the public ABI.
+// forecast.hip, diag.hip, score.hip): the exact per-segment sort and the percentile kernel that reads
+// its output (staging a host array on the device is clv::upload of internal.h).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_segmented_radix_sort.hpp>
@@ -13,16 +13,6 @@
 #include "percentile.h"
 
 namespace clv {
-
-// buf <- a device copy of host[count], queued on st.  A null host (an optional array) leaves buf
-// null.
-template <class T>
-int upload(DevBuf& buf, const T* host, size_t count, hipStream_t st) {
-  if (!host) return CLV_OK;
-  CLV_HIP(hipMalloc(&buf.p, sizeof(T) * count));
-  CLV_HIP(hipMemcpyAsync(buf.p, host, sizeof(T) * count, hipMemcpyHostToDevice, st));
-  return CLV_OK;
-}
 
 // per, lowered to the positive count the environment variable `name` holds, if it holds one: the
 // tests' knob for a batch size (read at call time; it never raises a batch).

@@ -35,16 +35,15 @@ using namespace clv;
 struct clv_gg {
   int device = 0;
   int64_t n = 0, nb = 0;  // customers, 256-customer blocks
-  int32_t* d_n = nullptr;
-  double *d_m = nullptr, *d_w = nullptr;
-  double* d_part = nullptr;  // [nb][GG_NS]
-  double* d_out = nullptr;   // [GG_NS]
+  DevBuf nn;    // int32
+  DevBuf m, w;  // double; w null: every weight 1
+  DevBuf part;  // [nb][GG_NS]
+  DevBuf out;   // [GG_NS]
 };
 
 namespace {
 
 constexpr int GG_NS = 5;  // sum w log L, 3 gradient sums, sum w
-constexpr int GG_MAX_GRID = 2048;
 constexpr double GG_STIRLING_FROM = 32.0;  // a from which the differences use the asymptotic series
 constexpr double GG_PSI_SHIFT_TO = 10.0;   // digamma: psi(x) = psi(x + 1) - 1 / x up to here
 
@@ -119,7 +118,7 @@ __global__ __launch_bounds__(256) void gg_eval_kernel(const int32_t* nn, const d
       v[4] = wi;
     }
     for (int k = 0; k < GG_NS; ++k) red[k][threadIdx.x] = v[k];
-    tree256<GG_NS>(red);
+    tree256(red, GG_NS);
     if (threadIdx.x < GG_NS) part[b * GG_NS + threadIdx.x] = red[threadIdx.x][0];
     __syncthreads();
   }
@@ -147,8 +146,6 @@ int gg_check_params(const double* params) {
   return CLV_OK;
 }
 
-unsigned gg_grid(int64_t nb) { return (unsigned)std::min<int64_t>(nb, GG_MAX_GRID); }
-
 }  // namespace
 
 extern "C" {
@@ -166,23 +163,21 @@ int clv_gg_create(int32_t device, int64_t n, const int32_t* frequency, const dou
     if (weights && (!std::isfinite(weights[i]) || weights[i] < 0.0))
       return fail(CLV_EINVAL, "gg: negative or non-finite weight at customer " + std::to_string(i));
   }
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count < 1) return fail(CLV_EHIP, "no HIP device visible");
-  if (device >= count) return fail(CLV_EINVAL, "gg: no such device");
+  int rc = check_device(device, "gg");
+  if (rc) return rc;
   clv_gg* h = new clv_gg();
   h->n = n;
   h->nb = (n + 255) / 256;
   DeviceScope ds(device);
-  int rc = [&]() -> int {
+  rc = [&]() -> int {
     CLV_HIP(hipGetDevice(&h->device));
-    CLV_HIP(dalloc(&h->d_n, (size_t)n));
-    CLV_HIP(dalloc(&h->d_m, (size_t)n));
-    if (weights) CLV_HIP(dalloc(&h->d_w, (size_t)n));
-    CLV_HIP(dalloc(&h->d_part, (size_t)h->nb * GG_NS));
-    CLV_HIP(dalloc(&h->d_out, (size_t)GG_NS));
-    CLV_HIP(hipMemcpy(h->d_n, frequency, sizeof(int32_t) * n, hipMemcpyHostToDevice));
-    CLV_HIP(hipMemcpy(h->d_m, monetary, sizeof(double) * n, hipMemcpyHostToDevice));
-    if (weights) CLV_HIP(hipMemcpy(h->d_w, weights, sizeof(double) * n, hipMemcpyHostToDevice));
+    int rc;
+    if ((rc = upload(h->nn, frequency, (size_t)n, nullptr)) || (rc = upload(h->m, monetary, (size_t)n, nullptr)) ||
+        (rc = upload(h->w, weights, (size_t)n, nullptr)))
+      return rc;
+    CLV_HIP(hipMalloc(&h->part.p, sizeof(double) * (size_t)h->nb * GG_NS));
+    CLV_HIP(hipMalloc(&h->out.p, sizeof(double) * GG_NS));
+    CLV_HIP(hipStreamSynchronize(nullptr));  // the caller's arrays are read
     return CLV_OK;
   }();
   if (rc != CLV_OK) {
@@ -195,14 +190,7 @@ int clv_gg_create(int32_t device, int64_t n, const int32_t* frequency, const dou
 
 void clv_gg_destroy(clv_gg* h) {
   if (!h) return;
-  {
-    DeviceScope ds(h->device);
-    (void)hipFree(h->d_n);
-    (void)hipFree(h->d_m);
-    (void)hipFree(h->d_w);
-    (void)hipFree(h->d_part);
-    (void)hipFree(h->d_out);
-  }
+  DeviceScope ds(h->device);
   delete h;
 }
 
@@ -211,15 +199,13 @@ int clv_gg_eval(clv_gg* h, const double* params, double* sums) {
   int rc = gg_check_params(params);
   if (rc) return rc;
   DeviceScope ds(h->device);
-  hipLaunchKernelGGL(gg_eval_kernel, dim3(gg_grid(h->nb)), dim3(256), 0, nullptr, (const int32_t*)h->d_n,
-                     (const double*)h->d_m, (const double*)h->d_w, h->n, h->nb, params[0], params[1], params[2],
-                     h->d_part);
-  CLV_HIP(hipGetLastError());
-  hipLaunchKernelGGL(pnbd_final_kernel, dim3(GG_NS, 1), dim3(256), 0, nullptr, (const double*)h->d_part, h->nb, GG_NS,
-                     h->d_out);
-  CLV_HIP(hipGetLastError());
-  CLV_HIP(hipMemcpy(sums, h->d_out, sizeof(double) * GG_NS, hipMemcpyDeviceToHost));
-  return CLV_OK;
+  return launch_sums(
+      [&] {
+        hipLaunchKernelGGL(gg_eval_kernel, dim3(grid_for(h->nb)), dim3(256), 0, nullptr, h->nn.as<const int32_t>(),
+                           h->m.as<const double>(), h->w.as<const double>(), h->n, h->nb, params[0], params[1], params[2],
+                           h->part.as<double>());
+      },
+      h->part.as<const double>(), h->nb, GG_NS, 1, h->out.as<double>(), sums);
 }
 
 int clv_gg_customers(clv_gg* h, const double* params, double* out) {
@@ -227,13 +213,10 @@ int clv_gg_customers(clv_gg* h, const double* params, double* out) {
   int rc = gg_check_params(params);
   if (rc) return rc;
   DeviceScope ds(h->device);
-  DevBuf bo;
-  CLV_HIP(hipMalloc(&bo.p, sizeof(double) * 4 * (size_t)h->n));
-  hipLaunchKernelGGL(gg_customers_kernel, dim3(gg_grid(h->nb)), dim3(256), 0, nullptr, (const int32_t*)h->d_n,
-                     (const double*)h->d_m, h->n, params[0], params[1], params[2], bo.as<double>());
-  CLV_HIP(hipGetLastError());
-  CLV_HIP(hipMemcpy(out, bo.p, sizeof(double) * 4 * (size_t)h->n, hipMemcpyDeviceToHost));
-  return CLV_OK;
+  return launch_rows(4 * (size_t)h->n, out, [&](double* d) {
+    hipLaunchKernelGGL(gg_customers_kernel, dim3(grid_for(h->nb)), dim3(256), 0, nullptr, h->nn.as<const int32_t>(),
+                       h->m.as<const double>(), h->n, params[0], params[1], params[2], d);
+  });
 }
 
 int clv_digamma(int32_t device, int64_t n, const double* x, double* out) {
@@ -241,19 +224,15 @@ int clv_digamma(int32_t device, int64_t n, const double* x, double* out) {
   if (!x || !out) return fail(CLV_EINVAL, "digamma: null argument");
   for (int64_t i = 0; i < n; ++i)
     if (!(x[i] > 0.0) || !std::isfinite(x[i])) return fail(CLV_EINVAL, "digamma: arguments must be positive and finite");
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count < 1) return fail(CLV_EHIP, "no HIP device visible");
-  if (device >= count) return fail(CLV_EINVAL, "digamma: no such device");
+  int rc = check_device(device, "digamma");
+  if (rc) return rc;
   DeviceScope ds(device);
-  DevBuf bi, bo;
-  CLV_HIP(hipMalloc(&bi.p, sizeof(double) * (size_t)n));
-  CLV_HIP(hipMalloc(&bo.p, sizeof(double) * (size_t)n));
-  CLV_HIP(hipMemcpy(bi.p, x, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(gg_digamma_kernel, dim3(gg_grid((n + 255) / 256)), dim3(256), 0, nullptr, bi.as<const double>(), n,
-                     bo.as<double>());
-  CLV_HIP(hipGetLastError());
-  CLV_HIP(hipMemcpy(out, bo.p, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost));
-  return CLV_OK;
+  DevBuf bi;
+  if ((rc = upload(bi, x, (size_t)n, nullptr))) return rc;
+  return launch_rows((size_t)n, out, [&](double* d) {
+    hipLaunchKernelGGL(gg_digamma_kernel, dim3(grid_for((n + 255) / 256)), dim3(256), 0, nullptr, bi.as<const double>(), n,
+                       d);
+  });
 }
 
 }  // extern "C"

@@ -116,6 +116,20 @@ struct DeviceScope {
       return ::clv::fail(CLV_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_));          \
   } while (0)
 
+namespace clv {
+
+// buf <- a device copy of host[count], queued on st.  A null host (an optional array) leaves buf
+// null.
+template <class T>
+int upload(DevBuf& buf, const T* host, size_t count, hipStream_t st) {
+  if (!host) return CLV_OK;
+  CLV_HIP(hipMalloc(&buf.p, sizeof(T) * count));
+  CLV_HIP(hipMemcpyAsync(buf.p, host, sizeof(T) * count, hipMemcpyHostToDevice, st));
+  return CLV_OK;
+}
+
+}  // namespace clv
+
 struct clv_sampler {
   clv_config cfg{};
   clv_prior prior{};

@@ -43,16 +43,16 @@ using namespace clv;
 struct clv_pnbd {
   int device = 0;
   int64_t n = 0, nb = 0;  // customers, 256-customer blocks
-  int32_t* d_x = nullptr;
-  double *d_tx = nullptr, *d_T = nullptr, *d_w = nullptr;
-  double* d_part = nullptr;  // [nb][PNBD_NS] block partials
-  double* d_out = nullptr;   // [PNBD_NS]
+  DevBuf x;               // int32
+  DevBuf tx, T, w;        // double; w null: every weight 1
+  DevBuf part;            // [nb][PNBD_NS] block partials
+  DevBuf out;             // [PNBD_NS]
   // covariates (clv_pnbd_set_covariates): [k][n] each, a wavefront reads a covariate row coalesced
   bool has_cov = false;
   int32_t k1 = 0, k2 = 0;
-  double *d_z1 = nullptr, *d_z2 = nullptr;
-  double* d_partc = nullptr;  // [nb][PNBD_NS + k1 + k2]
-  double* d_outc = nullptr;   // [PNBD_NS + k1 + k2]
+  DevBuf z1, z2;
+  DevBuf partc;  // [nb][PNBD_NS + k1 + k2]
+  DevBuf outc;   // [PNBD_NS + k1 + k2]
 };
 
 namespace {
@@ -60,8 +60,7 @@ namespace {
 constexpr int PNBD_NS = 7;            // sum w log L, 4 gradient sums, sum w, unconverged customers
 constexpr int PNBD_TERM_CAP = 2048;   // series terms after u_0 (reaches z of about 0.98)
 constexpr double PNBD_EPS = 0x1p-53;  // relative remainder at which the series stops
-constexpr int PNBD_MAX_GRID = 2048;
-constexpr int PNBD_MAX_COV = 8;       // covariate columns per process
+constexpr int PNBD_MAX_COV = 8;      // covariate columns per process
 constexpr int PNBD_COV_GROUP = 8;     // covariate sums reduced per pass over the LDS tile
 
 struct Params {
@@ -192,55 +191,6 @@ __host__ __device__ inline double pnbd_expected(double t, const Params& p) {
   return p.r * p.b / p.a * pnbd_phi(p.s - 1.0, log1p(t / p.b));
 }
 
-__global__ __launch_bounds__(256) void pnbd_eval_kernel(const int32_t* x, const double* tx, const double* T,
-                                                        const double* w, int64_t n, int64_t nb, Params p,
-                                                        double* part /*[nb][PNBD_NS]*/) {
-  __shared__ double red[PNBD_NS][256];
-  for (int64_t b = blockIdx.x; b < nb; b += gridDim.x) {
-    const int64_t i = b * 256 + threadIdx.x;
-    double v[PNBD_NS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-    if (i < n) {
-      const Point q = pnbd_point(x[i], tx[i], T[i], p);
-      const double wi = w ? w[i] : 1.0;
-      v[0] = wi * q.logL;
-      for (int j = 0; j < 4; ++j) v[1 + j] = wi * q.g[j];
-      v[5] = wi;
-      v[6] = q.conv ? 0.0 : 1.0;
-    }
-    for (int k = 0; k < PNBD_NS; ++k) red[k][threadIdx.x] = v[k];
-    tree256<PNBD_NS>(red);
-    if (threadIdx.x < PNBD_NS) part[b * PNBD_NS + threadIdx.x] = red[threadIdx.x][0];
-    __syncthreads();
-  }
-}
-
-__global__ __launch_bounds__(256) void pnbd_customers_kernel(const int32_t* x, const double* tx, const double* T,
-                                                             int64_t n, Params p, double t_star,
-                                                             double* out /*[n][3]*/) {
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    const Point q = pnbd_point(x[i], tx[i], T[i], p);
-    const double Ti = T[i];
-    out[i * 3 + 0] = q.logL;
-    out[i * 3 + 1] = q.p_alive;
-    out[i * 3 + 2] = q.p_alive * (p.r + (double)x[i]) * (p.b + Ti) / (p.a + Ti) *
-                     pnbd_phi(p.s - 1.0, log1p(t_star / (p.b + Ti)));
-  }
-}
-
-// part[j][b] = tree sum over block b's customers of E[X(max(times[j] - birth, 0))]; grid (blocks, times).
-__global__ __launch_bounds__(256) void pnbd_track_kernel(const double* birth, const double* times, int64_t n,
-                                                         int64_t nb, Params p, double* part /*[n_times][nb]*/) {
-  __shared__ double red[1][256];
-  const double tj = times[blockIdx.y];
-  for (int64_t b = blockIdx.x; b < nb; b += gridDim.x) {
-    const int64_t i = b * 256 + threadIdx.x;
-    red[0][threadIdx.x] = i < n ? pnbd_expected(fmax(tj - birth[i], 0.0), p) : 0.0;
-    tree256<1>(red);
-    if (threadIdx.x == 0) part[(int64_t)blockIdx.y * nb + b] = red[0][0];
-    __syncthreads();
-  }
-}
-
 // theta of the covariate model: the four baseline parameters and the coefficients of each process.
 struct CovParams {
   double r, a0, s, b0;
@@ -258,31 +208,42 @@ __device__ inline Params pnbd_cov_params(const CovParams& c, const double* z1, c
   return Params{c.r, c.a0 * exp(-e1), c.s, c.b0 * exp(-e2)};
 }
 
-// tree256 over the first m rows of the tile: per row the additions of tree256, whatever m is.
-__device__ __forceinline__ void tree256n(double (*red)[256], int m) {
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
-    if ((int)threadIdx.x < off)
-      for (int k = 0; k < m; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + off];
-    __syncthreads();
-  }
-}
+// Where a kernel takes customer i's (r, alpha_i, s, beta_i) from: every kernel below is one body
+// compiled for the two sources.  Plain: the same four for every customer, from the kernel arguments.
+struct PlainSource {
+  static constexpr bool COV = false;
+  Params p;
+  __device__ Params at(int64_t) const { return p; }
+};
 
-// part[b][0..7) as pnbd_eval_kernel; part[b][7 + k] = tree sum of w g_logalpha,i (-z1[k][i]) for k < k1 and
-// of w g_logbeta,i (-z2[k - k1][i]) after them.  The covariate sums go through the tile in groups of
-// PNBD_COV_GROUP rows; a row's tree does not see the other rows, so the grouping is not in the bits.
-__global__ __launch_bounds__(256) void pnbd_eval_cov_kernel(const int32_t* x, const double* tx, const double* T,
-                                                            const double* w, const double* z1, const double* z2,
-                                                            int64_t n, int64_t nb, CovParams c,
-                                                            double* part /*[nb][PNBD_NS + k1 + k2]*/) {
+// Covariates: the customer's own alpha_i and beta_i, formed per lane from the covariate rows z [k][n].
+struct CovSource {
+  static constexpr bool COV = true;
+  CovParams c;
+  const double *z1, *z2;
+  int64_t n;
+  __device__ Params at(int64_t i) const { return pnbd_cov_params(c, z1, z2, n, i); }
+};
+
+// part[b][0..7) = block b's tree sums of w log L, the four w g, w and the unconverged count.  With
+// covariates, part[b][7 + k] = tree sum of w g_logalpha,i (-z1[k][i]) for k < k1 and of
+// w g_logbeta,i (-z2[k - k1][i]) after them, through the tile in groups of PNBD_COV_GROUP rows (the tile
+// is 8 rows high then, 7 without); a row's tree does not see the other rows, so the grouping is not in
+// the bits, and the first seven are the plain instance's.
+template <class Src>
+__global__ __launch_bounds__(256) void pnbd_eval_kernel(const int32_t* x, const double* tx, const double* T,
+                                                        const double* w, int64_t n, int64_t nb, Src src,
+                                                        double* part /*[nb][PNBD_NS + k1 + k2]*/) {
   static_assert(PNBD_COV_GROUP >= PNBD_NS, "the tile holds the seven baseline sums");
-  __shared__ double red[PNBD_COV_GROUP][256];
-  const int nc = c.k1 + c.k2, ns = PNBD_NS + nc;
+  __shared__ double red[Src::COV ? PNBD_COV_GROUP : PNBD_NS][256];
+  int nc = 0;
+  if constexpr (Src::COV) nc = src.c.k1 + src.c.k2;
+  const int ns = PNBD_NS + nc;
   for (int64_t b = blockIdx.x; b < nb; b += gridDim.x) {
     const int64_t i = b * 256 + threadIdx.x;
     double v[PNBD_NS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     if (i < n) {
-      const Params p = pnbd_cov_params(c, z1, z2, n, i);
+      const Params p = src.at(i);
       const Point q = pnbd_point(x[i], tx[i], T[i], p);
       const double wi = w ? w[i] : 1.0;
       v[0] = wi * q.logL;
@@ -291,53 +252,58 @@ __global__ __launch_bounds__(256) void pnbd_eval_cov_kernel(const int32_t* x, co
       v[6] = q.conv ? 0.0 : 1.0;
     }
     for (int k = 0; k < PNBD_NS; ++k) red[k][threadIdx.x] = v[k];
-    tree256<PNBD_NS>(red);
+    tree256(red, PNBD_NS);
     if (threadIdx.x < PNBD_NS) part[b * ns + threadIdx.x] = red[threadIdx.x][0];
     __syncthreads();
-    for (int k0 = 0; k0 < nc; k0 += PNBD_COV_GROUP) {
-      const int m = nc - k0 < PNBD_COV_GROUP ? nc - k0 : PNBD_COV_GROUP;
-      for (int j = 0; j < m; ++j) {
-        const int k = k0 + j;
-        double t = 0.0;
-        if (i < n) t = k < c.k1 ? v[2] * -z1[(int64_t)k * n + i] : v[4] * -z2[(int64_t)(k - c.k1) * n + i];
-        red[j][threadIdx.x] = t;
+    if constexpr (Src::COV) {
+      for (int k0 = 0; k0 < nc; k0 += PNBD_COV_GROUP) {
+        const int m = nc - k0 < PNBD_COV_GROUP ? nc - k0 : PNBD_COV_GROUP;
+        for (int j = 0; j < m; ++j) {
+          const int k = k0 + j;
+          double t = 0.0;
+          if (i < n)
+            t = k < src.c.k1 ? v[2] * -src.z1[(int64_t)k * n + i] : v[4] * -src.z2[(int64_t)(k - src.c.k1) * n + i];
+          red[j][threadIdx.x] = t;
+        }
+        tree256(red, m);
+        if ((int)threadIdx.x < m) part[b * ns + PNBD_NS + k0 + threadIdx.x] = red[threadIdx.x][0];
+        __syncthreads();
       }
-      tree256n(red, m);
-      if ((int)threadIdx.x < m) part[b * ns + PNBD_NS + k0 + threadIdx.x] = red[threadIdx.x][0];
-      __syncthreads();
     }
   }
 }
 
-// out[i] = log L, P(alive), E[Y(t*) | x, t_x, T, z_i] and the score components d log L_i /
-// d log(r, alpha_i, s, beta_i); the first three as pnbd_customers_kernel writes them.
-__global__ __launch_bounds__(256) void pnbd_customers_cov_kernel(const int32_t* x, const double* tx, const double* T,
-                                                                 const double* z1, const double* z2, int64_t n,
-                                                                 CovParams c, double t_star, double* out /*[n][7]*/) {
+// out[i] = log L, P(alive), E[Y(t*) | x, t_x, T]; with covariates E[Y(t*) | x, t_x, T, z_i] and then the
+// score components d log L_i / d log(r, alpha_i, s, beta_i).
+template <class Src>
+__global__ __launch_bounds__(256) void pnbd_customers_kernel(const int32_t* x, const double* tx, const double* T,
+                                                             int64_t n, Src src, double t_star,
+                                                             double* out /*[n][3], with covariates [n][7]*/) {
+  constexpr int W = Src::COV ? 7 : 3;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    const Params p = pnbd_cov_params(c, z1, z2, n, i);
+    const Params p = src.at(i);
     const Point q = pnbd_point(x[i], tx[i], T[i], p);
     const double Ti = T[i];
-    out[i * 7 + 0] = q.logL;
-    out[i * 7 + 1] = q.p_alive;
-    out[i * 7 + 2] = q.p_alive * (p.r + (double)x[i]) * (p.b + Ti) / (p.a + Ti) *
+    out[i * W + 0] = q.logL;
+    out[i * W + 1] = q.p_alive;
+    out[i * W + 2] = q.p_alive * (p.r + (double)x[i]) * (p.b + Ti) / (p.a + Ti) *
                      pnbd_phi(p.s - 1.0, log1p(t_star / (p.b + Ti)));
-    for (int j = 0; j < 4; ++j) out[i * 7 + 3 + j] = q.g[j];
+    if constexpr (Src::COV)
+      for (int j = 0; j < 4; ++j) out[i * W + 3 + j] = q.g[j];
   }
 }
 
-// pnbd_track_kernel with E[X(t) | z_i] = r beta_i / alpha_i phi(s - 1, log((beta_i + t) / beta_i)).
-__global__ __launch_bounds__(256) void pnbd_track_cov_kernel(const double* birth, const double* times,
-                                                             const double* z1, const double* z2, int64_t n, int64_t nb,
-                                                             CovParams c, double* part /*[n_times][nb]*/) {
+// part[j][b] = tree sum over block b's customers of E[X(max(times[j] - birth, 0))], with covariates of
+// E[X(t) | z_i] = r beta_i / alpha_i phi(s - 1, log((beta_i + t) / beta_i)); grid (blocks, times).
+template <class Src>
+__global__ __launch_bounds__(256) void pnbd_track_kernel(const double* birth, const double* times, int64_t n,
+                                                         int64_t nb, Src src, double* part /*[n_times][nb]*/) {
   __shared__ double red[1][256];
   const double tj = times[blockIdx.y];
   for (int64_t b = blockIdx.x; b < nb; b += gridDim.x) {
     const int64_t i = b * 256 + threadIdx.x;
-    double e = 0.0;
-    if (i < n) e = pnbd_expected(fmax(tj - birth[i], 0.0), pnbd_cov_params(c, z1, z2, n, i));
-    red[0][threadIdx.x] = e;
-    tree256<1>(red);
+    red[0][threadIdx.x] = i < n ? pnbd_expected(fmax(tj - birth[i], 0.0), src.at(i)) : 0.0;
+    tree256(red, 1);
     if (threadIdx.x == 0) part[(int64_t)blockIdx.y * nb + b] = red[0][0];
     __syncthreads();
   }
@@ -396,10 +362,10 @@ __host__ __device__ inline double pnbd_dert_integral(double s, double B, double 
 
 // out[i] = P(alive), DERT = P(alive) (r + x) / (alpha_i + T) J(s, beta_i + T, delta, H).
 __global__ __launch_bounds__(256) void pnbd_dert_kernel(const int32_t* x, const double* tx, const double* T,
-                                                        const double* z1, const double* z2, int64_t n, CovParams c,
-                                                        double delta, double H, double* out /*[n][2]*/) {
+                                                        int64_t n, CovSource src, double delta, double H,
+                                                        double* out /*[n][2]*/) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-    const Params p = pnbd_cov_params(c, z1, z2, n, i);
+    const Params p = src.at(i);
     const double Ti = T[i];
     const Point q = pnbd_point(x[i], tx[i], Ti, p);
     out[i * 2 + 0] = q.p_alive;
@@ -421,8 +387,6 @@ int check_params(const double* params, Params* p) {
   *p = Params{params[0], params[1], params[2], params[3]};
   return CLV_OK;
 }
-
-unsigned grid_for(int64_t nb) { return (unsigned)std::min<int64_t>(nb, PNBD_MAX_GRID); }
 
 // params = (r, alpha0, s, beta0, gamma1[k1], gamma2[k2]).
 int check_cov_params(const double* params, int32_t k1, int32_t k2, CovParams* c) {
@@ -449,6 +413,78 @@ int check_covariates(int64_t n, int32_t k1, const double* z1, int32_t k2, const 
   return CLV_OK;
 }
 
+int check_t_star(double t_star) {
+  if (!(t_star >= 0.0) || !std::isfinite(t_star)) return fail(CLV_EINVAL, "pnbd: t_star must be >= 0 and finite");
+  return CLV_OK;
+}
+
+// The two tracking entries: the arguments that need no data first, the values after the parameters.
+int check_track_args(int64_t n, const double* birth_week, const double* times, int32_t n_times, const double* cum) {
+  if (n <= 0 || n_times < 1 || n_times > 65535) return fail(CLV_EINVAL, "pnbd: n must be >= 1 and n_times in 1..65535");
+  if (!birth_week || !times || !cum) return fail(CLV_EINVAL, "pnbd: null argument");
+  return CLV_OK;
+}
+
+int check_track_values(int64_t n, const double* birth_week, const double* times, int32_t n_times) {
+  for (int64_t i = 0; i < n; ++i)
+    if (!std::isfinite(birth_week[i])) return fail(CLV_EINVAL, "pnbd: non-finite birth_week");
+  for (int32_t j = 0; j < n_times; ++j)
+    if (!std::isfinite(times[j])) return fail(CLV_EINVAL, "pnbd: non-finite time");
+  return CLV_OK;
+}
+
+CovSource cov_source(const clv_pnbd* h, const CovParams& c) {
+  return CovSource{c, h->z1.as<const double>(), h->z2.as<const double>(), h->n};
+}
+
+// sums[0..6) and *n_unconverged from the seven baseline sums of the handle's customers at src, then the
+// nc covariate sums; part and out are the handle's buffers of that width.
+template <class Src>
+int eval_sums(clv_pnbd* h, const Src& src, int nc, const DevBuf& part, const DevBuf& out, double* sums,
+              int64_t* n_unconverged) {
+  DeviceScope ds(h->device);
+  double res[PNBD_NS + 2 * PNBD_MAX_COV];
+  int rc = launch_sums(
+      [&] {
+        hipLaunchKernelGGL(pnbd_eval_kernel<Src>, dim3(grid_for(h->nb)), dim3(256), 0, nullptr, h->x.as<const int32_t>(),
+                           h->tx.as<const double>(), h->T.as<const double>(), h->w.as<const double>(), h->n, h->nb, src,
+                           part.as<double>());
+      },
+      part.as<const double>(), h->nb, PNBD_NS + nc, 1, out.as<double>(), res);
+  if (rc) return rc;
+  for (int k = 0; k < 6; ++k) sums[k] = res[k];
+  for (int k = 0; k < nc; ++k) sums[6 + k] = res[PNBD_NS + k];
+  if (n_unconverged) *n_unconverged = (int64_t)res[6];
+  return CLV_OK;
+}
+
+// out [n][3], with covariates [n][7]: pnbd_customers_kernel over the handle's customers.
+template <class Src>
+int customer_rows(clv_pnbd* h, const Src& src, double t_star, double* out) {
+  DeviceScope ds(h->device);
+  return launch_rows((Src::COV ? 7 : 3) * (size_t)h->n, out, [&](double* d) {
+    hipLaunchKernelGGL(pnbd_customers_kernel<Src>, dim3(grid_for(h->nb)), dim3(256), 0, nullptr,
+                       h->x.as<const int32_t>(), h->tx.as<const double>(), h->T.as<const double>(), h->n, src, t_star, d);
+  });
+}
+
+// cum [n_times] of pnbd_track_kernel at src, on the current device.
+template <class Src>
+int track_sums(int64_t n, const double* birth_week, const double* times, int32_t n_times, const Src& src, double* cum) {
+  const int64_t nb = (n + 255) / 256;
+  DevBuf bb, bt, bp, bo;
+  int rc;
+  if ((rc = upload(bb, birth_week, (size_t)n, nullptr)) || (rc = upload(bt, times, (size_t)n_times, nullptr))) return rc;
+  CLV_HIP(hipMalloc(&bp.p, sizeof(double) * (size_t)n_times * (size_t)nb));
+  CLV_HIP(hipMalloc(&bo.p, sizeof(double) * (size_t)n_times));
+  return launch_sums(
+      [&] {
+        hipLaunchKernelGGL(pnbd_track_kernel<Src>, dim3(grid_for(nb), (unsigned)n_times), dim3(256), 0, nullptr,
+                           bb.as<const double>(), bt.as<const double>(), n, nb, src, bp.as<double>());
+      },
+      bp.as<const double>(), nb, 1, n_times, bo.as<double>(), cum);
+}
+
 }  // namespace
 
 extern "C" {
@@ -468,25 +504,21 @@ int clv_pnbd_create(int32_t device, int64_t n, const int32_t* x, const double* t
     if (weights && (!std::isfinite(weights[i]) || weights[i] < 0.0))
       return fail(CLV_EINVAL, "pnbd: negative or non-finite weight at customer " + std::to_string(i));
   }
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count < 1) return fail(CLV_EHIP, "no HIP device visible");
-  if (device >= count) return fail(CLV_EINVAL, "pnbd: no such device");
+  int rc = check_device(device, "pnbd");
+  if (rc) return rc;
   clv_pnbd* h = new clv_pnbd();
   h->n = n;
   h->nb = (n + 255) / 256;
   DeviceScope ds(device);
-  int rc = [&]() -> int {
+  rc = [&]() -> int {
     CLV_HIP(hipGetDevice(&h->device));
-    CLV_HIP(dalloc(&h->d_x, (size_t)n));
-    CLV_HIP(dalloc(&h->d_tx, (size_t)n));
-    CLV_HIP(dalloc(&h->d_T, (size_t)n));
-    if (weights) CLV_HIP(dalloc(&h->d_w, (size_t)n));
-    CLV_HIP(dalloc(&h->d_part, (size_t)h->nb * PNBD_NS));
-    CLV_HIP(dalloc(&h->d_out, (size_t)PNBD_NS));
-    CLV_HIP(hipMemcpy(h->d_x, x, sizeof(int32_t) * n, hipMemcpyHostToDevice));
-    CLV_HIP(hipMemcpy(h->d_tx, t_x, sizeof(double) * n, hipMemcpyHostToDevice));
-    CLV_HIP(hipMemcpy(h->d_T, T, sizeof(double) * n, hipMemcpyHostToDevice));
-    if (weights) CLV_HIP(hipMemcpy(h->d_w, weights, sizeof(double) * n, hipMemcpyHostToDevice));
+    int rc;
+    if ((rc = upload(h->x, x, (size_t)n, nullptr)) || (rc = upload(h->tx, t_x, (size_t)n, nullptr)) ||
+        (rc = upload(h->T, T, (size_t)n, nullptr)) || (rc = upload(h->w, weights, (size_t)n, nullptr)))
+      return rc;
+    CLV_HIP(hipMalloc(&h->part.p, sizeof(double) * (size_t)h->nb * PNBD_NS));
+    CLV_HIP(hipMalloc(&h->out.p, sizeof(double) * PNBD_NS));
+    CLV_HIP(hipStreamSynchronize(nullptr));  // the caller's arrays are read
     return CLV_OK;
   }();
   if (rc != CLV_OK) {
@@ -499,19 +531,7 @@ int clv_pnbd_create(int32_t device, int64_t n, const int32_t* x, const double* t
 
 void clv_pnbd_destroy(clv_pnbd* h) {
   if (!h) return;
-  {
-    DeviceScope ds(h->device);
-    (void)hipFree(h->d_x);
-    (void)hipFree(h->d_tx);
-    (void)hipFree(h->d_T);
-    (void)hipFree(h->d_w);
-    (void)hipFree(h->d_part);
-    (void)hipFree(h->d_out);
-    (void)hipFree(h->d_z1);
-    (void)hipFree(h->d_z2);
-    (void)hipFree(h->d_partc);
-    (void)hipFree(h->d_outc);
-  }
+  DeviceScope ds(h->device);
   delete h;
 }
 
@@ -520,64 +540,27 @@ int clv_pnbd_eval(clv_pnbd* h, const double* params, double* sums, int64_t* n_un
   Params p;
   int rc = check_params(params, &p);
   if (rc) return rc;
-  DeviceScope ds(h->device);
-  hipLaunchKernelGGL(pnbd_eval_kernel, dim3(grid_for(h->nb)), dim3(256), 0, nullptr, (const int32_t*)h->d_x,
-                     (const double*)h->d_tx, (const double*)h->d_T, (const double*)h->d_w, h->n, h->nb, p, h->d_part);
-  CLV_HIP(hipGetLastError());
-  hipLaunchKernelGGL(pnbd_final_kernel, dim3(PNBD_NS, 1), dim3(256), 0, nullptr, (const double*)h->d_part, h->nb,
-                     PNBD_NS, h->d_out);
-  CLV_HIP(hipGetLastError());
-  double res[PNBD_NS];
-  CLV_HIP(hipMemcpy(res, h->d_out, sizeof(res), hipMemcpyDeviceToHost));
-  for (int k = 0; k < 6; ++k) sums[k] = res[k];
-  if (n_unconverged) *n_unconverged = (int64_t)res[6];
-  return CLV_OK;
+  return eval_sums(h, PlainSource{p}, 0, h->part, h->out, sums, n_unconverged);
 }
 
 int clv_pnbd_customers(clv_pnbd* h, const double* params, double t_star, double* out) {
   if (!h || !out) return fail(CLV_EINVAL, "pnbd: null handle or output");
   Params p;
   int rc = check_params(params, &p);
-  if (rc) return rc;
-  if (!(t_star >= 0.0) || !std::isfinite(t_star)) return fail(CLV_EINVAL, "pnbd: t_star must be >= 0 and finite");
-  DeviceScope ds(h->device);
-  DevBuf bo;
-  CLV_HIP(hipMalloc(&bo.p, sizeof(double) * 3 * (size_t)h->n));
-  hipLaunchKernelGGL(pnbd_customers_kernel, dim3(grid_for(h->nb)), dim3(256), 0, nullptr, (const int32_t*)h->d_x,
-                     (const double*)h->d_tx, (const double*)h->d_T, h->n, p, t_star, bo.as<double>());
-  CLV_HIP(hipGetLastError());
-  CLV_HIP(hipMemcpy(out, bo.p, sizeof(double) * 3 * (size_t)h->n, hipMemcpyDeviceToHost));
-  return CLV_OK;
+  if (rc || (rc = check_t_star(t_star))) return rc;
+  return customer_rows(h, PlainSource{p}, t_star, out);
 }
 
+// No device-count check here, and none of device against the count in clv_pnbd_track_cov: a call
+// without a usable device fails at its first allocation.
 int clv_pnbd_track(int32_t device, int64_t n, const double* birth_week, const double* times, int32_t n_times,
                    const double* params, double* cum) {
-  if (n <= 0 || n_times < 1 || n_times > 65535) return fail(CLV_EINVAL, "pnbd: n must be >= 1 and n_times in 1..65535");
-  if (!birth_week || !times || !cum) return fail(CLV_EINVAL, "pnbd: null argument");
-  Params p;
-  int rc = check_params(params, &p);
+  int rc = check_track_args(n, birth_week, times, n_times, cum);
   if (rc) return rc;
-  for (int64_t i = 0; i < n; ++i)
-    if (!std::isfinite(birth_week[i])) return fail(CLV_EINVAL, "pnbd: non-finite birth_week");
-  for (int32_t j = 0; j < n_times; ++j)
-    if (!std::isfinite(times[j])) return fail(CLV_EINVAL, "pnbd: non-finite time");
+  Params p;
+  if ((rc = check_params(params, &p)) || (rc = check_track_values(n, birth_week, times, n_times))) return rc;
   DeviceScope ds(device);
-  const int64_t nb = (n + 255) / 256;
-  DevBuf bb, bt, bp, bo;
-  CLV_HIP(hipMalloc(&bb.p, sizeof(double) * (size_t)n));
-  CLV_HIP(hipMalloc(&bt.p, sizeof(double) * (size_t)n_times));
-  CLV_HIP(hipMalloc(&bp.p, sizeof(double) * (size_t)n_times * (size_t)nb));
-  CLV_HIP(hipMalloc(&bo.p, sizeof(double) * (size_t)n_times));
-  CLV_HIP(hipMemcpy(bb.p, birth_week, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
-  CLV_HIP(hipMemcpy(bt.p, times, sizeof(double) * (size_t)n_times, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(pnbd_track_kernel, dim3(grid_for(nb), (unsigned)n_times), dim3(256), 0, nullptr,
-                     bb.as<const double>(), bt.as<const double>(), n, nb, p, bp.as<double>());
-  CLV_HIP(hipGetLastError());
-  hipLaunchKernelGGL(pnbd_final_kernel, dim3(1, (unsigned)n_times), dim3(256), 0, nullptr, bp.as<const double>(), nb, 1,
-                     bo.as<double>());
-  CLV_HIP(hipGetLastError());
-  CLV_HIP(hipMemcpy(cum, bo.p, sizeof(double) * (size_t)n_times, hipMemcpyDeviceToHost));
-  return CLV_OK;
+  return track_sums(n, birth_week, times, n_times, PlainSource{p}, cum);
 }
 
 int clv_pnbd_set_covariates(clv_pnbd* h, int32_t k1, const double* z1, int32_t k2, const double* z2) {
@@ -585,29 +568,18 @@ int clv_pnbd_set_covariates(clv_pnbd* h, int32_t k1, const double* z1, int32_t k
   int rc = check_covariates(h->n, k1, z1, k2, z2);
   if (rc) return rc;
   DeviceScope ds(h->device);
-  double *n1 = nullptr, *n2 = nullptr, *np = nullptr, *no = nullptr;
+  DevBuf n1, n2, np, no;  // a failure frees them: the handle keeps what it had
   const size_t ns = (size_t)(PNBD_NS + k1 + k2);
-  rc = [&]() -> int {
-    if (k1) CLV_HIP(dalloc(&n1, (size_t)k1 * (size_t)h->n));
-    if (k2) CLV_HIP(dalloc(&n2, (size_t)k2 * (size_t)h->n));
-    CLV_HIP(dalloc(&np, (size_t)h->nb * ns));
-    CLV_HIP(dalloc(&no, ns));
-    if (k1) CLV_HIP(hipMemcpy(n1, z1, sizeof(double) * (size_t)k1 * (size_t)h->n, hipMemcpyHostToDevice));
-    if (k2) CLV_HIP(hipMemcpy(n2, z2, sizeof(double) * (size_t)k2 * (size_t)h->n, hipMemcpyHostToDevice));
-    return CLV_OK;
-  }();
-  if (rc != CLV_OK) {  // the handle keeps what it had
-    (void)hipFree(n1);
-    (void)hipFree(n2);
-    (void)hipFree(np);
-    (void)hipFree(no);
+  if ((k1 && (rc = upload(n1, z1, (size_t)k1 * (size_t)h->n, nullptr))) ||
+      (k2 && (rc = upload(n2, z2, (size_t)k2 * (size_t)h->n, nullptr))))
     return rc;
-  }
-  (void)hipFree(h->d_z1);
-  (void)hipFree(h->d_z2);
-  (void)hipFree(h->d_partc);
-  (void)hipFree(h->d_outc);
-  h->d_z1 = n1, h->d_z2 = n2, h->d_partc = np, h->d_outc = no;
+  CLV_HIP(hipMalloc(&np.p, sizeof(double) * (size_t)h->nb * ns));
+  CLV_HIP(hipMalloc(&no.p, sizeof(double) * ns));
+  CLV_HIP(hipStreamSynchronize(nullptr));  // the caller's arrays are read
+  std::swap(h->z1.p, n1.p);                // the locals free what the handle had
+  std::swap(h->z2.p, n2.p);
+  std::swap(h->partc.p, np.p);
+  std::swap(h->outc.p, no.p);
   h->k1 = k1, h->k2 = k2, h->has_cov = true;
   return CLV_OK;
 }
@@ -618,21 +590,7 @@ int clv_pnbd_eval_cov(clv_pnbd* h, const double* params, double* sums, int64_t* 
   CovParams c;
   int rc = check_cov_params(params, h->k1, h->k2, &c);
   if (rc) return rc;
-  const int nc = h->k1 + h->k2, ns = PNBD_NS + nc;
-  DeviceScope ds(h->device);
-  hipLaunchKernelGGL(pnbd_eval_cov_kernel, dim3(grid_for(h->nb)), dim3(256), 0, nullptr, (const int32_t*)h->d_x,
-                     (const double*)h->d_tx, (const double*)h->d_T, (const double*)h->d_w, (const double*)h->d_z1,
-                     (const double*)h->d_z2, h->n, h->nb, c, h->d_partc);
-  CLV_HIP(hipGetLastError());
-  hipLaunchKernelGGL(pnbd_final_kernel, dim3((unsigned)ns, 1), dim3(256), 0, nullptr, (const double*)h->d_partc, h->nb,
-                     ns, h->d_outc);
-  CLV_HIP(hipGetLastError());
-  double res[PNBD_NS + 2 * PNBD_MAX_COV];
-  CLV_HIP(hipMemcpy(res, h->d_outc, sizeof(double) * (size_t)ns, hipMemcpyDeviceToHost));
-  for (int k = 0; k < 6; ++k) sums[k] = res[k];
-  for (int k = 0; k < nc; ++k) sums[6 + k] = res[PNBD_NS + k];
-  if (n_unconverged) *n_unconverged = (int64_t)res[6];
-  return CLV_OK;
+  return eval_sums(h, cov_source(h, c), h->k1 + h->k2, h->partc, h->outc, sums, n_unconverged);
 }
 
 int clv_pnbd_customers_cov(clv_pnbd* h, const double* params, double t_star, double* out) {
@@ -640,17 +598,8 @@ int clv_pnbd_customers_cov(clv_pnbd* h, const double* params, double t_star, dou
   if (!h->has_cov) return fail(CLV_EINVAL, "pnbd: the handle has no covariates (clv_pnbd_set_covariates)");
   CovParams c;
   int rc = check_cov_params(params, h->k1, h->k2, &c);
-  if (rc) return rc;
-  if (!(t_star >= 0.0) || !std::isfinite(t_star)) return fail(CLV_EINVAL, "pnbd: t_star must be >= 0 and finite");
-  DeviceScope ds(h->device);
-  DevBuf bo;
-  CLV_HIP(hipMalloc(&bo.p, sizeof(double) * 7 * (size_t)h->n));
-  hipLaunchKernelGGL(pnbd_customers_cov_kernel, dim3(grid_for(h->nb)), dim3(256), 0, nullptr, (const int32_t*)h->d_x,
-                     (const double*)h->d_tx, (const double*)h->d_T, (const double*)h->d_z1, (const double*)h->d_z2, h->n,
-                     c, t_star, bo.as<double>());
-  CLV_HIP(hipGetLastError());
-  CLV_HIP(hipMemcpy(out, bo.p, sizeof(double) * 7 * (size_t)h->n, hipMemcpyDeviceToHost));
-  return CLV_OK;
+  if (rc || (rc = check_t_star(t_star))) return rc;
+  return customer_rows(h, cov_source(h, c), t_star, out);
 }
 
 int clv_pnbd_dert(clv_pnbd* h, const double* params, double delta, double horizon, double* out) {
@@ -663,14 +612,10 @@ int clv_pnbd_dert(clv_pnbd* h, const double* params, double delta, double horizo
   if (std::isinf(horizon) && delta == 0.0)
     return fail(CLV_EINVAL, "pnbd: an infinite horizon needs a discount rate > 0");
   DeviceScope ds(h->device);
-  DevBuf bo;
-  CLV_HIP(hipMalloc(&bo.p, sizeof(double) * 2 * (size_t)h->n));
-  hipLaunchKernelGGL(pnbd_dert_kernel, dim3(grid_for(h->nb)), dim3(256), 0, nullptr, (const int32_t*)h->d_x,
-                     (const double*)h->d_tx, (const double*)h->d_T, (const double*)h->d_z1, (const double*)h->d_z2, h->n,
-                     c, delta, horizon, bo.as<double>());
-  CLV_HIP(hipGetLastError());
-  CLV_HIP(hipMemcpy(out, bo.p, sizeof(double) * 2 * (size_t)h->n, hipMemcpyDeviceToHost));
-  return CLV_OK;
+  return launch_rows(2 * (size_t)h->n, out, [&](double* d) {
+    hipLaunchKernelGGL(pnbd_dert_kernel, dim3(grid_for(h->nb)), dim3(256), 0, nullptr, h->x.as<const int32_t>(),
+                       h->tx.as<const double>(), h->T.as<const double>(), h->n, cov_source(h, c), delta, horizon, d);
+  });
 }
 
 int clv_dert_integral(int32_t device, int64_t n, const double* s, const double* B, const double* delta,
@@ -685,64 +630,33 @@ int clv_dert_integral(int32_t device, int64_t n, const double* s, const double* 
     if (std::isinf(horizon[i]) && delta[i] == 0.0)
       return fail(CLV_EINVAL, "dert: an infinite horizon needs a discount rate > 0");
   }
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count < 1) return fail(CLV_EHIP, "no HIP device visible");
-  if (device >= count) return fail(CLV_EINVAL, "dert: no such device");
+  int rc = check_device(device, "dert");
+  if (rc) return rc;
   DeviceScope ds(device);
-  DevBuf bi, bo;
-  const size_t bytes = sizeof(double) * (size_t)n;
-  CLV_HIP(hipMalloc(&bi.p, 4 * bytes));
-  CLV_HIP(hipMalloc(&bo.p, bytes));
-  double* in = bi.as<double>();
-  CLV_HIP(hipMemcpy(in, s, bytes, hipMemcpyHostToDevice));
-  CLV_HIP(hipMemcpy(in + n, B, bytes, hipMemcpyHostToDevice));
-  CLV_HIP(hipMemcpy(in + 2 * n, delta, bytes, hipMemcpyHostToDevice));
-  CLV_HIP(hipMemcpy(in + 3 * n, horizon, bytes, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(pnbd_dert_integral_kernel, dim3(grid_for((n + 255) / 256)), dim3(256), 0, nullptr,
-                     (const double*)in, (const double*)(in + n), (const double*)(in + 2 * n),
-                     (const double*)(in + 3 * n), n, bo.as<double>());
-  CLV_HIP(hipGetLastError());
-  CLV_HIP(hipMemcpy(out, bo.p, bytes, hipMemcpyDeviceToHost));
-  return CLV_OK;
+  DevBuf bs, bB, bd, bh;
+  if ((rc = upload(bs, s, (size_t)n, nullptr)) || (rc = upload(bB, B, (size_t)n, nullptr)) ||
+      (rc = upload(bd, delta, (size_t)n, nullptr)) || (rc = upload(bh, horizon, (size_t)n, nullptr)))
+    return rc;
+  return launch_rows((size_t)n, out, [&](double* d) {
+    hipLaunchKernelGGL(pnbd_dert_integral_kernel, dim3(grid_for((n + 255) / 256)), dim3(256), 0, nullptr,
+                       bs.as<const double>(), bB.as<const double>(), bd.as<const double>(), bh.as<const double>(), n, d);
+  });
 }
 
 int clv_pnbd_track_cov(int32_t device, int64_t n, const double* birth_week, const double* times, int32_t n_times,
                        const double* params, int32_t k1, const double* z1, int32_t k2, const double* z2, double* cum) {
-  if (n <= 0 || n_times < 1 || n_times > 65535) return fail(CLV_EINVAL, "pnbd: n must be >= 1 and n_times in 1..65535");
-  if (!birth_week || !times || !cum) return fail(CLV_EINVAL, "pnbd: null argument");
-  int rc = check_covariates(n, k1, z1, k2, z2);
+  int rc = check_track_args(n, birth_week, times, n_times, cum);
   if (rc) return rc;
   CovParams c;
-  rc = check_cov_params(params, k1, k2, &c);
-  if (rc) return rc;
-  for (int64_t i = 0; i < n; ++i)
-    if (!std::isfinite(birth_week[i])) return fail(CLV_EINVAL, "pnbd: non-finite birth_week");
-  for (int32_t j = 0; j < n_times; ++j)
-    if (!std::isfinite(times[j])) return fail(CLV_EINVAL, "pnbd: non-finite time");
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count < 1) return fail(CLV_EHIP, "no HIP device visible");
+  if ((rc = check_covariates(n, k1, z1, k2, z2)) || (rc = check_cov_params(params, k1, k2, &c)) ||
+      (rc = check_track_values(n, birth_week, times, n_times)) || (rc = check_device(-1, "pnbd")))
+    return rc;
   DeviceScope ds(device);
-  const int64_t nb = (n + 255) / 256;
-  DevBuf bb, bt, b1, b2, bp, bo;
-  CLV_HIP(hipMalloc(&bb.p, sizeof(double) * (size_t)n));
-  CLV_HIP(hipMalloc(&bt.p, sizeof(double) * (size_t)n_times));
-  if (k1) CLV_HIP(hipMalloc(&b1.p, sizeof(double) * (size_t)k1 * (size_t)n));
-  if (k2) CLV_HIP(hipMalloc(&b2.p, sizeof(double) * (size_t)k2 * (size_t)n));
-  CLV_HIP(hipMalloc(&bp.p, sizeof(double) * (size_t)n_times * (size_t)nb));
-  CLV_HIP(hipMalloc(&bo.p, sizeof(double) * (size_t)n_times));
-  CLV_HIP(hipMemcpy(bb.p, birth_week, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
-  CLV_HIP(hipMemcpy(bt.p, times, sizeof(double) * (size_t)n_times, hipMemcpyHostToDevice));
-  if (k1) CLV_HIP(hipMemcpy(b1.p, z1, sizeof(double) * (size_t)k1 * (size_t)n, hipMemcpyHostToDevice));
-  if (k2) CLV_HIP(hipMemcpy(b2.p, z2, sizeof(double) * (size_t)k2 * (size_t)n, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(pnbd_track_cov_kernel, dim3(grid_for(nb), (unsigned)n_times), dim3(256), 0, nullptr,
-                     bb.as<const double>(), bt.as<const double>(), b1.as<const double>(), b2.as<const double>(), n, nb, c,
-                     bp.as<double>());
-  CLV_HIP(hipGetLastError());
-  hipLaunchKernelGGL(pnbd_final_kernel, dim3(1, (unsigned)n_times), dim3(256), 0, nullptr, bp.as<const double>(), nb, 1,
-                     bo.as<double>());
-  CLV_HIP(hipGetLastError());
-  CLV_HIP(hipMemcpy(cum, bo.p, sizeof(double) * (size_t)n_times, hipMemcpyDeviceToHost));
-  return CLV_OK;
+  DevBuf b1, b2;
+  if ((k1 && (rc = upload(b1, z1, (size_t)k1 * (size_t)n, nullptr))) ||
+      (k2 && (rc = upload(b2, z2, (size_t)k2 * (size_t)n, nullptr))))
+    return rc;
+  return track_sums(n, birth_week, times, n_times, CovSource{c, b1.as<const double>(), b2.as<const double>(), n}, cum);
 }
 
 }  // extern "C"

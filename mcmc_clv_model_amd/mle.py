@@ -27,6 +27,7 @@ gradient; the Gamma-Gamma likelihood (csrc/gg.hip) and the DERT integral are HIP
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import warnings
 from types import SimpleNamespace
@@ -208,10 +209,12 @@ def wald_summary(theta, cov_theta, names, n_log: int) -> pd.DataFrame:
 
 
 class _WaldMixin:
-    """covariance_, standard_errors_ and summary_ of a maximum-likelihood fit from the Hessian of
-    sum w log L in theta, shared by ParetoNBDFitter and GammaGammaFitter.  ``_N_LOG`` leading
-    parameters are positive and optimised on their logs."""
+    """What ParetoNBDFitter and GammaGammaFitter share: the optimiser half of fit(), and covariance_,
+    standard_errors_ and summary_ from the Hessian of sum w log L in theta.  The ``_N_LOG`` leading
+    parameters (``_NAMES``) are positive and optimised on their logs; a fitter adds
+    ``_gradient(data)``, theta -> d sum w log L / d theta on the device."""
     _N_LOG = 0
+    _NAMES = ()
 
     def _theta_names(self):
         names = list(self.params_.index)
@@ -221,6 +224,37 @@ class _WaldMixin:
         t = self.params_.to_numpy(dtype=np.float64).copy()
         t[:self._N_LOG] = np.log(t[:self._N_LOG])
         return t
+
+    def _natural(self, theta) -> np.ndarray:
+        """The parameters of theta: exp of its first _N_LOG entries, the rest as they are."""
+        return np.concatenate([np.exp(theta[:self._N_LOG]), theta[self._N_LOG:]])
+
+    def _fitted(self) -> np.ndarray:
+        if self.params_ is None:
+            raise RuntimeError("fit() has not been called")
+        return self.params_.to_numpy(dtype=np.float64)
+
+    def _fit_objective(self, value_and_grad: Callable, initial_params, tol: float, max_iter: int, names=None):
+        """fit_objective of both fitters (their caller's caller gets the warning)."""
+        names = list(self._NAMES if names is None else names)
+        p0 = np.asarray(initial_params, np.float64).reshape(len(names))
+        L = self._N_LOG
+        res = minimize_bfgs(value_and_grad, np.concatenate([np.log(p0[:L]), p0[L:]]), tol, max_iter)
+        self.params_ = pd.Series(self._natural(res.x), index=names)
+        self.converged_ = bool(res.converged)
+        self.n_iter_, self.n_eval_ = int(res.n_iter), int(res.n_eval)
+        self.grad_norm_ = float(res.grad_norm)
+        self.message_ = res.message
+        if not res.converged:
+            warnings.warn(f"{type(self).__name__} did not converge: {res.message} "
+                          f"(max |gradient| = {res.grad_norm:.3g} after {res.n_eval} evaluations)", RuntimeWarning,
+                          stacklevel=4)
+        return self
+
+    def _uncertainty(self, data, robust: bool, theta=None, step: float = HESSIAN_STEP):
+        theta = self._theta() if theta is None else theta
+        H = central_hessian(self._gradient(data), theta, step)
+        return self._set_uncertainty(H, data.scores(self._natural(theta)) if robust else None, theta)
 
     def _set_uncertainty(self, H, scores=None, theta=None):
         """covariance_ = (-H)^-1 on theta, or the sandwich H^-1 (sum s_i s_i') H^-1 with ``scores``
@@ -258,9 +292,27 @@ class _WaldMixin:
 MAX_COVARIATES = 8
 
 
-def _params_array(params) -> np.ndarray:
-    p = np.ascontiguousarray(np.asarray(params, np.float64).reshape(4))
-    return p
+class _Handle:
+    """A handle of the C library (``_h``, freed by the entry ``_DESTROY`` of ``_L``): closed by close(),
+    on leaving its ``with`` block and when collected."""
+    _DESTROY = ""
+
+    def close(self):
+        if getattr(self, "_h", None):
+            getattr(self._L, self._DESTROY)(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def covariate_matrix(cov, n: int, what: str = "covariates", names=None):
@@ -300,8 +352,9 @@ def _cov_pair(covariates, covariates_dropout, n: int, names=None):
     return (z1, n1), covariate_matrix(covariates_dropout, n, "covariates_dropout", names if same else None)
 
 
-class PnbdData:
+class PnbdData(_Handle):
     """The CBS columns resident on the device for the evaluations of a fit (clv_pnbd_create)."""
+    _DESTROY = "clv_pnbd_destroy"
 
     def __init__(self, frequency, recency, T, weights=None, *, device: int = -1, covariates=None,
                  covariates_dropout=None):
@@ -315,9 +368,10 @@ class PnbdData:
         if _lib.device_count() < 1:
             raise _lib.ClvError("no HIP device visible; the Pareto/NBD likelihood has no CPU fallback")
         f = np.asarray(frequency)
-        if f.size and not np.all(np.asarray(f, np.float64) == np.round(np.asarray(f, np.float64))):
+        ff = np.asarray(f, np.float64)
+        if f.size and not np.all(ff == np.round(ff)):
             raise ValueError("frequency must hold integer repeat counts")
-        if f.size and (np.asarray(f, np.float64).max() > 2 ** 31 - 1 or np.asarray(f, np.float64).min() < -2 ** 31):
+        if f.size and (ff.max() > 2 ** 31 - 1 or ff.min() < -2 ** 31):
             raise ValueError("frequency exceeds int32")
         self.x = np.ascontiguousarray(f, dtype=np.int32).reshape(-1)
         self.t_x = np.ascontiguousarray(np.asarray(recency, np.float64).reshape(-1))
@@ -351,28 +405,40 @@ class PnbdData:
         self.k1, self.k2 = int(z1.shape[0]), int(z2.shape[0])
         self.z1, self.z2 = z1, z2
 
-    def _cov_params(self, params) -> np.ndarray:
-        if self.k1 is None:
+    def _params(self, params, cov: bool) -> np.ndarray:
+        """params as a plain entry takes them (4) or, ``cov``, a covariate entry (4 + K1 + K2; a handle
+        without covariates is given K1 = K2 = 0 first)."""
+        if cov and self.k1 is None:
             self.set_covariates(np.empty((0, self.n)), np.empty((0, self.n)))
-        return np.ascontiguousarray(np.asarray(params, np.float64).reshape(4 + self.k1 + self.k2))
+        k = self.k1 + self.k2 if cov else 0
+        return np.ascontiguousarray(np.asarray(params, np.float64).reshape(4 + k))
+
+    def _evaluate(self, params, cov: bool):
+        """(sums, n_unconverged) of clv_pnbd_eval or, ``cov``, clv_pnbd_eval_cov."""
+        p = self._params(params, cov)
+        sums = np.empty(p.size + 2)
+        nu = ctypes.c_int64(0)
+        entry = self._L.clv_pnbd_eval_cov if cov else self._L.clv_pnbd_eval
+        check(entry(self._h, dptr(p), dptr(sums), ctypes.byref(nu)))
+        return sums, int(nu.value)
+
+    def _per_customer(self, entry: str, width: int, params, cov: bool, *args) -> np.ndarray:
+        """[n][width] of the per-customer entry ``entry(handle, params, *args, out)``."""
+        p = self._params(params, cov)
+        out = np.empty((self.n, width))
+        check(getattr(self._L, entry)(self._h, dptr(p), *args, dptr(out)))
+        return out
 
     def eval_cov(self, params):
         """(sums[6 + K1 + K2], n_unconverged) at params = (r, alpha0, s, beta0, gamma1, gamma2): the six
         sums of :meth:`eval`, then d sum w log L / d gamma1 and / d gamma2 (clv_pnbd_eval_cov).  A handle
         without covariates takes K1 = K2 = 0."""
-        p = self._cov_params(params)
-        sums = np.empty(6 + self.k1 + self.k2)
-        nu = ctypes.c_int64(0)
-        check(self._L.clv_pnbd_eval_cov(self._h, dptr(p), dptr(sums), ctypes.byref(nu)))
-        return sums, int(nu.value)
+        return self._evaluate(params, True)
 
     def customers_cov(self, params, t_star: float = 0.0) -> np.ndarray:
         """[n][7]: log L, P(alive), E[Y(t_star) | x, t_x, T, z] and the score with respect to
         log(r, alpha_i, s, beta_i) (clv_pnbd_customers_cov)."""
-        p = self._cov_params(params)
-        out = np.empty((self.n, 7))
-        check(self._L.clv_pnbd_customers_cov(self._h, dptr(p), float(t_star), dptr(out)))
-        return out
+        return self._per_customer("clv_pnbd_customers_cov", 7, params, True, float(t_star))
 
     def scores(self, params) -> np.ndarray:
         """[n][4 + K1 + K2]: w_i d log L_i / d theta, theta = (log r, log alpha0, log s, log beta0,
@@ -383,44 +449,16 @@ class PnbdData:
 
     def dert(self, params, delta: float, horizon: float) -> np.ndarray:
         """[n][2]: P(alive) and the discounted expected residual transactions (clv_pnbd_dert)."""
-        k = 0 if self.k1 is None else self.k1 + self.k2
-        p = np.ascontiguousarray(np.asarray(params, np.float64).reshape(4 + k))
-        out = np.empty((self.n, 2))
-        check(self._L.clv_pnbd_dert(self._h, dptr(p), float(delta), float(horizon), dptr(out)))
-        return out
+        return self._per_customer("clv_pnbd_dert", 2, params, self.k1 is not None, float(delta), float(horizon))
 
     def eval(self, params):
         """(sums[6], n_unconverged): sum w log L, its derivatives with respect to
         log(r, alpha, s, beta), sum w; customers whose series hit the term cap (sums[0] is NaN then)."""
-        p = _params_array(params)
-        sums = np.empty(6)
-        nu = ctypes.c_int64(0)
-        check(self._L.clv_pnbd_eval(self._h, dptr(p), dptr(sums), ctypes.byref(nu)))
-        return sums, int(nu.value)
+        return self._evaluate(params, False)
 
     def customers(self, params, t_star: float = 0.0) -> np.ndarray:
         """[n][3]: log L, P(alive), E[Y(t_star) | x, t_x, T]."""
-        p = _params_array(params)
-        out = np.empty((self.n, 3))
-        check(self._L.clv_pnbd_customers(self._h, dptr(p), float(t_star), dptr(out)))
-        return out
-
-    def close(self):
-        if self._h:
-            self._L.clv_pnbd_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._per_customer("clv_pnbd_customers", 3, params, False, float(t_star))
 
 
 def phi(k: float, ell):
@@ -443,6 +481,7 @@ class ParetoNBDFitter(_WaldMixin):
     ``covariates_dropout`` (the same matrix unless given), and the penalty gains
     penalizer_coef * sum(gamma^2)."""
     _N_LOG = 4
+    _NAMES = PARAM_NAMES
 
     def __init__(self, penalizer_coef: float = 0.0):
         self.penalizer_coef = float(penalizer_coef)
@@ -451,15 +490,18 @@ class ParetoNBDFitter(_WaldMixin):
         self._k = None                # (K1, K2) of a covariate fit
         self._shared_dropout = True
 
-    def _objective_cov(self, data: PnbdData):
+    def _objective(self, data: PnbdData, cov: bool = False):
+        """theta -> (penalised mean negative log-likelihood, its gradient) from clv_pnbd_eval, or ``cov``
+        from clv_pnbd_eval_cov: the plain model is the covariate model without trailing coefficients."""
         pen = self.penalizer_coef
+        evaluate = data.eval_cov if cov else data.eval
 
         def f(theta):
             with np.errstate(over="ignore"):
-                p = np.concatenate([np.exp(theta[:4]), theta[4:]])
+                p = self._natural(theta)
             if not (np.isfinite(p).all() and (p[:4] > 0.0).all()):
                 return np.nan, np.full(theta.size, np.nan)
-            sums, _ = data.eval_cov(p)
+            sums, _ = evaluate(p)
             val = -sums[0] / sums[5] + pen * float((p ** 2).sum())
             g = -np.concatenate([sums[1:5], sums[6:]]) / sums[5]
             g[:4] += 2.0 * pen * p[:4] ** 2
@@ -467,30 +509,15 @@ class ParetoNBDFitter(_WaldMixin):
             return val, g
         return f
 
-    @staticmethod
-    def _gradient(data: PnbdData):
+    def _gradient(self, data: PnbdData):
         """theta -> d sum w log L / d theta on the device (the covariate entry point when the handle
         has covariates, clv_pnbd_eval otherwise)."""
+        evaluate = data.eval if data.k1 is None else data.eval_cov
+
         def g(theta):
-            p = np.concatenate([np.exp(theta[:4]), theta[4:]])
-            if data.k1 is None:
-                return data.eval(p)[0][1:5]
-            s = data.eval_cov(p)[0]
+            s = evaluate(self._natural(theta))[0]
             return np.concatenate([s[1:5], s[6:]])
         return g
-
-    def _objective(self, data: PnbdData):
-        pen = self.penalizer_coef
-
-        def f(theta):
-            with np.errstate(over="ignore"):
-                p = np.exp(theta)
-            if not (np.isfinite(p).all() and (p > 0.0).all()):
-                return np.nan, np.full(4, np.nan)
-            sums, _ = data.eval(p)
-            val = -sums[0] / sums[5] + pen * float((p ** 2).sum())
-            return val, -sums[1:5] / sums[5] + 2.0 * pen * p ** 2
-        return f
 
     def fit(self, frequency, recency, T, weights=None, initial_params=None, tol: float = 1e-7, max_iter: int = 200,
             *, device: int = -1, covariates=None, covariates_dropout=None, covariate_names=None,
@@ -499,59 +526,48 @@ class ParetoNBDFitter(_WaldMixin):
         (N, K2) for the dropout process (default: the same matrix; K2 = 0 allowed), at most 8 columns
         each.  ``standard_errors=True`` fills covariance_, standard_errors_ and summary_ from 2 P more
         gradient evaluations (``robust=True``: the sandwich covariance)."""
-        if covariates is None:
-            if covariates_dropout is not None:
-                raise ValueError("covariates_dropout without covariates: pass covariates with zero columns")
-            p0 = np.ones(4) if initial_params is None else np.asarray(initial_params, np.float64).reshape(4)
-            if not (np.isfinite(p0).all() and (p0 > 0.0).all()):
-                raise ValueError("initial_params must be four positive finite numbers")
-            with PnbdData(frequency, recency, T, weights, device=device) as data:
-                self.fit_objective(self._objective(data), p0, tol, max_iter)
-                sums, nu = data.eval(self.params_.to_numpy())
-                self._k, self._shared_dropout = None, True
-                if standard_errors:
-                    self._uncertainty(data, robust)
-            self.log_likelihood_ = float(sums[0])
-            self.n_unconverged_ = nu
-            self._device = int(device)
-            return self
-        n = int(np.asarray(frequency).reshape(-1).shape[0])
-        (z1, n1), (z2, n2) = _cov_pair(covariates, covariates_dropout, n, covariate_names)
-        names = list(PARAM_NAMES) + [f"purchase:{c}" for c in n1] + [f"dropout:{c}" for c in n2]
+        cov = covariates is not None
+        names, k = list(PARAM_NAMES), None
+        if cov:
+            n = int(np.asarray(frequency).reshape(-1).shape[0])
+            (z1, n1), (z2, n2) = _cov_pair(covariates, covariates_dropout, n, covariate_names)
+            names += [f"purchase:{c}" for c in n1] + [f"dropout:{c}" for c in n2]
+            k = (len(n1), len(n2))
+        elif covariates_dropout is not None:
+            raise ValueError("covariates_dropout without covariates: pass covariates with zero columns")
         P = len(names)
-        if initial_params is None:
-            p0 = None          # below: the plain optimum with gamma = 0, so the nested fit can only gain
-        else:
-            p0 = np.asarray(initial_params, np.float64).reshape(-1)
+        p0 = None
+        if initial_params is not None:
+            p0 = np.asarray(initial_params, np.float64).reshape(-1 if cov else 4)
             if p0.size == 4:
                 p0 = np.concatenate([p0, np.zeros(P - 4)])
-        if p0 is not None and (p0.size != P or not (np.isfinite(p0).all() and (p0[:4] > 0.0).all())):
-            raise ValueError(f"initial_params must be four positive finite numbers, or those and the {P - 4} "
-                             "finite covariate coefficients")
+            if p0.size != P or not (np.isfinite(p0).all() and (p0[:4] > 0.0).all()):
+                raise ValueError("initial_params must be four positive finite numbers" +
+                                 (f", or those and the {P - 4} finite covariate coefficients" if cov else ""))
         with PnbdData(frequency, recency, T, weights, device=device) as data:
-            data.set_covariates(z1, z2)
-            n_plain = 0
-            if p0 is None:
-                with warnings.catch_warnings():
-                    warnings.simplefilter("ignore", RuntimeWarning)
-                    self.fit_objective(self._objective(data), np.ones(4), tol, max_iter)
-                p0, n_plain = np.concatenate([self.params_.to_numpy(), np.zeros(P - 4)]), self.n_eval_
-            self.fit_objective(self._objective_cov(data), p0, tol, max_iter, names=names)
-            self.n_eval_ += n_plain
-            sums, nu = data.eval_cov(self.params_.to_numpy())
-            self._k, self._shared_dropout = (len(n1), len(n2)), covariates_dropout is None
+            if cov:
+                data.set_covariates(z1, z2)
+            if p0 is None or not cov:
+                # the plain fit; a covariate fit without initial_params starts from its optimum with
+                # gamma = 0, so the nested fit can only gain, and leaves the warnings to its own stage
+                with warnings.catch_warnings() if cov else contextlib.nullcontext():
+                    if cov:
+                        warnings.simplefilter("ignore", RuntimeWarning)
+                    self.fit_objective(self._objective(data), np.ones(4) if p0 is None else p0, tol, max_iter)
+            if cov:
+                n_plain = 0
+                if p0 is None:
+                    p0, n_plain = np.concatenate([self.params_.to_numpy(), np.zeros(P - 4)]), self.n_eval_
+                self.fit_objective(self._objective(data, True), p0, tol, max_iter, names=names)
+                self.n_eval_ += n_plain
+            sums, nu = data._evaluate(self.params_.to_numpy(), cov)
+            self._k, self._shared_dropout = k, covariates_dropout is None
             if standard_errors:
                 self._uncertainty(data, robust)
         self.log_likelihood_ = float(sums[0])
         self.n_unconverged_ = nu
         self._device = int(device)
         return self
-
-    def _uncertainty(self, data: PnbdData, robust: bool, theta=None, step: float = HESSIAN_STEP):
-        theta = self._theta() if theta is None else theta
-        H = central_hessian(self._gradient(data), theta, step)
-        scores = data.scores(np.concatenate([np.exp(theta[:4]), theta[4:]])) if robust else None
-        return self._set_uncertainty(H, scores, theta)
 
     def _data(self, frequency, recency, T, weights, covariates, covariates_dropout) -> PnbdData:
         """The handle for a call after the fit; a covariate fit requires its covariates (ValueError
@@ -590,7 +606,7 @@ class ParetoNBDFitter(_WaldMixin):
             t = np.asarray(theta, np.float64).reshape(-1)
             if t.size != len(names) or not np.isfinite(t).all():
                 raise ValueError(f"theta must hold {len(names)} finite numbers")
-            self.params_ = pd.Series(np.concatenate([np.exp(t[:4]), t[4:]]), index=names)
+            self.params_ = pd.Series(self._natural(t), index=names)
         theta = self._theta() if theta is None else np.asarray(theta, np.float64).reshape(-1)
         if theta.size != len(self._fitted()) or not np.isfinite(theta).all():
             raise ValueError(f"theta must hold {len(self._fitted())} finite numbers")
@@ -609,32 +625,12 @@ class ParetoNBDFitter(_WaldMixin):
         four parameters and the covariate coefficients as they are: sets params_, converged_, n_iter_,
         n_eval_, grad_norm_ and warns when tol was not met.  fit() calls it with the device objective;
         the CPU tests call it with the numpy model."""
-        names = list(PARAM_NAMES) if names is None else list(names)
-        p0 = np.asarray(initial_params, np.float64).reshape(len(names))
-        res = minimize_bfgs(value_and_grad, np.concatenate([np.log(p0[:4]), p0[4:]]), tol, max_iter)
-        self.params_ = pd.Series(np.concatenate([np.exp(res.x[:4]), res.x[4:]]), index=names)
-        self.converged_ = bool(res.converged)
-        self.n_iter_, self.n_eval_ = int(res.n_iter), int(res.n_eval)
-        self.grad_norm_ = float(res.grad_norm)
-        self.message_ = res.message
-        if not res.converged:
-            warnings.warn(f"ParetoNBDFitter did not converge: {res.message} "
-                          f"(max |gradient| = {res.grad_norm:.3g} after {res.n_eval} evaluations)", RuntimeWarning,
-                          stacklevel=3)
-        return self
-
-    def _fitted(self) -> np.ndarray:
-        if self.params_ is None:
-            raise RuntimeError("fit() has not been called")
-        return self.params_.to_numpy(dtype=np.float64)
+        return self._fit_objective(value_and_grad, initial_params, tol, max_iter, names)
 
     def _customers(self, t, frequency, recency, T, covariates=None, covariates_dropout=None) -> np.ndarray:
         p = self._fitted()
-        if self._k is None and covariates is None and covariates_dropout is None:
-            with PnbdData(frequency, recency, T, device=self._device) as data:
-                return data.customers(p, t)
         with self._data(frequency, recency, T, None, covariates, covariates_dropout) as data:
-            return data.customers_cov(p, t)
+            return data.customers(p, t) if self._k is None else data.customers_cov(p, t)
 
     def conditional_expected_number_of_purchases_up_to_time(self, t, frequency, recency, T, *, covariates=None,
                                                             covariates_dropout=None) -> np.ndarray:
@@ -669,13 +665,6 @@ class ParetoNBDFitter(_WaldMixin):
         return self._dert(frequency, recency, T, discount_rate, periods_per_year, horizon, covariates,
                           covariates_dropout)[:, 1].copy()
 
-    def _information_criteria_cov(self,frequency, recency, T, covariates, covariates_dropout) -> dict:
-        ll = self.pointwise_log_likelihood(frequency, recency, T, covariates=covariates,
-                                           covariates_dropout=covariates_dropout)
-        out = mle_information_criteria(ll, n_params=len(self._fitted()))
-        out["n_params"] = len(self._fitted())
-        return out
-
     def information_criteria(self, frequency, recency, T, *, covariates=None, covariates_dropout=None) -> dict:
         """The fitted model as an entry of ``analysis.compare_models`` beside the HB models'
         ``analysis.marginal_information_criteria`` (:func:`mle_information_criteria` of
@@ -684,9 +673,12 @@ class ParetoNBDFitter(_WaldMixin):
         (4 / N per customer) — no customer is left out, so it flatters the MLE by what four
         parameters can overfit N customers, and pareto_k is NaN.  A covariate fit is penalised by its
         4 + K1 + K2 parameters and reports them as ``n_params``."""
-        if self._k is not None or covariates is not None or covariates_dropout is not None:
-            return self._information_criteria_cov(frequency, recency, T, covariates, covariates_dropout)
-        return mle_information_criteria(self.pointwise_log_likelihood(frequency, recency, T))
+        ll = self.pointwise_log_likelihood(frequency, recency, T, covariates=covariates,
+                                           covariates_dropout=covariates_dropout)
+        out = mle_information_criteria(ll, n_params=len(self._fitted()))
+        if self._k is not None:
+            out["n_params"] = len(self._fitted())
+        return out
 
     def expected_number_of_purchases_up_to_time(self, t, covariates=None, covariates_dropout=None):
         """E[X(t)] = r beta / alpha phi(s - 1, log((beta + t) / beta)), elementwise (host numpy).  With
@@ -749,8 +741,9 @@ def _gg_columns(frequency, monetary_value, allow_zero: bool = False):
     return np.ascontiguousarray(f, dtype=np.int32), np.ascontiguousarray(m)
 
 
-class GgData:
+class GgData(_Handle):
     """Frequency, mean spend and weights resident on the device for a Gamma-Gamma fit (clv_gg_create)."""
+    _DESTROY = "clv_gg_destroy"
 
     def __init__(self, frequency, monetary_value, weights=None, *, device: int = -1):
         self.nn, self.m = _gg_columns(frequency, monetary_value)
@@ -786,23 +779,6 @@ class GgData:
         s = self.customers(params)[:, 1:4]
         return s if self.w is None else s * self.w[:, None]
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.clv_gg_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        self.close()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def device_digamma(x, *, device: int = -1) -> np.ndarray:
     """psi(x) for positive x as the Gamma-Gamma kernel computes it (clv_digamma)."""
@@ -834,6 +810,7 @@ class GammaGammaFitter(_WaldMixin):
     ``penalizer_coef`` adds penalizer_coef * sum(params^2) to the per-customer mean negative
     log-likelihood.  The likelihood and its gradient are HIP kernels (csrc/gg.hip)."""
     _N_LOG = 3
+    _NAMES = GG_PARAM_NAMES
 
     def __init__(self, penalizer_coef: float = 0.0):
         self.penalizer_coef = float(penalizer_coef)
@@ -869,27 +846,11 @@ class GammaGammaFitter(_WaldMixin):
     def fit_objective(self, value_and_grad: Callable, initial_params, tol: float = 1e-7, max_iter: int = 200):
         """The optimiser half of fit() for any ``value_and_grad(log params)``, as
         :meth:`ParetoNBDFitter.fit_objective`."""
-        res = minimize_bfgs(value_and_grad, np.log(np.asarray(initial_params, np.float64).reshape(3)), tol, max_iter)
-        self.params_ = pd.Series(np.exp(res.x), index=list(GG_PARAM_NAMES))
-        self.converged_ = bool(res.converged)
-        self.n_iter_, self.n_eval_ = int(res.n_iter), int(res.n_eval)
-        self.grad_norm_ = float(res.grad_norm)
-        self.message_ = res.message
-        if not res.converged:
-            warnings.warn(f"GammaGammaFitter did not converge: {res.message} "
-                          f"(max |gradient| = {res.grad_norm:.3g} after {res.n_eval} evaluations)", RuntimeWarning,
-                          stacklevel=3)
-        return self
+        return self._fit_objective(value_and_grad, initial_params, tol, max_iter)
 
-    def _fitted(self) -> np.ndarray:
-        if self.params_ is None:
-            raise RuntimeError("fit() has not been called")
-        return self.params_.to_numpy(dtype=np.float64)
-
-    def _uncertainty(self, data: GgData, robust: bool, theta=None, step: float = HESSIAN_STEP):
-        theta = self._theta() if theta is None else theta
-        H = central_hessian(lambda t: data.eval(np.exp(t))[1:4], theta, step)
-        return self._set_uncertainty(H, data.scores(np.exp(theta)) if robust else None, theta)
+    @staticmethod
+    def _gradient(data: GgData):
+        return lambda theta: data.eval(np.exp(theta))[1:4]
 
     def hessian(self, frequency, monetary_value, weights=None, *, theta=None, step: float = HESSIAN_STEP,
                 robust: bool = False) -> np.ndarray:
@@ -977,36 +938,28 @@ def pnbd_weekly_tracking(fitter: ParetoNBDFitter, birth_week, times, *, device: 
     """cum[j] = sum_i E[X(max(times[j] - birth_week[i], 0))]: the "Pareto/NBD (MLE)" curve of the
     reference's Figure 2 (bivariate/analysis_abe.py:434-438), summed on the device.  A covariate fit
     takes the customers' ``covariates`` and sums E[X(t) | z_i] (clv_pnbd_track_cov)."""
-    if fitter._k is not None or covariates is not None or covariates_dropout is not None:
-        return _pnbd_weekly_tracking_cov(fitter, birth_week, times, device, covariates, covariates_dropout)
-    L = _lib.lib()
-    if _lib.device_count() < 1:
-        raise _lib.ClvError("no HIP device visible; the tracking kernel has no CPU fallback")
-    b = np.ascontiguousarray(np.asarray(birth_week, np.float64).reshape(-1))
-    t = np.ascontiguousarray(np.asarray(times, np.float64).reshape(-1))
-    p = _params_array(fitter._fitted())
-    out = np.empty(t.shape[0])
-    check(L.clv_pnbd_track(int(device), b.shape[0], dptr(b), dptr(t), t.shape[0], dptr(p), dptr(out)))
-    return out
-
-
-def _pnbd_weekly_tracking_cov(fitter, birth_week, times, device, covariates, covariates_dropout) -> np.ndarray:
-    if fitter._k is None:
+    cov = fitter._k is not None
+    if not cov and (covariates is not None or covariates_dropout is not None):
         raise ValueError("the model was fitted without covariates")
-    if covariates is None:
+    if cov and covariates is None:
         raise ValueError("the model was fitted with covariates: pass covariates=")
     b = np.ascontiguousarray(np.asarray(birth_week, np.float64).reshape(-1))
     t = np.ascontiguousarray(np.asarray(times, np.float64).reshape(-1))
-    if np.shape(covariates)[0] != b.shape[0]:
-        raise ValueError("covariates must have one row per birth_week entry")
-    z1, z2 = fitter._customer_matrices(covariates, covariates_dropout)
     p = np.ascontiguousarray(fitter._fitted())
+    zs = ()
+    if cov:
+        if np.shape(covariates)[0] != b.shape[0]:
+            raise ValueError("covariates must have one row per birth_week entry")
+        z1, z2 = fitter._customer_matrices(covariates, covariates_dropout)
+        zs = (z1.shape[0], dptr(z1) if z1.size else None, z2.shape[0], dptr(z2) if z2.size else None)
+    else:
+        p = p.reshape(4)
     L = _lib.lib()
     if _lib.device_count() < 1:
         raise _lib.ClvError("no HIP device visible; the tracking kernel has no CPU fallback")
     out = np.empty(t.shape[0])
-    check(L.clv_pnbd_track_cov(int(device), b.shape[0], dptr(b), dptr(t), t.shape[0], dptr(p), z1.shape[0],
-                               dptr(z1) if z1.size else None, z2.shape[0], dptr(z2) if z2.size else None, dptr(out)))
+    track = L.clv_pnbd_track_cov if cov else L.clv_pnbd_track
+    check(track(int(device), b.shape[0], dptr(b), dptr(t), t.shape[0], dptr(p), *zs, dptr(out)))
     return out
 
 

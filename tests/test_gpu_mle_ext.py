@@ -89,6 +89,50 @@ def test_bit_identity_with_the_plain_kernels(abe, n):
             assert bits(sc[6 + z1.shape[1] + k]) == bits(R.device_sum(-z2[:, k] * cc[:, 6])), k
 
 
+def test_replacing_the_covariates_of_a_handle(abe):
+    """clv_pnbd_set_covariates swaps the handle's two covariate matrices and its two reduction buffers for new
+    ones: K1 = K2 = 8, then 1 (23 sums to 9), then 0 on one handle of 257 customers (two blocks, one live lane
+    in the second) give what a fresh handle with the same covariates gives, and the last the plain kernel's sums."""
+    from mcmc_clv_model_amd.mle import PnbdData
+    n = 257
+    x, tx, T, _ = (a[:n] for a in abe)
+    rng = np.random.default_rng(13)
+    Z1, Z2 = rng.uniform(-1.0, 1.0, (n, 8)), rng.uniform(-1.0, 1.0, (n, 8))
+    with PnbdData(x, tx, T) as d:
+        s_plain, _ = d.eval(NEAR_OPT)
+        for k in (8, 1, 0):
+            z1, z2 = Z1[:, :k], Z2[:, :k]
+            p = np.concatenate([NEAR_OPT, np.linspace(-0.15, 0.15, 2 * k)])
+            d.set_covariates(z1.T, z2.T)
+            with PnbdData(x, tx, T, covariates=z1, covariates_dropout=z2) as fresh:
+                want_s, want_u = fresh.eval_cov(p)
+                want_c = fresh.customers_cov(p, 39.0)
+            s, u = d.eval_cov(p)
+            assert s.shape == (6 + 2 * k,) and u == want_u == 0
+            assert np.array_equal(bits(s), bits(want_s)), k
+            assert np.array_equal(bits(d.customers_cov(p, 39.0)), bits(want_c)), k
+        assert np.array_equal(bits(s), bits(s_plain))
+
+
+@pytest.mark.parametrize("n", [1, 257])
+def test_dert_on_a_handle_with_an_empty_covariate_set(abe, n):
+    """clv_pnbd_dert reads K1 = K2 = 0 from a handle that never had covariates and from one given none."""
+    from mcmc_clv_model_amd.mle import PnbdData
+    x, tx, T, _ = (a[:n] for a in abe)
+    delta = math.log1p(0.15) / 52.0
+    with PnbdData(x, tx, T) as d:
+        never = [d.dert(NEAR_OPT, delta, H) for H in (np.inf, 52.0)]
+    with PnbdData(x, tx, T, covariates=np.empty((n, 0))) as d:
+        assert d.k1 == d.k2 == 0
+        empty = [d.dert(NEAR_OPT, delta, H) for H in (np.inf, 52.0)]
+    assert never[0].shape == (n, 2) and np.isfinite(never[0]).all()
+    assert np.array_equal(bits(never), bits(empty))
+
+
+# clv_pnbd_track against clv_pnbd_track_cov with K1 = K2 = 0, bit for bit: the last assertion of
+# test_tracking_with_covariates (700 births in three blocks, 78 times) calls both entries.
+
+
 # ---------------------------------------------------------------------------------------------
 # 2. covariate edge grid against the quadrature
 # ---------------------------------------------------------------------------------------------
