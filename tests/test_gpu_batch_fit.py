@@ -44,18 +44,20 @@ def single(D, cbs, covs, seed, **kw):
     return SINGLE[D](cbs, covs, seed=seed, trace=0, **kw)
 
 
+@pytest.mark.parametrize("D", [2, 3])
 @pytest.mark.parametrize("sink", ["full", "summary"])
-def test_tile_edges(sink):
+def test_tile_edges(sink, D):
     full = with_covariates(cdnow("full"), 1)
-    ns = (1, 255, 256, 257, 513, 1000)
+    # the smallest fit: one customer; trivariate two (omega2 is the variance of log_s: NaN of one row)
+    ns = (1 if D == 2 else 2, 255, 256, 257, 513, 1000)
     fits = [full.iloc[2:2 + n].reset_index(drop=True) for n in ns]  # row 2: x > 0 (a fit of one x = 0 row has lam_init 0)
     seeds = [100 + 7 * j for j in range(len(ns))]
     kw = dict(mcmc=7, burnin=3, thin=3, chains=2, n_mh_steps=20, draw_sink=sink)
-    out, info = mcmc_draw_parameters_many(fits, ["c1"], seeds=seeds, return_info=True, **kw)
+    out, info = MANY[D](fits, ["c1"], seeds=seeds, return_info=True, **kw)
     assert list(info["path"]) == ["batch"] * len(ns) and list(info["blocks"]) == [1, 1, 1, 2, 3, 4]
     assert info.attrs["kernel_ms"] > 0.0
     for j, n in enumerate(ns):
-        assert_same_fit(out[j], single(2, fits[j], ["c1"], seeds[j], **kw), f"N = {n}")
+        assert_same_fit(out[j], single(D, fits[j], ["c1"], seeds[j], **kw), f"N = {n}")
 
 
 @pytest.mark.parametrize("D,K", [(D, K) for D in (2, 3) for K in range(1, 10)])

@@ -9,6 +9,7 @@ import pandas as pd
 import pytest
 
 from oracle import philox as oph
+from tests import summary_ref as SR
 from tests.helpers import GOLDEN, bits, cdnow, golden, replay_case, with_covariates
 
 pytestmark = pytest.mark.gpu
@@ -238,7 +239,8 @@ def test_resume_from_state_is_exact(L):
 
 
 def test_storage_indexing_and_summary_sink(L):
-    """burnin/thin storage (bi:402) and the on-device summary sink == means of the full draws."""
+    """burnin/thin storage (bi:402) and the on-device summary sink == means of the full draws: every
+    stat against tests/summary_ref.py, the exact ones by their bits, the log ones within its bound."""
     df = cdnow("abe", 600)
     kw = dict(mcmc=23, burnin=7, thin=4, chains=2, seed=4242)
     full = _bi(df, **kw)
@@ -246,11 +248,19 @@ def test_storage_indexing_and_summary_sink(L):
     nd = (23 - 1) // 4 + 1
     assert full["level_1"][0].shape == (nd, 600, 4) and full["level_2"][0].shape == (nd, 5)
     assert summ["level_1"] is None and summ["summary"]["n_draws"] == nd
+    sm = summ["summary"]
+    assert sorted(sm) == sorted(["n_draws"] + [nm for nm in SR.SUM_STATS if "eta" not in nm])
     for c in range(2):
         l1 = full["level_1"][c]
-        np.testing.assert_allclose(summ["summary"]["lambda"][c], l1[:, :, 0].mean(0), rtol=1e-12)
-        np.testing.assert_allclose(summ["summary"]["z"][c], l1[:, :, 3].mean(0), rtol=1e-12, atol=1e-15)
-        np.testing.assert_allclose(summ["summary"]["log_mu"][c], np.log(l1[:, :, 1]).mean(0), rtol=1e-12)
+        ref = SR.sums_from_draws(l1) / nd
+        for k, nm in enumerate(SR.SUM_STATS):
+            if nm not in sm:
+                continue
+            if nm in SR.LOG_STATS:  # the division by nd rounds once on either side
+                bound = SR.log_sum_bound(l1[:, :, SR.LOG_COLUMN[nm]]) / nd + SR.U * (np.abs(sm[nm][c]) + np.abs(ref[k]))
+                assert np.all(np.abs(sm[nm][c] - ref[k]) <= bound), (c, nm)
+            else:
+                assert np.array_equal(bits(sm[nm][c]), bits(ref[k])), (c, nm)
         assert np.array_equal(bits(summ["level_2"][c]), bits(full["level_2"][c]))
 
 
