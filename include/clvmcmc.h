@@ -751,6 +751,39 @@ int clv_debug_marginal_loglik(int32_t device, const double* level2, int32_t D, i
                               const double* log_s, double omega2, int32_t nodes, int64_t batch_customers, int32_t grid,
                               double* out, double* out_centre);
 
+/* ---- The log-normal Pareto/NBD by maximum marginal likelihood (csrc/mml.hip) ----
+ * The objective is sum_i w_i l_i with l_i = clv_marginal_loglik's cell of customer i under the one
+ * record (beta [2][K], then Sigma_00, Sigma_01, Sigma_11: D = 2, 2K + 3 doubles), bit for bit, and its
+ * score comes from the customer's posterior moments by Fisher's identity: with (da, db) = (log lambda,
+ * log mu) - m_i and P = Sigma^-1, d l_i / d m_i = P E_i[(da, db)] and d l_i / d Sigma = P (S_i - Sigma) P / 2,
+ * S_i = E_i[(da, db)(da, db)'].  The moments are sums over the nodes of the quadrature that forms l_i:
+ * the score is the derivative of the quadrature value at fixed nodes.
+ * clv_mml_create copies x, t_x, T, weights (NULL: all 1) and cov [K - 1][n] (NULL for K = 1) to the
+ * device, where they stay until clv_mml_destroy.  cov is not checked for finiteness: a customer with a
+ * non-finite covariate has a NaN row.
+ * clv_mml_eval: sums[2K + 6] = sum w l, sum w, the customers whose l is not finite (also
+ * *n_nonfinite, which may be NULL), sum w S_i (00, 01, 11), sum w d_ik E_i[da] for k < K, then sum w d_ik
+ * E_i[db] for k < K (d_i0 = 1), in the fixed order of clv_pnbd_eval (zero-padded 256-customer blocks
+ * by the 256-tree, the block partials by the final kernel): the same bits on every call and grid.  A
+ * non-finite customer makes the sums NaN; none is dropped.
+ * clv_mml_customers: out[n][8] = l_i, P(alive | data, record), E_i[da], E_i[db], E_i[da da], E_i[da db],
+ * E_i[db db] and E[X*(t_star) | data, record], the expected purchases in (T, T + t_star].
+ * clv_debug_mml_eval: clv_mml_eval with the most workgroups overridden (grid > 0), the tests' knob.
+ * clv_mml_info: out[0] customers and out[1] lanes per workgroup; VGPRs and scratch bytes per lane of
+ * the eval kernel (out[2], out[3]) and of the customers kernel (out[4], out[5]); out[6] the device time in
+ * ns of the eval kernel of the calling thread's last clv_mml_eval (-1 before one).
+ * CLV_EINVAL: a null handle or pointer, K not 1 .. 9, cov not matching K, x < 0, t_x outside [0, T], a
+ * negative or non-finite weight, nodes not 0, 8, 16, 24 or 32, t_star negative or not finite. */
+typedef struct clv_mml clv_mml;
+int clv_mml_create(int32_t device, int64_t n, const int32_t* x, const double* t_x, const double* T,
+                   const double* weights, int32_t K, const double* cov, clv_mml** out);
+void clv_mml_destroy(clv_mml* h);
+int clv_mml_eval(clv_mml* h, const double* record, int32_t nodes, double* sums, int64_t* n_nonfinite);
+int clv_mml_customers(clv_mml* h, const double* record, int32_t nodes, double t_star, double* out);
+int clv_debug_mml_eval(clv_mml* h, const double* record, int32_t nodes, int32_t grid, double* sums,
+                       int64_t* n_nonfinite);
+int clv_mml_info(int64_t* out);
+
 /* ---- Convergence diagnostics on device (csrc/diag.hip) ----
  * The reference checks convergence with ArviZ on its level-2 draws (bivariate/analysis_abe.py:
  * 651-706: az.summary, az.plot_autocorr).  Here a series is m chains x n draws (n >= 8) of one

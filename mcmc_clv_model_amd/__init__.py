@@ -44,6 +44,9 @@ model), standard errors, a Wald summary and likelihood-ratio tests of a fit (sta
 likelihood_ratio_test), the Gamma-Gamma spend model (GammaGammaFitter), DERT and the classical CLV
 that stands beside lifetime_value (ParetoNBDFitter.discounted_expected_transactions,
 classical_lifetime_value).
+The log-normal Pareto/NBD fitted by maximum marginal likelihood: the HB models'
+heterogeneity with the classical estimation principle (LogNormalParetoNBDFitter), its score from the
+posterior moments of the marginal-likelihood quadrature by Fisher's identity.
 
 The per-sweep work runs in hand-written HIP kernels for gfx950 (csrc/), bound through the C
 ABI in include/clvmcmc.h.  There is no CPU fallback.
@@ -59,8 +62,8 @@ from .analysis import (chain_total_loglik, compare_forecasts, compare_models, co
                        marginal_information_criteria, marginal_log_likelihood, marginal_log_score)
 from .batch import kfold_cross_validation, mcmc_draw_parameters_many, mcmc_draw_parameters_rfm_m_many
 from .bivariate import mcmc_draw_parameters
-from .mle import (GammaGammaFitter, ParetoNBDFitter, classical_lifetime_value, likelihood_ratio_test, mape_aggregate,
-                  pnbd_weekly_tracking)
+from .mle import (GammaGammaFitter, LogNormalParetoNBDFitter, ParetoNBDFitter, classical_lifetime_value,
+                  likelihood_ratio_test, mape_aggregate, pnbd_weekly_tracking)
 from .trivariate import mcmc_draw_parameters_rfm_m
 
 __all__ = ["mcmc_draw_parameters", "mcmc_draw_parameters_rfm_m", "draw_future_transactions",
@@ -74,5 +77,5 @@ __all__ = ["mcmc_draw_parameters", "mcmc_draw_parameters_rfm_m", "draw_future_tr
            "forecast_table", "posterior_predictive_check", "ppc_pit", "marginal_log_likelihood",
            "marginal_information_criteria", "marginal_log_score", "mcmc_draw_parameters_many",
            "mcmc_draw_parameters_rfm_m_many", "kfold_cross_validation", "GammaGammaFitter",
-           "classical_lifetime_value", "likelihood_ratio_test"]
+           "classical_lifetime_value", "likelihood_ratio_test", "LogNormalParetoNBDFitter"]
 __version__ = "0.1.0"

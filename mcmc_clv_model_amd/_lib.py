@@ -199,6 +199,12 @@ def lib() -> ctypes.CDLL:
         "clv_marginal_info": (c_int32, [POINTER(c_int64)]),
         "clv_debug_marginal_loglik": (c_int32, [c_int32, dp, c_int32, c_int32, dp, c_int64, c_int64, POINTER(c_int32),
                                                 dp, dp, dp, c_double, c_int32, c_int64, c_int32, dp, dp]),
+        "clv_mml_create": (c_int32, [c_int32, c_int64, POINTER(c_int32), dp, dp, dp, c_int32, dp, POINTER(sp)]),
+        "clv_mml_destroy": (None, [sp]),
+        "clv_mml_eval": (c_int32, [sp, dp, c_int32, dp, POINTER(c_int64)]),
+        "clv_mml_customers": (c_int32, [sp, dp, c_int32, c_double, dp]),
+        "clv_debug_mml_eval": (c_int32, [sp, dp, c_int32, c_int32, dp, POINTER(c_int64)]),
+        "clv_mml_info": (c_int32, [POINTER(c_int64)]),
         "clv_diagnostics": (c_int32, [c_int32, dp, c_int32, c_int64, c_int64, c_int32, c_uint32, dp]),
         "clv_diagnostics_sampler": (c_int32, [sp, c_uint32, dp, dp]),
         "clv_autocorr": (c_int32, [c_int32, dp, c_int32, c_int64, c_int64, c_int32, dp]),
@@ -363,6 +369,21 @@ def marginal_info() -> dict:
     return dict(orders=tuple(int(v) for v in out[0:4]), default_nodes=int(out[4]), newton=int(out[5]),
                 block=int(out[6]), max_records=int(out[7]), vgprs=int(out[8]), scratch_bytes=int(out[9]),
                 kernel_ns=int(out[10]))
+
+
+# Columns of clv_mml_customers() (include/clvmcmc.h): (da, db) = (log lambda, log mu) - m_i.
+MML_ROW = ("loglik", "p_alive", "e_da", "e_db", "e_dada", "e_dadb", "e_dbdb", "xstar")
+
+
+def mml_info() -> dict:
+    """clv_mml_info: customers and lanes per workgroup of csrc/mml.hip, and VGPRs and scratch bytes per
+    lane of its eval kernel and of its customers kernel, and the device time in ns of the eval kernel
+    of this thread's last clv_mml_eval (-1 before one)."""
+    out = (c_int64 * 7)()
+    check(lib().clv_mml_info(out))
+    keys = ("customers", "block", "eval_vgprs", "eval_scratch_bytes", "customers_vgprs", "customers_scratch_bytes",
+            "eval_kernel_ns")
+    return {k: int(v) for k, v in zip(keys, out)}
 
 
 # Many fits in one launch (csrc/batch.hip): the most 256-customer tiles of a fit the batch kernel takes

@@ -112,6 +112,95 @@ def minimize_bfgs(value_and_grad: Callable, theta0, tol: float = 1e-7, max_iter:
     return res
 
 
+def minimize_bfgs_score(value_and_grad: Callable, theta0, tol: float = 1e-7, max_iter: int = 200, *,
+                        curvature: float = 0.9, value_slack: float = 1e-3, max_line_steps: int = 30):
+    """BFGS whose line search is decided by the score, for an objective whose gradient is not exactly
+    the derivative of its value (the fixed-node score of a quadrature): along the
+    direction p a step t is accepted when the directional derivative has shrunk,
+    |g(theta + t p)' p| <= curvature |g(theta)' p| (the strong Wolfe curvature condition, which also makes
+    the BFGS update positive definite); a positive derivative brackets the root and the next trial
+    is the secant root of the derivative, a still steep negative one doubles the step.  The value is
+    a sanity bound only: a trial that is not finite or whose value exceeds f + value_slack max(1, |f|)
+    is too far and the step is halved towards the last good one.  Stops when max |g| <= tol: the
+    result is the root of the score.  Same namespace as :func:`minimize_bfgs`."""
+    theta = np.array(theta0, np.float64)
+    d = theta.size
+    n_eval = 0
+
+    def ev(t):
+        nonlocal n_eval
+        n_eval += 1
+        f, g = value_and_grad(t)
+        g = np.asarray(g, np.float64)
+        return float(f), g, bool(np.isfinite(f) and np.isfinite(g).all())
+
+    f, g, ok = ev(theta)
+    res = SimpleNamespace(x=theta, fun=f, grad=g, grad_norm=float(np.max(np.abs(g))) if ok else np.inf,
+                          converged=False, n_iter=0, n_eval=n_eval, message="")
+    if not ok:
+        res.message = "the objective is not finite at the starting point"
+        return res
+    H = np.eye(d)
+    fresh = True
+    for it in range(1, max_iter + 1):
+        if np.max(np.abs(g)) <= tol:
+            res.converged, res.message = True, "score tolerance met"
+            break
+        p = -H @ g
+        slope = float(g @ p)
+        if not slope < 0.0:
+            H, fresh = np.eye(d), True
+            p, slope = -g, -float(g @ g)
+        t = min(1.0, 1.0 / np.max(np.abs(p))) if fresh else 1.0
+        lo, dlo, hi, dhi = 0.0, slope, None, None     # the derivative along p is negative at lo
+        found = False
+        for _ in range(max_line_steps):
+            tn = theta + t * p
+            fn, gn, okn = ev(tn)
+            if not okn or fn > f + value_slack * max(1.0, abs(f)):
+                hi, dhi = t, None
+            else:
+                dn = float(gn @ p)
+                if abs(dn) <= curvature * abs(slope):
+                    found = True
+                    break
+                if dn > 0.0:
+                    hi, dhi = t, dn
+                else:
+                    lo, dlo = t, dn
+            if hi is None:
+                t = 2.0 * t
+            elif dhi is None:
+                t = 0.5 * (lo + hi)
+            else:
+                t = lo + (hi - lo) * (-dlo) / (dhi - dlo)
+                t = min(max(t, lo + 0.1 * (hi - lo)), hi - 0.1 * (hi - lo))
+        res.n_iter = it
+        if not found:
+            if fresh:
+                res.message = "line search failed along the steepest descent direction"
+                break
+            H, fresh = np.eye(d), True
+            continue
+        s, y = tn - theta, gn - g
+        sy = float(s @ y)
+        if sy > 1e-10 * np.sqrt(float(s @ s) * float(y @ y)):
+            if fresh:
+                H = np.eye(d) * (sy / float(y @ y))
+            rho = 1.0 / sy
+            V = np.eye(d) - rho * np.outer(s, y)
+            H = V @ H @ V.T + rho * np.outer(s, s)
+            fresh = False
+        theta, f, g = tn, fn, gn
+    else:
+        if np.max(np.abs(g)) <= tol:
+            res.converged, res.message = True, "score tolerance met"
+        else:
+            res.message = f"max_iter = {max_iter} iterations without meeting tol"
+    res.x, res.fun, res.grad, res.grad_norm, res.n_eval = theta, f, g, float(np.max(np.abs(g))), n_eval
+    return res
+
+
 # ---------------------------------------------------------------------------------------------
 # Uncertainty of a fit: Hessian by central differences of the gradient, Wald summary, tests
 # ---------------------------------------------------------------------------------------------
@@ -969,3 +1058,344 @@ def mape_aggregate(actual, pred) -> float:
     a = np.cumsum(np.asarray(actual, np.float64))
     p = np.cumsum(np.asarray(pred, np.float64))
     return float(np.mean(np.abs(p - a)) / a[-1] * 100.0)
+
+
+# ---------------------------------------------------------------------------------------------
+# The log-normal Pareto/NBD by maximum marginal likelihood
+# ---------------------------------------------------------------------------------------------
+def log_cholesky_sigma(c) -> np.ndarray:
+    """(Sigma_00, Sigma_01, Sigma_11) of c = (c0, c1, c2): Sigma = C C', C = [[e^c0, 0], [c1, e^c2]]."""
+    c = np.asarray(c, np.float64)
+    e0, e2 = np.exp(c[0]), np.exp(c[2])
+    return np.array([e0 * e0, e0 * c[1], c[1] * c[1] + e2 * e2])
+
+
+def sigma_log_cholesky(sigma) -> np.ndarray:
+    """(c0, c1, c2) of a positive definite (Sigma_00, Sigma_01, Sigma_11) (ValueError otherwise)."""
+    s00, s01, s11 = (float(v) for v in np.asarray(sigma, np.float64).reshape(3))
+    if not (np.isfinite([s00, s01, s11]).all() and s00 > 0.0 and s00 * s11 - s01 * s01 > 0.0):
+        raise ValueError("Sigma must be finite and positive definite")
+    e0 = np.sqrt(s00)
+    c1 = s01 / e0
+    return np.array([np.log(e0), c1, 0.5 * np.log(s11 - c1 * c1)])
+
+
+def mml_record(theta, K: int) -> np.ndarray:
+    """The level-2 record (beta [2][K], then Sigma_00, Sigma_01, Sigma_11) of theta = (beta, c0, c1, c2)."""
+    theta = np.asarray(theta, np.float64).reshape(2 * K + 3)
+    return np.ascontiguousarray(np.concatenate([theta[:2 * K], log_cholesky_sigma(theta[2 * K:])]))
+
+
+def mml_score(theta, K: int, sda, sdb, S, W) -> np.ndarray:
+    """[2K + 3, ...]: the score of theta from moments by Fisher's identity and the chain rule.  ``sda``,
+    ``sdb`` [K, ...] are (sums of w) d_k E[da] and d_k E[db], ``S`` [3, ...] of E[da da], E[da db], E[db db],
+    ``W`` [...] the weight: the sums of clv_mml_eval, or per customer the rows of clv_mml_customers.
+    d / d m = P E[(da, db)] and G = d / d Sigma = P (S - W Sigma) P / 2 with P = Sigma^-1; through
+    Sigma = C C', d / d C = 2 G C, and the diagonal of C is e^c0, e^c2."""
+    theta = np.asarray(theta, np.float64).reshape(2 * K + 3)
+    c = theta[2 * K:]
+    s00, s01, s11 = log_cholesky_sigma(c)
+    det = s00 * s11 - s01 * s01
+    P00, P01, P11 = s11 / det, -s01 / det, s00 / det
+    sda, sdb, S, W = (np.asarray(v, np.float64) for v in (sda, sdb, S, W))
+    R00, R01, R11 = S[0] - W * s00, S[1] - W * s01, S[2] - W * s11
+    A00, A01 = P00 * R00 + P01 * R01, P00 * R01 + P01 * R11       # P R
+    A10, A11 = P01 * R00 + P11 * R01, P01 * R01 + P11 * R11
+    G00 = 0.5 * (A00 * P00 + A01 * P01)
+    G01 = 0.5 * (A00 * P01 + A01 * P11)
+    G11 = 0.5 * (A10 * P01 + A11 * P11)
+    a, b = np.exp(c[0]), np.exp(c[2])
+    out = np.empty((2 * K + 3,) + W.shape)
+    out[:K] = P00 * sda + P01 * sdb
+    out[K:2 * K] = P01 * sda + P11 * sdb
+    out[2 * K] = 2.0 * (G00 * a + G01 * c[1]) * a
+    out[2 * K + 1] = 2.0 * (G01 * a + G11 * c[1])
+    out[2 * K + 2] = 2.0 * G11 * b * b
+    return out
+
+
+def mml_params(theta, K: int):
+    """(params [2K + 4], J [2K + 4][2K + 3]): beta, Sigma_00, Sigma_01, Sigma_11 and the correlation
+    rho = Sigma_01 / sqrt(Sigma_00 Sigma_11) of theta, and their Jacobian (the delta method's)."""
+    theta = np.asarray(theta, np.float64).reshape(2 * K + 3)
+    c0, c1, c2 = theta[2 * K:]
+    e0, e2 = np.exp(c0), np.exp(c2)
+    s00, s01, s11 = log_cholesky_sigma(theta[2 * K:])
+    J = np.zeros((2 * K + 4, 2 * K + 3))
+    J[:2 * K, :2 * K] = np.eye(2 * K)
+    J[2 * K, 2 * K] = 2.0 * s00
+    J[2 * K + 1, 2 * K:2 * K + 2] = [s01, e0]
+    J[2 * K + 2, 2 * K + 1:] = [2.0 * c1, 2.0 * e2 * e2]
+    J[2 * K + 3, 2 * K + 1:] = [e2 * e2 / s11 ** 1.5, -c1 * e2 * e2 / s11 ** 1.5]
+    return np.concatenate([theta[:2 * K], [s00, s01, s11, c1 / np.sqrt(s11)]]), J
+
+
+class MmlData(_Handle):
+    """x, t_x, T, weights and the covariate rows resident on the device for the evaluations of a
+    maximum-marginal-likelihood fit (clv_mml_create).  ``covariates``: (N, K - 1) or None."""
+    _DESTROY = "clv_mml_destroy"
+
+    def __init__(self, frequency, recency, T, weights=None, covariates=None, *, device: int = -1, check_finite=True):
+        f = np.asarray(frequency)
+        ff = np.asarray(f, np.float64)
+        if f.size and not np.all(ff == np.round(ff)):
+            raise ValueError("frequency must hold integer repeat counts")
+        if f.size and (ff.max() > 2 ** 31 - 1 or ff.min() < -2 ** 31):
+            raise ValueError("frequency exceeds int32")
+        self.x = np.ascontiguousarray(f, dtype=np.int32).reshape(-1)
+        self.t_x = np.ascontiguousarray(np.asarray(recency, np.float64).reshape(-1))
+        self.T = np.ascontiguousarray(np.asarray(T, np.float64).reshape(-1))
+        self.n = int(self.x.shape[0])
+        if self.t_x.shape[0] != self.n or self.T.shape[0] != self.n:
+            raise ValueError("frequency, recency and T must have the same length")
+        self.w = None
+        if weights is not None:
+            self.w = np.ascontiguousarray(np.asarray(weights, np.float64).reshape(-1))
+            if self.w.shape[0] != self.n:
+                raise ValueError("weights must have the length of frequency")
+        self.cov = None
+        if covariates is not None:
+            if check_finite:
+                self.cov = covariate_matrix(covariates, self.n)[0]
+            else:
+                self.cov = np.ascontiguousarray(np.asarray(covariates, np.float64).reshape(self.n, -1).T)
+            if self.cov.shape[0] == 0:
+                self.cov = None
+        self.K = 1 if self.cov is None else 1 + int(self.cov.shape[0])
+        L = _lib.lib()
+        if _lib.device_count() < 1:
+            raise _lib.ClvError("no HIP device visible; the marginal likelihood has no CPU fallback")
+        self._L = L
+        self._h = ctypes.c_void_p()
+        check(L.clv_mml_create(int(device), self.n, self.x.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                               dptr(self.t_x), dptr(self.T), dptr(self.w), self.K, dptr(self.cov), ctypes.byref(self._h)))
+
+    def design(self) -> np.ndarray:
+        """d [K][n]: the intercept row, then the covariate rows."""
+        one = np.ones((1, self.n))
+        return one if self.cov is None else np.concatenate([one, self.cov])
+
+    def eval(self, record, nodes: int = 0, grid: Optional[int] = None):
+        """(sums [2K + 6], n_nonfinite) of clv_mml_eval (``grid`` given: clv_debug_mml_eval)."""
+        r = np.ascontiguousarray(np.asarray(record, np.float64).reshape(2 * self.K + 3))
+        sums = np.empty(2 * self.K + 6)
+        nn = ctypes.c_int64(0)
+        if grid is None:
+            check(self._L.clv_mml_eval(self._h, dptr(r), int(nodes), dptr(sums), ctypes.byref(nn)))
+        else:
+            check(self._L.clv_debug_mml_eval(self._h, dptr(r), int(nodes), int(grid), dptr(sums), ctypes.byref(nn)))
+        return sums, int(nn.value)
+
+    def customers(self, record, nodes: int = 0, t_star: float = 0.0) -> np.ndarray:
+        """[n][8] of clv_mml_customers: the columns _lib.MML_ROW."""
+        r = np.ascontiguousarray(np.asarray(record, np.float64).reshape(2 * self.K + 3))
+        out = np.empty((self.n, len(_lib.MML_ROW)))
+        check(self._L.clv_mml_customers(self._h, dptr(r), int(nodes), float(t_star), dptr(out)))
+        return out
+
+    def value_and_score(self, theta, nodes: int = 0):
+        """(sum w l, its score in theta, n_nonfinite) at theta = (beta, c0, c1, c2)."""
+        K = self.K
+        sums, nn = self.eval(mml_record(theta, K), nodes)
+        return sums[0], mml_score(theta, K, sums[6:6 + K], sums[6 + K:6 + 2 * K], sums[3:6], sums[1]), nn
+
+    def scores(self, theta, nodes: int = 0) -> np.ndarray:
+        """[n][2K + 3]: w_i d l_i / d theta from the rows of :meth:`customers`."""
+        rows = self.customers(mml_record(theta, self.K), nodes)
+        d = self.design()
+        s = mml_score(theta, self.K, d * rows[:, 2], d * rows[:, 3], rows[:, 4:7].T, np.ones(self.n)).T
+        return s if self.w is None else s * self.w[:, None]
+
+
+class LogNormalParetoNBDFitter(_WaldMixin):
+    """The Pareto/NBD with Abe (2009)'s log-normal heterogeneity, (log lambda_i, log mu_i) ~ N2(B' d_i, Sigma),
+    fitted the classical way: (B, Sigma) maximise the marginal likelihood, the customers' own
+    (lambda_i, mu_i) integrated out by the adaptive Gauss-Hermite rule of ``marginal_log_likelihood``
+    (csrc/mml.hip).  The score comes from the posterior moments by Fisher's identity, at the
+    quadrature's fixed nodes, and the estimate is the root of that score (:func:`minimize_bfgs_score`);
+    ``log_likelihood_`` is the quadrature value there.  DESIGN.md §4n.
+
+    theta = (beta in ``level_2`` order, c0, c1, c2) with Sigma = C C', C = [[e^c0, 0], [c1, e^c2]].
+    ``params_`` holds beta (``purchase:intercept``, ``purchase:<covariate>`` ..., ``dropout:...``),
+    Sigma_00, Sigma_01, Sigma_11 and rho; ``theta_`` the optimiser's parameters, on which ``covariance_``
+    and ``hessian_`` stand; ``params_covariance_``, ``standard_errors_`` and ``summary_`` are the delta
+    method's on ``params_``."""
+    _N_LOG = 0
+    SIGMA_NAMES = ("Sigma_00", "Sigma_01", "Sigma_11", "rho")
+
+    def __init__(self):
+        self.params_: Optional[pd.Series] = None
+        self.theta_ = None
+        self._device = -1
+        self._K = 1
+        self._nodes = 0
+        self._names = []
+
+    @staticmethod
+    def _beta_names(names):
+        cols = ["intercept"] + list(names)
+        return [f"purchase:{c}" for c in cols] + [f"dropout:{c}" for c in cols]
+
+    def _theta_names(self):
+        return self._beta_names(self._names) + ["c0", "c1", "c2"]
+
+    def _theta(self):
+        return np.array(self.theta_, np.float64)
+
+    def _require(self):
+        if self.theta_ is None:
+            raise RuntimeError("fit() has not been called")
+
+    @staticmethod
+    def default_start(K: int, frequency, recency, T) -> np.ndarray:
+        """theta of the default start: the sampler's initial intercepts (log of mean x over the mean
+        of t_x, T where t_x = 0; log of the mean of 1 / (t_x + 1 / (2 lambda))), no covariate effect, Sigma = I."""
+        x, t_x, T = (np.asarray(v, np.float64).reshape(-1) for v in (frequency, recency, T))
+        lam = x.mean() / np.mean(np.where(t_x == 0, T, t_x))
+        theta = np.zeros(2 * K + 3)
+        theta[0] = np.log(lam)
+        theta[K] = np.log(np.mean(1.0 / (t_x + 0.5 / lam)))
+        return theta
+
+    def _adopt(self, theta):
+        self.theta_ = np.array(theta, np.float64)
+        p, _ = mml_params(self.theta_, self._K)
+        self.params_ = pd.Series(p, index=self._beta_names(self._names) + list(self.SIGMA_NAMES))
+
+    def fit(self, frequency, recency, T, weights=None, covariates=None, initial_params=None, tol: float = 1e-7,
+            max_iter: int = 200, *, device: int = -1, covariate_names=None, standard_errors: bool = False,
+            robust: bool = False, nodes: int = 32):
+        """``covariates`` (N, K - 1) array or DataFrame (at most 8 columns); ``initial_params`` a level-2
+        record (beta [2][K], Sigma_00, Sigma_01, Sigma_11).  ``tol`` bounds max |d sum w l / d theta|.
+        ``standard_errors=True`` adds 2 P score evaluations (``robust=True``: the sandwich)."""
+        from .analysis import marginal_nodes
+        q = marginal_nodes(nodes)
+        n = int(np.asarray(frequency).reshape(-1).shape[0])
+        names = []
+        if covariates is not None:
+            names = covariate_matrix(covariates, n, "covariates", covariate_names)[1]
+        K = 1 + len(names)
+        if initial_params is None:
+            theta0 = self.default_start(K, frequency, recency, T)
+        else:
+            r0 = np.asarray(initial_params, np.float64).reshape(-1)
+            if r0.size != 2 * K + 3 or not np.isfinite(r0).all():
+                raise ValueError(f"initial_params must be a level-2 record of {2 * K + 3} finite numbers")
+            theta0 = np.concatenate([r0[:2 * K], sigma_log_cholesky(r0[2 * K:])])
+        with MmlData(frequency, recency, T, weights, covariates if K > 1 else None, device=device) as data:
+            def objective(theta):
+                with np.errstate(over="ignore", invalid="ignore"):
+                    v, g, nn = data.value_and_score(theta, q)
+                if nn:
+                    return np.nan, np.full(theta.size, np.nan)
+                return -v, -g
+            res = minimize_bfgs_score(objective, theta0, tol, max_iter)
+            self._K, self._names, self._nodes, self._device = K, list(names), q, int(device)
+            self._adopt(res.x)
+            self.converged_ = bool(res.converged)
+            self.n_iter_, self.n_eval_ = int(res.n_iter), int(res.n_eval)
+            self.grad_norm_ = float(res.grad_norm)
+            self.message_ = res.message
+            if not res.converged:
+                warnings.warn(f"{type(self).__name__} did not converge: {res.message} "
+                              f"(max |score| = {res.grad_norm:.3g} after {res.n_eval} evaluations)", RuntimeWarning,
+                              stacklevel=2)
+            sums, nn = data.eval(mml_record(self.theta_, K), q)
+            if standard_errors:
+                self._uncertainty(data, robust)
+        self.log_likelihood_ = float(sums[0])
+        self.n_nonfinite_ = nn
+        return self
+
+    def _uncertainty(self, data, robust: bool, theta=None, step: float = HESSIAN_STEP):
+        theta = self._theta() if theta is None else theta
+        H = central_hessian(lambda t: data.value_and_score(t, self._nodes)[1], theta, step)
+        return self._set_uncertainty(H, data.scores(theta, self._nodes) if robust else None, theta)
+
+    def _set_uncertainty(self, H, scores=None, theta=None):
+        theta = self._theta() if theta is None else np.asarray(theta, np.float64)
+        keep, self.params_ = self.params_, pd.Series(theta, index=self._theta_names())
+        try:
+            super()._set_uncertainty(H, scores, theta)     # hessian_, covariance_ and the summary on theta
+        finally:
+            self.params_ = keep
+        self.theta_summary_ = self.summary_
+        p, J = mml_params(theta, self._K)
+        pc = J @ self.covariance_.to_numpy() @ J.T
+        names = list(self.params_.index)
+        self.params_covariance_ = pd.DataFrame(pc, index=names, columns=names)
+        self.standard_errors_ = pd.Series(delta_standard_errors(p, pc, 0), index=names)
+        self.summary_ = wald_summary(p, pc, names, 0)
+        return self
+
+    def _data(self, frequency, recency, T, weights, covariates) -> MmlData:
+        self._require()
+        if self._K == 1 and covariates is not None:
+            raise ValueError("the model was fitted without covariates")
+        if self._K > 1:
+            if covariates is None:
+                raise ValueError("the model was fitted with covariates: pass covariates=")
+            if np.ndim(covariates) == 2 and np.shape(covariates)[1] != self._K - 1:
+                raise ValueError(f"the model was fitted with {self._K - 1} covariates")
+        return MmlData(frequency, recency, T, weights, covariates, device=self._device)
+
+    def _rows(self, t, frequency, recency, T, covariates) -> np.ndarray:
+        with self._data(frequency, recency, T, None, covariates) as data:
+            return data.customers(mml_record(self.theta_, self._K), self._nodes, float(t))
+
+    def hessian(self, frequency, recency, T, weights=None, *, covariates=None, step: float = HESSIAN_STEP,
+                robust: bool = False) -> np.ndarray:
+        """The Jacobian of the score in theta by central differences (2 P evaluations, symmetrised) at
+        the fitted theta; sets covariance_, standard_errors_ and summary_ from it."""
+        with self._data(frequency, recency, T, weights, covariates) as data:
+            self._uncertainty(data, robust, None, step)
+        return self.hessian_.copy()
+
+    def scores(self, frequency, recency, T, weights=None, *, covariates=None) -> np.ndarray:
+        """[N][2K + 3]: w_i d l_i / d theta at the fitted theta: the rows of the sandwich covariance."""
+        with self._data(frequency, recency, T, weights, covariates) as data:
+            return data.scores(self.theta_, self._nodes)
+
+    def pointwise_log_likelihood(self, frequency, recency, T, *, covariates=None) -> np.ndarray:
+        """l_i per customer at the fitted (beta, Sigma): the bits of ``marginal_log_likelihood`` of
+        :meth:`as_level2_record`."""
+        return self._rows(0.0, frequency, recency, T, covariates)[:, 0].copy()
+
+    def conditional_probability_alive(self, frequency, recency, T, *, covariates=None) -> np.ndarray:
+        """The empirical-Bayes P(alive at T | x, t_x, T, theta-hat)."""
+        return self._rows(0.0, frequency, recency, T, covariates)[:, 1].copy()
+
+    def conditional_expected_number_of_purchases_up_to_time(self, t, frequency, recency, T, *,
+                                                            covariates=None) -> np.ndarray:
+        """E[X*(t) | x, t_x, T, theta-hat]: the expected purchases in (T, T + t] (t a scalar)."""
+        return self._rows(float(t), frequency, recency, T, covariates)[:, 7].copy()
+
+    def posterior_means(self, frequency, recency, T, *, covariates=None) -> pd.DataFrame:
+        """Per customer the empirical-Bayes posterior mean and sd of log lambda_i and log mu_i, their
+        correlation and P(alive)."""
+        with self._data(frequency, recency, T, None, covariates) as data:
+            rows = data.customers(mml_record(self.theta_, self._K), self._nodes, 0.0)
+            d = data.design()
+        K = self._K
+        m0, m1 = self.theta_[:K] @ d, self.theta_[K:2 * K] @ d
+        va = np.maximum(rows[:, 4] - rows[:, 2] ** 2, 0.0)
+        vb = np.maximum(rows[:, 6] - rows[:, 3] ** 2, 0.0)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            corr = (rows[:, 5] - rows[:, 2] * rows[:, 3]) / np.sqrt(va * vb)
+        return pd.DataFrame(dict(log_lambda_mean=m0 + rows[:, 2], log_lambda_sd=np.sqrt(va), log_mu_mean=m1 + rows[:, 3],
+                                 log_mu_sd=np.sqrt(vb), corr=corr, p_alive=rows[:, 1]))
+
+    def information_criteria(self, frequency, recency, T, *, covariates=None) -> dict:
+        """The fitted model as an entry of ``analysis.compare_models`` beside ``marginal_information_criteria``
+        and ``ParetoNBDFitter.information_criteria``: in-sample, penalised by its 2K + 3 parameters
+        (:func:`mle_information_criteria`), ``"kind": "marginal"``."""
+        ll = self.pointwise_log_likelihood(frequency, recency, T, covariates=covariates)
+        out = mle_information_criteria(ll, n_params=2 * self._K + 3)
+        out["n_params"] = 2 * self._K + 3
+        return out
+
+    def as_level2_record(self) -> np.ndarray:
+        """theta-hat in the ``level_2`` layout, [1 chain][1 draw][2K + 3]: what ``marginal_log_likelihood``,
+        ``marginal_log_score`` and ``score_customers`` take as ``draws``."""
+        self._require()
+        return mml_record(self.theta_, self._K).reshape(1, 1, -1)
