@@ -370,6 +370,17 @@ int clv_debug_split_layout(int32_t n_chains, int32_t nb, int32_t* out);
 int clv_debug_split_relay_plan(int32_t S, int32_t R, int32_t* out);
 int clv_debug_split_draw_plan(int32_t R, int32_t share, int32_t* out);
 int clv_debug_split_stamps(clv_sampler* s, uint64_t* out);
+/* Host only: the sweep path clv_create decides on (the same function, no device and no environment),
+ * from numbers.  in[20] = D, K, n_mh_steps, n_chains, local blocks, blocks_per_unit, n_units_global,
+ * world_size, replay (0 / 1); the device's CUs (0: a query failed); workgroups per CU and scratch
+ * bytes per lane of the block instance (the peer instance at world size > 1), of the split layout's
+ * helper instance and of its relay instance (scratch -1: the query failed, -2: not queried yet);
+ * CLV_PERSISTENT (-1 unset, 0, 1), CLV_PERSIST_LAYOUT (0 unset, 1 block, 2 split, -1 anything else),
+ * CLV_SPLIT_RELAY (-1 unset, 0, 1, 2 anything else), CLV_DEFER (0: "0", else 1).
+ * out[8] = persistent, split, relay_steps, p2p_capable, p2p_persist_fits, fx_capable, defer, and the
+ * instances whose resources the decision still waits for (1 helper | 2 relay; their fields stay 0).
+ * CLV_EINVAL with clv_create's message where clv_create rejects a knob. */
+int clv_debug_sweep_plan(const int64_t* in, int32_t* out);
 
 /* ---- In-process multi-device runs (SURVEY.md §8b devices=, §8e) ----
  * A group drives the n shards of one problem from one host thread: shards[r] = the sampler of rank

@@ -21,7 +21,8 @@ namespace {
 
 thread_local std::string g_err;
 
-constexpr int PRIOR_DOUBLES = 81 + 81 + 27 + 9;  // V, cholV, A0B0, S0B
+// The prior as the device holds it: V, cholV (9 x 9 each), A0B0 (9 x 3), S0B (3 x 3)
+constexpr int PRIOR_V = 0, PRIOR_CHOLV = 81, PRIOR_A0B0 = 162, PRIOR_S0B = 189, PRIOR_DOUBLES = 198;
 constexpr int GRAPH_CHUNK = 64;                  // sweeps per captured graph
 constexpr int TIMING_EVENTS = 256;               // sweep launches timed per harvest
 
@@ -36,14 +37,25 @@ namespace {
 
 HyperArgs hyper_args(clv_sampler* s, const double* units, int mode);
 
+Rng rng_args(const clv_sampler* s) {  // (seed, chain_first, tape, tape_sweep_stride, tape_sweeps)
+  return Rng{s->cfg.seed, s->cfg.chain_first, s->d_tape, clv_replay_sweep_stride(s), s->tape_sweeps};
+}
+
+std::vector<double> pack_prior(const clv_prior* prior, int D, int K) {
+  std::vector<double> pr(PRIOR_DOUBLES, 0.0);
+  for (int i = 0; i < K * K; ++i) {
+    pr[PRIOR_V + i] = prior->V[i];
+    pr[PRIOR_CHOLV + i] = prior->chol_V[i];
+  }
+  for (int i = 0; i < K * D; ++i) pr[PRIOR_A0B0 + i] = prior->A0B0[i];
+  for (int i = 0; i < D * D; ++i) pr[PRIOR_S0B + i] = prior->S0_B0A0B0[i];
+  return pr;
+}
+
 SweepArgs sweep_args(clv_sampler* s, int init, int fuse = 0) {
   SweepArgs a{};
   a.g = s->g;
-  a.r.seed = s->cfg.seed;
-  a.r.chain_first = s->cfg.chain_first;
-  a.r.tape = s->d_tape;
-  a.r.tape_sweep_stride = clv_replay_sweep_stride(s);
-  a.r.tape_sweeps = s->tape_sweeps;
+  a.r = rng_args(s);
   a.x = s->d_x;
   a.tx = s->d_tx;
   a.T = s->d_T;
@@ -88,20 +100,16 @@ SweepArgs sweep_args(clv_sampler* s, int init, int fuse = 0) {
 HyperArgs hyper_args(clv_sampler* s, const double* units, int mode) {
   HyperArgs a{};
   a.g = s->g;
-  a.r.seed = s->cfg.seed;
-  a.r.chain_first = s->cfg.chain_first;
-  a.r.tape = s->d_tape;
-  a.r.tape_sweep_stride = clv_replay_sweep_stride(s);
-  a.r.tape_sweeps = s->tape_sweeps;
+  a.r = rng_args(s);
   a.units = units ? units : s->d_unit;
   a.hyper = s->d_hyper;
   a.ctrl = s->d_ctrl;
   a.level2 = s->d_level2;
   a.loglik = s->d_loglik;
-  a.V = s->d_prior;
-  a.cholV = s->d_prior + 81;
-  a.A0B0 = s->d_prior + 162;
-  a.S0B = s->d_prior + 189;
+  a.V = s->d_prior + PRIOR_V;
+  a.cholV = s->d_prior + PRIOR_CHOLV;
+  a.A0B0 = s->d_prior + PRIOR_A0B0;
+  a.S0B = s->d_prior + PRIOR_S0B;
   a.nu_n = s->prior.nu_n;
   a.omega2 = s->prior.omega2;
   a.mode = mode;
@@ -111,17 +119,21 @@ HyperArgs hyper_args(clv_sampler* s, const double* units, int mode) {
   return a;
 }
 
+// The block partials of the sweep just enqueued summed into unit partials (blocks_per_unit > 1).
+int enqueue_group(clv_sampler* s) {
+  if (s->g.blocks_per_unit == 1) return CLV_OK;
+  GroupArgs ga{};
+  ga.g = s->g;
+  ga.blockpart = s->d_block;
+  ga.unitpart = s->d_unit;
+  CLV_HIP(launch_group(ga, s->stream));
+  return CLV_OK;
+}
+
 int enqueue_sweep(clv_sampler* s, hipEvent_t e0, hipEvent_t e1) {
   s->last_persist_n = 0;
   CLV_HIP(launch_sweep(sweep_args(s, 0), s->replay, s->stream, e0, e1));
-  if (s->g.blocks_per_unit > 1) {
-    GroupArgs ga{};
-    ga.g = s->g;
-    ga.blockpart = s->d_block;
-    ga.unitpart = s->d_unit;
-    CLV_HIP(launch_group(ga, s->stream));
-  }
-  return CLV_OK;
+  return enqueue_group(s);
 }
 
 // world_size == 1: one launch per sweep (the level-2 draw runs in the sweep kernel's tail)
@@ -169,12 +181,18 @@ int ensure_events(clv_sampler* s) {
   return CLV_OK;
 }
 
-int build_graph(clv_sampler* s, int n) {
-  if (s->graph_exec && s->graph_sweeps == n) return CLV_OK;
+// The captured graph holds state pointers, the tape, the wait bound and its stream: dropped when one changes.
+int drop_graph(clv_sampler* s) {
   if (s->graph_exec) {
     CLV_HIP(hipGraphExecDestroy(s->graph_exec));
     s->graph_exec = nullptr;
   }
+  return CLV_OK;
+}
+
+int build_graph(clv_sampler* s, int n) {
+  if (s->graph_exec && s->graph_sweeps == n) return CLV_OK;
+  if (int rc = drop_graph(s)) return rc;
   hipGraph_t graph;
   CLV_HIP(hipStreamBeginCapture(s->stream, hipStreamCaptureModeThreadLocal));
   for (int k = 0; k < n; ++k) {
@@ -194,18 +212,11 @@ int build_graph(clv_sampler* s, int n) {
 
 bool is_pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
 
-// Draws stored by the first `sweeps` sweeps (per chain): bi:402's condition, capped at n_draws.
-int64_t stored_count(const clv_sampler* s, int64_t sweeps) {
-  const Geometry& g = s->g;
-  if (sweeps <= g.burnin || g.n_draws <= 0) return 0;
-  return std::min<int64_t>((sweeps - 1 - g.burnin) / g.thin + 1, g.n_draws);
-}
-
 // Hand the level-1 draws completed since the last call to the copy pool (clv_stream_draws).
 void stream_enqueue(clv_sampler* s) {
   if (!s->ds_dest || !s->d_level1) return;
   const Geometry& g = s->g;
-  const int64_t k = stored_count(s, s->sweeps_done);
+  const int64_t k = stored_draws(s);
   if (k <= s->ds_next) return;
   const int64_t row = g.n * (g.D + 2);  // doubles per draw and chain
   for (int c = 0; c < g.n_chains; ++c) {
@@ -220,7 +231,7 @@ void stream_enqueue(clv_sampler* s) {
 void stream_rewind(clv_sampler* s) {
   if (!s->ds_dest) return;
   stream_wait(s->ds);
-  s->ds_next = std::min(s->ds_next, stored_count(s, s->sweeps_done));
+  s->ds_next = std::min(s->ds_next, stored_draws(s));
 }
 
 // The wait-timeout record of the last failed launch (kernels.hip report_wait) as text, and cleared
@@ -361,7 +372,9 @@ constexpr size_t PERSIST_SCRATCH_MAX = 64;
 #endif
 constexpr bool SPLIT_RELAY_DEFAULT = CLV_SPLIT_RELAY_DEFAULT != 0;
 
-bool clv::persist_worth(int D, int K, int n_chains, int64_t grid_wgs, int n_cu) {
+namespace {
+
+bool persist_worth(int D, int K, int n_chains, int64_t grid_wgs, int n_cu) {
   (void)D, (void)K, (void)n_chains;
   return n_cu > 0 && grid_wgs > 0;
 }
@@ -372,7 +385,7 @@ bool clv::persist_worth(int D, int K, int n_chains, int64_t grid_wgs, int n_cu) 
 // margin of one CU per 64 (4 of 256; c2 and c3 take 252).  The block rule's margin is one slot per 32
 // CUs of two-slot CUs; here a slot is a whole CU, so the same share of the card would leave c2 out.
 // Every wait stays bounded, and a handle whose split launch aborts goes back to the block layout.
-bool clv::persist_split_fits(int n_chains, int nb, int blocks_per_cu, int n_cu) {
+bool persist_split_fits(int n_chains, int nb, int blocks_per_cu, int n_cu) {
   if (n_chains < 1 || nb < 1 || nb > SPLIT_MAX_NB || blocks_per_cu < 1 || n_cu < 1) return false;
   const int64_t grid = (int64_t)n_chains * (split_wgs(nb) + 1);
   const int64_t margin = std::max(1, n_cu / 64);
@@ -381,20 +394,18 @@ bool clv::persist_split_fits(int n_chains, int nb, int blocks_per_cu, int n_cu) 
 
 // Worth choosing only where the block layout doubles up: with one block workgroup per CU no SIMD
 // holds two customer waves and there is nothing to balance.
-bool clv::persist_split_pays(int n_chains, int nb, int n_cu) { return (int64_t)n_chains * (nb + 1) > n_cu; }
+bool persist_split_pays(int n_chains, int nb, int n_cu) { return (int64_t)n_chains * (nb + 1) > n_cu; }
 
-// Chain by chain, each chain's workgroups in order (workgroup p hosts wave rows 6p .. 6p + 5), its
-// level-2 workgroup last: consecutive dispatch positions go round the XCDs, so every chain spreads
+// Per physical workgroup chain << 16 | p, chain by chain, each chain's workgroups in order (workgroup p hosts
+// wave rows 6p .. 6p + 5), its level-2 workgroup (p = split_wgs(nb)) last: consecutive dispatch positions go round the XCDs, so every chain spreads
 // over all of them.
-std::vector<int32_t> clv::persist_split_layout(int n_chains, int nb) {
+std::vector<int32_t> persist_split_layout(int n_chains, int nb) {
   const int per = split_wgs(nb) + 1;
   std::vector<int32_t> map((size_t)n_chains * per);
   for (int c = 0; c < n_chains; ++c)
     for (int p = 0; p < per; ++p) map[(size_t)c * per + p] = (c << 16) | p;
   return map;
 }
-
-namespace {
 
 // Persistent grid: which (chain, block) each dispatched workgroup runs.  The grid has more
 // workgroups (T = chains x (blocks + 1)) than CUs, and the dispatcher fills every CU once before
@@ -470,13 +481,108 @@ std::vector<int32_t> persist_wg_map(int C, int nb, int n_cu) {
   return map;
 }
 
-}  // namespace
+// ---- The sweep path of a handle, decided once at create: plan_sweep, a function of numbers (no HIP
+// call, no environment), so that it can be read and tested (clv_debug_sweep_plan) without a GPU. ----
 
-extern "C" {
+// The environment's knobs, read in one place.
+struct SweepEnv {
+  int persistent = -1;  // CLV_PERSISTENT: 0 never, 1 whenever the grid fits (tests, A/B), else -1: where it pays
+  int layout = 0;       // CLV_PERSIST_LAYOUT: 0 unset, LAYOUT_BLOCK, LAYOUT_SPLIT (tests, A/B), -1 anything else
+  int relay = -1;       // CLV_SPLIT_RELAY: -1 unset, 0 the helpers, 1 the relay (tests, A/B), 2 anything else
+  bool defer = true;    // CLV_DEFER=0: every launch draws its last level-2 draw
+  int mail_first = 0;   // CLV_MAIL_ALLOC = uncached | fine | default: the first memory kind tried for the mail
+  double wait_ms = 0.0;  // CLV_WAIT_TIMEOUT_MS (clamped to [1 ms, 1 h]); 0 unset, -1 not a finite decimal number
+};
 
-int clv_create(const clv_config* cfg, const clv_data* data, const clv_prior* prior, clv_sampler** out) {
-  if (!cfg || !data || !prior || !out) return fail(CLV_EINVAL, "null argument");
-  *out = nullptr;
+SweepEnv read_sweep_env() {
+  const auto is = [](const char* v, const char* text) { return v && !std::strcmp(v, text); };
+  SweepEnv e;
+  const char* v = std::getenv("CLV_PERSISTENT");
+  e.persistent = is(v, "0") ? 0 : is(v, "1") ? 1 : -1;
+  v = std::getenv("CLV_PERSIST_LAYOUT");
+  e.layout = !v ? 0 : is(v, "block") ? LAYOUT_BLOCK : is(v, "split") ? LAYOUT_SPLIT : -1;
+  v = std::getenv("CLV_SPLIT_RELAY");
+  e.relay = !v ? -1 : is(v, "0") ? 0 : is(v, "1") ? 1 : 2;
+  e.defer = !is(std::getenv("CLV_DEFER"), "0");
+  v = std::getenv("CLV_MAIL_ALLOC");
+  e.mail_first = is(v, "fine") ? 1 : is(v, "default") ? 2 : 0;
+  v = std::getenv("CLV_WAIT_TIMEOUT_MS");
+  if (v && !parse_wait_ms(v, &e.wait_ms)) e.wait_ms = -1.0;
+  return e;
+}
+
+// What the runtime reports of a kernel instance: workgroups per CU and scratch (spill) bytes per lane;
+// scratch < 0: not asked yet (plan_sweep says when it needs it), or the query failed (never capable).
+constexpr int64_t NOT_QUERIED = -2, QUERY_FAILED = -1;
+struct Instance { int bpc = 0; int64_t scratch = NOT_QUERIED; };
+struct SweepResources {
+  int n_cu = 0;                  // 0: a query of the block instance failed
+  Instance block, split, relay;  // persist_kernel (peer variant at world size > 1); persist_kernel_split: helpers, relay
+};
+struct SweepPlan {
+  bool persistent = false, split = false, p2p_capable = false, p2p_persist_fits = false, fx_capable = false, defer = false;
+  int relay_steps = 0;
+  bool need_split = false, need_relay = false;  // undecided until this instance's resources are known
+  const char* error = nullptr;                  // a rejected knob on a path that reads it (CLV_EINVAL)
+};
+
+// A shard whose persistent grid the kernels can run at all (every workgroup resident at once: the chain
+// hand-off spins on the others); with peers also the exchange's bounds: ranks, units, this rank's partials in UMAIL.
+bool persist_shape(const Geometry& g, bool replay) {
+  if (replay || g.nb_local <= 0 || g.nb_local > 2 * BLOCK) return false;
+  if (g.world_size == 1) return g.blocks_per_unit == 1;
+  const int bpu = g.blocks_per_unit;
+  return g.world_size <= MAX_WORLD && g.n_units_global <= 2 * BLOCK && bpu <= 64 &&
+         (int64_t)g.stride * ((g.nb_local + bpu - 1) / bpu) <= UMAIL;
+}
+
+// The two rules the CPU tests pin through clv_debug_persist_choice / clv_debug_split_choice.
+bool persist_grid_chosen(int D, int K, int n_chains, int64_t grid_wgs, int blocks_per_cu, int n_cu, bool force) {
+  return persist_grid_fits(grid_wgs, blocks_per_cu, n_cu) && (force || persist_worth(D, K, n_chains, grid_wgs, n_cu));
+}
+bool split_chosen(int n_chains, int nb, int blocks_per_cu, int n_cu, bool force) {
+  return persist_split_fits(n_chains, nb, blocks_per_cu, n_cu) && (force || persist_split_pays(n_chains, nb, n_cu));
+}
+
+SweepPlan plan_sweep(const Geometry& g, bool replay, const SweepResources& r, const SweepEnv& e) {
+  SweepPlan p;
+  const int C = g.n_chains, nb = g.nb_local;
+  // Persistent sweeps (one launch runs many sweeps) where the grid fits at once, here and (peers: the caller
+  // checks) on every rank; an instance spilling more than PERSIST_SCRATCH_MAX bytes per lane only when forced.
+  const bool force = e.persistent == 1;
+  const bool resident = persist_shape(g, replay) && e.persistent != 0 &&
+                        (force || (r.block.scratch >= 0 && r.block.scratch <= (int64_t)PERSIST_SCRATCH_MAX)) &&
+                        persist_grid_chosen(g.D, g.K, C, (int64_t)(nb + 1) * C, r.block.bpc, r.n_cu, force);
+  if (g.world_size == 1) p.persistent = resident;
+  else p.p2p_capable = p.p2p_persist_fits = resident;
+  // Any other shard with peers: the sweep kernel's fused level-2 tail exchanges through the same mail
+  // (one launch per sweep, no host collective; n_units_global <= 2 CLV_BLOCK as its readers assume)
+  p.fx_capable = !replay && g.world_size > 1 && g.world_size <= MAX_WORLD && g.n_units_global <= 2 * BLOCK;
+  p.defer = p.persistent && e.defer;
+  // Layout: split (persist_kernel_split: 6 customer + 2 helper wavefronts per CU) for bivariate models whose
+  // sweep's variates fit the pool, where its grid is resident whole with 0 B of scratch and the block layout
+  // would double up; forced, still only where it can run.  The layout knobs are read on this branch only.
+  if (!(p.persistent && g.D == 2 && g.S <= PRE_STEPS && nb <= SPLIT_MAX_NB)) return p;
+  if (e.layout < 0) p.error = "CLV_PERSIST_LAYOUT must be block or split";
+  else if (e.relay > 1) p.error = "CLV_SPLIT_RELAY must be 0 or 1";
+  if (p.error || e.layout == LAYOUT_BLOCK) return p;
+  if (r.split.scratch == NOT_QUERIED) {
+    p.need_split = true;
+    return p;
+  }
+  p.split = r.split.scratch == 0 && split_chosen(C, nb, r.split.bpc, r.n_cu, e.layout == LAYOUT_SPLIT);
+  // The relay instance (wavefronts 6 and 7 finish rows 4 and 5 from MH step SPLIT_RELAY_STEPS on) where the
+  // sweep has more steps than that and the instance has 0 B of scratch and fits; forced, only where it can run.
+  if (p.split && SPLIT_RELAY_STEPS > 0 && g.S > SPLIT_RELAY_STEPS && (e.relay < 0 ? SPLIT_RELAY_DEFAULT : e.relay == 1)) {
+    if (r.relay.scratch == NOT_QUERIED) p.need_relay = true;
+    else if (r.relay.scratch == 0 && persist_split_fits(C, nb, r.relay.bpc, r.n_cu)) p.relay_steps = SPLIT_RELAY_STEPS;
+  }
+  return p;
+}
+
+// ---- clv_create's steps.  Each returns its code; clv_create destroys the half-built handle. ----
+
+int validate_and_derive(const clv_config* cfg, const clv_data* data, const clv_prior* prior, clv_sampler** out) {
   if (cfg->abi_version != CLV_ABI_VERSION) return fail(CLV_EINVAL, "ABI version mismatch");
   if (cfg->D != 2 && cfg->D != 3) return fail(CLV_EINVAL, "D must be 2 or 3");
   if (cfg->K < 1 || cfg->K > CLV_MAX_K) return fail(CLV_EINVAL, "K must be in 1..9");
@@ -536,286 +642,249 @@ int clv_create(const clv_config* cfg, const clv_data* data, const clv_prior* pri
   g.thin = cfg->thin;
   g.n_draws = cfg->mcmc >= 1 ? (cfg->mcmc - 1) / cfg->thin + 1 : 0;
   g.l2w = cfg->D * cfg->K + cfg->D * (cfg->D + 1) / 2;
+  *out = s;
+  return CLV_OK;
+}
 
-  auto cleanup_fail = [&](int rc) {
-    clv_destroy(s);
-    return rc;
-  };
-#define CLV_HIPC(expr)                                                                            \
-  do {                                                                                            \
-    hipError_t e_ = (expr);                                                                       \
-    if (e_ != hipSuccess)                                                                         \
-      return cleanup_fail(fail(CLV_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)));    \
-  } while (0)
-
-  if (cfg->device >= 0) CLV_HIPC(hipSetDevice(cfg->device));
-  CLV_HIPC(hipGetDevice(&s->device));
-  if (cfg->stream) {
-    s->stream = (hipStream_t)(uintptr_t)cfg->stream;
+int open_device_and_stream(clv_sampler* s) {
+  if (s->cfg.device >= 0) CLV_HIP(hipSetDevice(s->cfg.device));
+  CLV_HIP(hipGetDevice(&s->device));
+  if (s->cfg.stream) {
+    s->stream = (hipStream_t)(uintptr_t)s->cfg.stream;
   } else {
-    CLV_HIPC(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-    s->own = s->stream;
-    s->own_stream = true;
+    CLV_HIP(hipStreamCreateWithFlags(&s->own, hipStreamNonBlocking));
+    s->stream = s->own;
   }
+  return CLV_OK;
+}
 
-  const int64_t n = g.n, C = g.n_chains;
-  CLV_HIPC(dalloc(&s->d_x, std::max<int64_t>(n, 1)));
-  CLV_HIPC(dalloc(&s->d_tx, std::max<int64_t>(n, 1)));
-  CLV_HIPC(dalloc(&s->d_T, std::max<int64_t>(n, 1)));
-  if (g.K > 1) CLV_HIPC(dalloc(&s->d_cov, (size_t)(g.K - 1) * std::max<int64_t>(n, 1)));
-  if (g.D == 3) CLV_HIPC(dalloc(&s->d_logs, std::max<int64_t>(n, 1)));
-  CLV_HIPC(dalloc(&s->d_clk, 2 * CLK_RING));
-  CLV_HIPC(hipMemsetAsync(s->d_clk, 0, sizeof(unsigned long long) * 2 * CLK_RING, s->stream));
-  CLV_HIPC(dalloc(&s->d_lam, C * std::max<int64_t>(n, 1)));
-  CLV_HIPC(dalloc(&s->d_mu, C * std::max<int64_t>(n, 1)));
-  CLV_HIPC(dalloc(&s->d_hyper, C * HS));
-  CLV_HIPC(dalloc(&s->d_block, (size_t)C * bpr * g.stride));
-  if (bpu > 1) CLV_HIPC(dalloc(&s->d_unit, (size_t)C * g.units_per_rank * g.stride));
-  else s->d_unit = s->d_block;
-  CLV_HIPC(dalloc(&s->d_prior, PRIOR_DOUBLES));
-  CLV_HIPC(dalloc(&s->d_ctrl, 1));
-  CLV_HIPC(dalloc(&s->d_arrive, C + C * (int64_t)g.units_per_rank));  // chain, then unit counters
-  CLV_HIPC(dalloc(&s->d_hvar, 2 * C * HV));
-  CLV_HIPC(dalloc(&s->d_hyp2, 2 * C * HS));
-  // Persistent sweeps (one launch runs many sweeps) when every workgroup of the grid can be
-  // resident at once — the chain hand-off spins on the other workgroups (CLV_PERSISTENT=0 opts out)
-  if (!s->replay && cfg->world_size == 1 && nb_local > 0 && bpu == 1 && nb_local <= 2 * BLOCK) {
-    const char* env = std::getenv("CLV_PERSISTENT");
+// One instance's resources for plan_sweep.  A failed query is "never capable", not an error.
+Instance query_split_instance(const Geometry& g, bool relay) {
+  Instance in;
+  size_t scratch = 0;
+  const bool ok = persist_split_resources(g.D, g.K, &in.bpc, &scratch, relay) == hipSuccess;
+  if (!ok) (void)hipGetLastError();
+  in.scratch = ok ? (int64_t)scratch : QUERY_FAILED;
+  return in;
+}
+
+// Ask the runtime for the resources the plan depends on — each instance only where plan_sweep reaches
+// the question — and record the plan in the handle.
+int decide_sweep_path(clv_sampler* s, const SweepEnv& env) {
+  const Geometry& g = s->g;
+  SweepResources r;
+  if (persist_shape(g, s->replay)) {
     hipDeviceProp_t prop{};
-    size_t scratch = SIZE_MAX;  // (a failed query: never persistent)
-    if (persist_occupancy(g.D, g.K, false, &s->persist_bpc) == hipSuccess &&
-        persist_scratch_bytes(g.D, g.K, false, &scratch) == hipSuccess &&
-        hipGetDeviceProperties(&prop, s->device) == hipSuccess)
-      s->n_cu = prop.multiProcessorCount;
-    // CLV_PERSISTENT: "0" never, "1" whenever the grid fits (tests, A/B), unset: where it pays;
-    // an instance that spills more than PERSIST_SCRATCH_MAX bytes per lane only when forced (tests)
-    const int64_t grid = (int64_t)(nb_local + 1) * C;
-    const bool force = env && std::string(env) == "1";
-    if ((!env || std::string(env) != "0") && (force || scratch <= PERSIST_SCRATCH_MAX) && persist_grid_fits(grid, s->persist_bpc, s->n_cu) &&
-        (force || persist_worth(g.D, g.K, (int)C, grid, s->n_cu)))
-      s->persistent = true;
-    // Layout of the persistent grid.  Split (persist_kernel_split: 6 customer + 2 helper wavefronts
-    // per CU) for bivariate models whose sweep's variates fit the pool, where its grid is resident
-    // whole with 0 B of scratch and the block layout would double up; CLV_PERSIST_LAYOUT=block |
-    // split forces one (tests, A/B; split still only where it can run).
-    if (s->persistent && g.D == 2 && g.S <= PRE_STEPS && nb_local <= SPLIT_MAX_NB) {
-      const char* lay = std::getenv("CLV_PERSIST_LAYOUT");
-      const std::string want = lay ? lay : "";
-      if (lay && want != "block" && want != "split")
-        return cleanup_fail(fail(CLV_EINVAL, "CLV_PERSIST_LAYOUT must be block or split"));
-      int bpc = 0;
-      size_t sscratch = SIZE_MAX;
-      if (want != "block" && persist_split_resources(g.D, g.K, &bpc, &sscratch) == hipSuccess && sscratch == 0 &&
-          persist_split_fits((int)C, (int)nb_local, bpc, s->n_cu) &&
-          (want == "split" || persist_split_pays((int)C, (int)nb_local, s->n_cu)))
-        s->split = true;
-      else
-        (void)hipGetLastError();
-      // The relay instance (wavefronts 6 and 7 finish rows 4 and 5 from MH step SPLIT_RELAY_STEPS on)
-      // where the sweep has more steps than that and the instance has 0 B of scratch and fits as the
-      // helper instance does; CLV_SPLIT_RELAY = 0 | 1 forces the helpers / the relay (tests, A/B;
-      // the relay still only where it can run).
-      const char* rel = std::getenv("CLV_SPLIT_RELAY");
-      const std::string rwant = rel ? rel : "";
-      if (rel && rwant != "0" && rwant != "1")
-        return cleanup_fail(fail(CLV_EINVAL, "CLV_SPLIT_RELAY must be 0 or 1"));
-      if (s->split && SPLIT_RELAY_STEPS > 0 && g.S > SPLIT_RELAY_STEPS && (rel ? rwant == "1" : SPLIT_RELAY_DEFAULT)) {
-        int rbpc = 0;
-        size_t rscratch = SIZE_MAX;
-        if (persist_split_resources(g.D, g.K, &rbpc, &rscratch, true) == hipSuccess && rscratch == 0 &&
-            persist_split_fits((int)C, (int)nb_local, rbpc, s->n_cu))
-          s->relay_steps = SPLIT_RELAY_STEPS;
-        else
-          (void)hipGetLastError();
-      }
+    size_t scratch = 0;
+    r.block.scratch = QUERY_FAILED;
+    if (persist_occupancy(g.D, g.K, g.world_size > 1, &r.block.bpc) == hipSuccess &&
+        persist_scratch_bytes(g.D, g.K, g.world_size > 1, &scratch) == hipSuccess &&
+        hipGetDeviceProperties(&prop, s->device) == hipSuccess) {
+      r.block.scratch = (int64_t)scratch;
+      r.n_cu = prop.multiProcessorCount;
     }
+    s->persist_bpc = r.block.bpc;
+    s->n_cu = r.n_cu;
   }
-  // World size > 1: the same persistent kernel exchanging unit partials with its peers over xGMI
-  // (clv_p2p_connect) when the grid fits at once here, as above, and on every rank (the caller
-  // checks that all ranks are capable before connecting).
-  if (!s->replay && cfg->world_size > 1 && cfg->world_size <= MAX_WORLD && nb_local > 0 && nb_local <= 2 * BLOCK && g.n_units_global <= 2 * BLOCK &&
-      bpu <= 64 && (int64_t)g.stride * ((nb_local + bpu - 1) / bpu) <= UMAIL) {
-    hipDeviceProp_t prop{};
-    size_t scratch = SIZE_MAX;  // (a failed query: never persistent)
-    if (persist_occupancy(g.D, g.K, true, &s->persist_bpc) == hipSuccess &&
-        persist_scratch_bytes(g.D, g.K, true, &scratch) == hipSuccess &&
-        hipGetDeviceProperties(&prop, s->device) == hipSuccess)
-      s->n_cu = prop.multiProcessorCount;
-    const char* env = std::getenv("CLV_PERSISTENT");  // "0": the fused exchange below instead
-    const int64_t grid = (int64_t)(nb_local + 1) * C;
-    const bool force = env && std::string(env) == "1";
-    if ((!env || std::string(env) != "0") && (force || scratch <= PERSIST_SCRATCH_MAX) && persist_grid_fits(grid, s->persist_bpc, s->n_cu) &&
-        (force || persist_worth(g.D, g.K, (int)C, grid, s->n_cu)))
-      s->p2p_capable = s->p2p_persist_fits = true;
+  SweepPlan p = plan_sweep(g, s->replay, r, env);
+  if (p.need_split) {
+    r.split = query_split_instance(g, false);
+    p = plan_sweep(g, s->replay, r, env);
   }
-  // Any other shard: the sweep kernel's fused level-2 tail exchanges through the same mail (one
-  // launch per sweep, no host collective; n_units_global <= 2 CLV_BLOCK as its readers assume)
-  if (!s->replay && cfg->world_size > 1 && cfg->world_size <= MAX_WORLD && g.n_units_global <= 2 * BLOCK)
-    s->fx_capable = true;
+  if (p.need_relay) {  // (the relay question follows the split answer)
+    r.relay = query_split_instance(g, true);
+    p = plan_sweep(g, s->replay, r, env);
+  }
+  if (p.error) return fail(CLV_EINVAL, p.error);
+  s->persistent = p.persistent;
+  s->split = p.split;
+  s->relay_steps = p.relay_steps;
+  s->p2p_capable = p.p2p_capable;
+  s->p2p_persist_fits = p.p2p_persist_fits;
+  s->fx_capable = p.fx_capable;
+  s->defer = p.defer;
+  if (s->persistent || s->p2p_capable || s->fx_capable) {
+    // every wait of the persistent kernel is bounded: 2 s at world size 1 (all workgroups are resident, so a wait
+    // that long means a fault), 10 s with peers (host-side launch skew between ranks); CLV_WAIT_TIMEOUT_MS overrides
+    if (env.wait_ms < 0) return fail(CLV_EINVAL, "CLV_WAIT_TIMEOUT_MS must be a finite decimal number of ms");
+    const double ms = env.wait_ms > 0 ? env.wait_ms : g.world_size > 1 ? 10000.0 : 2000.0;
+    s->wait_ticks = (uint64_t)(ms * 1e5);  // s_memrealtime: 100 MHz
+  }
+  return CLV_OK;
+}
+
+void forget_peers(clv_sampler* s) {  // not connected; the peers' IPC mappings closed
+  s->p2p_ready = false;
+  for (void* p : s->ipc_opened) (void)hipIpcCloseMemHandle(p);
+  s->ipc_opened.clear();
+}
+
+// every slot of the peer mail empty (all-ones bytes: the sentinel NaN)
+hipError_t fill_mail(clv_sampler* s) {
+  return hipMemsetAsync(s->d_mail, 0xFF, sizeof(double) * mail_count(s->g), s->stream);
+}
+
+// Every buffer of the handle, the clears queued on the stream (before the uploads and the initial
+// sweep: stream order).  The order among the clears is incidental.
+int allocate_and_clear(clv_sampler* s, const SweepEnv& env) {
+  const Geometry& g = s->g;
+  const hipStream_t st = s->stream;
+  const size_t C = g.n_chains, n1 = std::max<int64_t>(g.n, 1);  // (no empty allocation for an empty shard)
+  const bool summary = (s->cfg.draw_sink == CLV_SINK_SUMMARY || s->cfg.draw_sink == CLV_SINK_SUMMARY_PCT) && g.n > 0;
+  CLV_HIP(s->d_x.alloc(n1));
+  for (auto* b : {&s->d_tx, &s->d_T}) CLV_HIP(b->alloc(n1));
+  if (g.K > 1) CLV_HIP(s->d_cov.alloc((g.K - 1) * n1));
+  if (g.D == 3) CLV_HIP(s->d_logs.alloc(n1));
+  CLV_HIP(s->d_clk.alloc(2 * CLK_RING, 0, st));
+  for (auto* b : {&s->d_lam, &s->d_mu}) CLV_HIP(b->alloc(state_count(g)));
+  CLV_HIP(s->d_hyper.alloc(hyper_count(g), 0, st));
+  CLV_HIP(s->d_block.alloc(C * g.blocks_per_rank * g.stride, 0, st));
+  if (g.blocks_per_unit > 1) CLV_HIP(s->d_unit_own.alloc(unit_count(g), 0, st));
+  s->d_unit = g.blocks_per_unit > 1 ? s->d_unit_own : s->d_block;
+  CLV_HIP(s->d_prior.alloc(PRIOR_DOUBLES));
+  CLV_HIP(s->d_ctrl.alloc(1, 0, st));
+  CLV_HIP(s->d_arrive.alloc(arrive_count(g), 0, st));
+  CLV_HIP(s->d_hvar.alloc(2 * C * HV, 0, st));
+  CLV_HIP(s->d_hyp2.alloc(handoff_count(g)));
   if (s->p2p_capable || s->fx_capable) {
-    // the slots, then one progress word per rank (MAIL_TAIL)
-    const int64_t nm = mail_slots(g.world_size, (int)C, g.stride, g.units_per_rank) + MAIL_TAIL;
-    // The mail is written by OTHER GPUs (system-scope write-through stores over xGMI) while this
-    // GPU polls it.  Uncached device memory (MTYPE UC: every access of every agent goes to memory,
-    // no L2 line of this GPU can hold a stale copy of a peer's store); fine-grained, then plain
-    // device memory if the allocator refuses (CLV_MAIL_ALLOC = uncached | fine | default selects)
-    {
-      const char* env = std::getenv("CLV_MAIL_ALLOC");
-      const std::string want = env ? env : "uncached";
-      const unsigned flags[3] = {hipDeviceMallocUncached, hipDeviceMallocFinegrained, hipDeviceMallocDefault};
-      const int first = want == "fine" ? 1 : want == "default" ? 2 : 0;
-      for (int k = first; k < 3 && !s->d_mail; ++k) {
-        void* p = nullptr;
-        if (hipExtMallocWithFlags(&p, sizeof(double) * (size_t)nm, flags[k]) == hipSuccess && p) {
-          s->d_mail = (double*)p;
-          s->mail_kind = k;
-        } else {
-          (void)hipGetLastError();
-        }
+    // The mail is written by OTHER GPUs (system-scope write-through stores over xGMI) while this GPU polls it.
+    // Uncached device memory (MTYPE UC: every access of every agent goes to memory, no L2 line of this GPU can
+    // hold a stale copy of a peer's store); fine-grained, then plain device memory if the allocator refuses
+    const unsigned flags[3] = {hipDeviceMallocUncached, hipDeviceMallocFinegrained, hipDeviceMallocDefault};
+    for (int k = env.mail_first; k < 3 && !s->d_mail; ++k) {
+      void* p = nullptr;
+      if (hipExtMallocWithFlags(&p, sizeof(double) * mail_count(g), flags[k]) == hipSuccess && p) {
+        s->d_mail.reset((double*)p);
+        s->mail_kind = k;
+      } else {
+        (void)hipGetLastError();
       }
-      if (!s->d_mail) return cleanup_fail(fail(CLV_ENOMEM, "peer mail buffer"));
     }
-    CLV_HIPC(hipMemsetAsync(s->d_mail, 0xFF, sizeof(double) * nm, s->stream));  // every slot empty
-    CLV_HIPC(dalloc(&s->d_peers, g.world_size));
+    if (!s->d_mail) return fail(CLV_ENOMEM, "peer mail buffer");
+    CLV_HIP(fill_mail(s));
+    CLV_HIP(s->d_peers.alloc(g.world_size));
   }
   if (s->persistent || s->p2p_capable || s->fx_capable) {  // (fused exchange: the snapshot buffers)
-    // (the split layout's records: the block slots and two more per split block)
-    CLV_HIPC(dalloc(&s->d_pblock, (size_t)C * split_records(std::max((int)nb_local, 1)) * g.stride));
-    if (s->persistent) {  // deferred level-2 draws (CLV_DEFER=0: every launch draws its last one)
-      const char* env = std::getenv("CLV_DEFER");
-      s->defer = !(env && std::string(env) == "0");
-      if (s->defer) CLV_HIPC(dalloc(&s->d_pend, (size_t)2 * C * g.stride));
-    }
-    CLV_HIPC(dalloc(&s->d_lam_alt, C * std::max<int64_t>(n, 1)));
-    CLV_HIPC(dalloc(&s->d_mu_alt, C * std::max<int64_t>(n, 1)));
-    CLV_HIPC(dalloc(&s->d_hyper_alt, C * HS));
-    if ((cfg->draw_sink == CLV_SINK_SUMMARY || cfg->draw_sink == CLV_SINK_SUMMARY_PCT) && n > 0)
-      CLV_HIPC(dalloc(&s->d_sums_prev, (size_t)C * CLV_N_SUM_STATS * n));
-    CLV_HIPC(dalloc(&s->d_diag, DIAG_WORDS));
-    CLV_HIPC(hipMemsetAsync(s->d_diag, 0, sizeof(unsigned long long) * DIAG_WORDS, s->stream));
-    CLV_HIPC(hipHostMalloc((void**)&s->h_abort, sizeof(uint32_t), hipHostMallocMapped));
+    CLV_HIP(s->d_pblock.alloc(pblock_count(g)));
+    if (s->defer) CLV_HIP(s->d_pend.alloc(2 * C * g.stride));
+    for (auto* b : {&s->d_lam_alt, &s->d_mu_alt}) CLV_HIP(b->alloc(state_count(g)));
+    CLV_HIP(s->d_hyper_alt.alloc(hyper_count(g)));
+    if (summary) CLV_HIP(s->d_sums_prev.alloc(sums_count(g)));
+    CLV_HIP(s->d_diag.alloc(DIAG_WORDS, 0, st));
+    CLV_HIP(hipHostMalloc((void**)&s->h_abort, sizeof(uint32_t), hipHostMallocMapped));
     *s->h_abort = 0;
-    CLV_HIPC(hipHostGetDevicePointer((void**)&s->d_h_abort, s->h_abort, 0));
-    // every wait of the persistent kernel is bounded: 2 s at world size 1 (all workgroups are
-    // resident, so a wait that long means a fault), 10 s with peers (host-side launch skew between
-    // ranks); CLV_WAIT_TIMEOUT_MS overrides
-    double ms = cfg->world_size > 1 ? 10000.0 : 2000.0;
-    if (const char* env = std::getenv("CLV_WAIT_TIMEOUT_MS")) {
-      if (!parse_wait_ms(env, &ms))
-        return cleanup_fail(fail(CLV_EINVAL, "CLV_WAIT_TIMEOUT_MS must be a finite decimal number of ms"));
-    }
-    s->wait_ticks = (uint64_t)(ms * 1e5);  // s_memrealtime: 100 MHz
+    CLV_HIP(hipHostGetDevicePointer((void**)&s->d_h_abort, s->h_abort, 0));
   }
   if ((s->persistent || s->p2p_capable) && s->n_cu > 0) {
     // same-chain pairs on shared CUs, bivariate and trivariate: with the MH-phase wave priority
     // (kernels.hip persist_kernel) measured c2 10.70 -> 9.58 us per sweep against no map, c3 11.45 ->
     // 11.1 (chain pairs c / c + 2 instead: c2 10.16, c3 11.1; profiles/r05_ab_priority.txt)
-    {
-      std::vector<int32_t> map = persist_wg_map((int)C, (int)nb_local, s->n_cu);
-      CLV_HIPC(dalloc(&s->d_wgmap, map.size()));
-      CLV_HIPC(hipMemcpy(s->d_wgmap, map.data(), sizeof(int32_t) * map.size(), hipMemcpyHostToDevice));
-    }
+    const std::vector<int32_t> map = persist_wg_map((int)C, g.nb_local, s->n_cu);
+    CLV_HIP(s->d_wgmap.upload(map.data(), map.size()));
     if (s->split) {
-      std::vector<int32_t> map = persist_split_layout((int)C, (int)nb_local);
-      CLV_HIPC(dalloc(&s->d_wgmap_split, map.size()));
-      CLV_HIPC(hipMemcpy(s->d_wgmap_split, map.data(), sizeof(int32_t) * map.size(), hipMemcpyHostToDevice));
+      const std::vector<int32_t> smap = persist_split_layout((int)C, g.nb_local);
+      CLV_HIP(s->d_wgmap_split.upload(smap.data(), smap.size()));
     }
   }
 #ifdef CLV_STAMPS
   {
     // (+ 16 words per workgroup: the split layout's relay stamps and SIMD ids, clv_debug_split_stamps)
-    std::vector<unsigned long long> st(1024 * 8 + (12 + 16) * (size_t)C * (std::max(nb_local, 1) + 1), 0ull);
-    for (int i = 0; i < 1024; ++i) st[i * 8 + 0] = st[i * 8 + 4] = ~0ull;
-    CLV_HIPC(dalloc(&s->d_stamps, st.size()));
-    CLV_HIPC(hipMemcpy(s->d_stamps, st.data(), st.size() * sizeof(unsigned long long), hipMemcpyHostToDevice));
+    std::vector<unsigned long long> stamps(1024 * 8 + (12 + 16) * C * (std::max(g.nb_local, 1) + 1), 0ull);
+    for (int i = 0; i < 1024; ++i) stamps[i * 8 + 0] = stamps[i * 8 + 4] = ~0ull;
+    CLV_HIP(s->d_stamps.upload(stamps.data(), stamps.size()));
   }
 #endif
-  CLV_HIPC(hipMemsetAsync(s->d_hvar, 0, sizeof(double) * 2 * C * HV, s->stream));
-  CLV_HIPC(hipMemsetAsync(s->d_arrive, 0, sizeof(uint32_t) * (C + C * (int64_t)g.units_per_rank), s->stream));
-  CLV_HIPC(dalloc(&s->d_bs, C * (CLV_MAX_K * CLV_MAX_D + CLV_MAX_D * CLV_MAX_D)));
+  CLV_HIP(s->d_bs.alloc(C * (CLV_MAX_K * CLV_MAX_D + CLV_MAX_D * CLV_MAX_D)));
   if (g.n_draws > 0) {
-    CLV_HIPC(dalloc(&s->d_level2, (size_t)C * g.n_draws * g.l2w));
-    CLV_HIPC(dalloc(&s->d_loglik, (size_t)C * g.n_draws));
-    CLV_HIPC(hipMemsetAsync(s->d_level2, 0, sizeof(double) * C * g.n_draws * g.l2w, s->stream));
-    CLV_HIPC(hipMemsetAsync(s->d_loglik, 0, sizeof(double) * C * g.n_draws, s->stream));
-    if (cfg->draw_sink == CLV_SINK_FULL && n > 0) {
-      const size_t bytes = sizeof(double) * (size_t)C * g.n_draws * n * (g.D + 2);
-      CLV_HIPC(dalloc(&s->d_level1, bytes / sizeof(double)));
-      CLV_HIPC(hipMemsetAsync(s->d_level1, 0, bytes, s->stream));
-    }
+    CLV_HIP(s->d_level2.alloc(loglik_count(g) * g.l2w, 0, st));
+    CLV_HIP(s->d_loglik.alloc(loglik_count(g), 0, st));
+    if (s->cfg.draw_sink == CLV_SINK_FULL) CLV_HIP(s->d_level1.alloc(level1_count(g), 0, st));
   }
-  if ((cfg->draw_sink == CLV_SINK_SUMMARY || cfg->draw_sink == CLV_SINK_SUMMARY_PCT) && n > 0) {
-    CLV_HIPC(dalloc(&s->d_sums, (size_t)C * CLV_N_SUM_STATS * n));
-    CLV_HIPC(hipMemsetAsync(s->d_sums, 0, sizeof(double) * C * CLV_N_SUM_STATS * n, s->stream));
-  }
-  if (cfg->draw_sink == CLV_SINK_SUMMARY_PCT && n > 0 && g.n_draws > 0) {
-    const size_t nq = (size_t)C * g.n_draws * n;
-    if (hipMalloc((void**)&s->d_qstore, sizeof(float2) * nq) != hipSuccess) {
+  if (summary) CLV_HIP(s->d_sums.alloc(sums_count(g), 0, st));
+  if (s->cfg.draw_sink == CLV_SINK_SUMMARY_PCT) {
+    const size_t nq = loglik_count(g) * g.n;  // a (lambda, mu) pair per stored draw and customer
+    if (s->d_qstore.alloc(nq) != hipSuccess) {
       (void)hipGetLastError();
-      s->d_qstore = nullptr;
-      return cleanup_fail(fail(CLV_ENOMEM, "percentile store: " + std::to_string(sizeof(float2) * nq) +
-                                               " bytes of device memory not available"));
+      return fail(CLV_ENOMEM, "percentile store: " + std::to_string(sizeof(float2) * nq) +
+                                  " bytes of device memory not available");
     }
-    CLV_HIPC(hipMemsetAsync(s->d_qstore, 0, sizeof(float2) * nq, s->stream));
+    if (nq) CLV_HIP(hipMemsetAsync(s->d_qstore, 0, sizeof(float2) * nq, st));
   }
-  CLV_HIPC(hipMemsetAsync(s->d_block, 0, sizeof(double) * C * bpr * g.stride, s->stream));
-  if (bpu > 1) CLV_HIPC(hipMemsetAsync(s->d_unit, 0, sizeof(double) * C * g.units_per_rank * g.stride, s->stream));
-  CLV_HIPC(hipMemsetAsync(s->d_ctrl, 0, sizeof(Ctrl), s->stream));
-  CLV_HIPC(hipMemsetAsync(s->d_hyper, 0, sizeof(double) * C * HS, s->stream));
+  return CLV_OK;
+}
 
+int upload_data_and_prior(clv_sampler* s, const clv_data* data, const clv_prior* prior) {
+  const Geometry& g = s->g;
+  const hipStream_t st = s->stream;
+  const size_t n = g.n;
   if (n > 0) {
-    CLV_HIPC(hipMemcpyAsync(s->d_x, data->x, sizeof(int32_t) * n, hipMemcpyHostToDevice, s->stream));
-    CLV_HIPC(hipMemcpyAsync(s->d_tx, data->t_x, sizeof(double) * n, hipMemcpyHostToDevice, s->stream));
-    CLV_HIPC(hipMemcpyAsync(s->d_T, data->T_cal, sizeof(double) * n, hipMemcpyHostToDevice, s->stream));
-    if (g.K > 1)
-      CLV_HIPC(hipMemcpyAsync(s->d_cov, data->covariates, sizeof(double) * (g.K - 1) * n, hipMemcpyHostToDevice, s->stream));
-    if (g.D == 3)
-      CLV_HIPC(hipMemcpyAsync(s->d_logs, data->log_s, sizeof(double) * n, hipMemcpyHostToDevice, s->stream));
+    CLV_HIP(hipMemcpyAsync(s->d_x, data->x, sizeof(int32_t) * n, hipMemcpyHostToDevice, st));
+    CLV_HIP(hipMemcpyAsync(s->d_tx, data->t_x, sizeof(double) * n, hipMemcpyHostToDevice, st));
+    CLV_HIP(hipMemcpyAsync(s->d_T, data->T_cal, sizeof(double) * n, hipMemcpyHostToDevice, st));
+    if (g.K > 1) CLV_HIP(hipMemcpyAsync(s->d_cov, data->covariates, sizeof(double) * (g.K - 1) * n, hipMemcpyHostToDevice, st));
+    if (g.D == 3) CLV_HIP(hipMemcpyAsync(s->d_logs, data->log_s, sizeof(double) * n, hipMemcpyHostToDevice, st));
   }
-  {
-    std::vector<double> pr(PRIOR_DOUBLES, 0.0);
-    const int K = g.K, D = g.D;
-    for (int i = 0; i < K * K; ++i) {
-      pr[i] = prior->V[i];
-      pr[81 + i] = prior->chol_V[i];
-    }
-    for (int i = 0; i < K * D; ++i) pr[162 + i] = prior->A0B0[i];
-    for (int i = 0; i < D * D; ++i) pr[189 + i] = prior->S0_B0A0B0[i];
-    CLV_HIPC(hipMemcpyAsync(s->d_prior, pr.data(), sizeof(double) * PRIOR_DOUBLES, hipMemcpyHostToDevice, s->stream));
-    CLV_HIPC(hipStreamSynchronize(s->stream));
-  }
+  const std::vector<double> pr = pack_prior(prior, g.D, g.K);
+  CLV_HIP(hipMemcpyAsync(s->d_prior, pr.data(), sizeof(double) * pr.size(), hipMemcpyHostToDevice, st));
+  // needed: the copies read pageable host memory (pr, the caller's arrays) that must outlive them
+  CLV_HIP(hipStreamSynchronize(st));
+  return CLV_OK;
+}
 
-  // Initial state (bi:367-379, tri:488-504) and, for D == 2, the statistics of the first draw.
-  if (n > 0) CLV_HIPC(launch_sweep(sweep_args(s, 1), false, s->stream));
-  else CLV_HIPC(hipMemsetAsync(s->d_block, 0, sizeof(double) * C * bpr * g.stride, s->stream));
-  if (bpu > 1) {
-    GroupArgs ga{};
-    ga.g = g;
-    ga.blockpart = s->d_block;
-    ga.unitpart = s->d_unit;
-    if (n > 0) CLV_HIPC(launch_group(ga, s->stream));
+// Initial state (bi:367-379, tri:488-504) and, for D == 2, the statistics of the first draw.  In
+// stream order behind the clears and the uploads; the group kernel reads the sweep's block partials.
+int initial_state(clv_sampler* s) {
+  const Geometry& g = s->g;
+  if (g.n > 0) {
+    CLV_HIP(launch_sweep(sweep_args(s, 1), false, s->stream));
+    if (int rc = enqueue_group(s)) return rc;
   }
+  std::vector<double> bs;
   if (g.D == 3) {
-    std::vector<double> bs(C * (g.K * g.D + g.D * g.D));
-    for (int c = 0; c < C; ++c) {
-      double* o = bs.data() + c * (g.K * g.D + g.D * g.D);
-      for (int i = 0; i < g.K * g.D; ++i) o[i] = prior->beta_init[i];
-      for (int i = 0; i < g.D * g.D; ++i) o[g.K * g.D + i] = prior->sigma_init[i];
+    const int w = g.K * g.D + g.D * g.D;
+    bs.resize((size_t)g.n_chains * w);
+    for (int c = 0; c < g.n_chains; ++c) {
+      double* o = bs.data() + (size_t)c * w;
+      for (int i = 0; i < g.K * g.D; ++i) o[i] = s->prior.beta_init[i];
+      for (int i = 0; i < g.D * g.D; ++i) o[g.K * g.D + i] = s->prior.sigma_init[i];
     }
-    CLV_HIPC(hipMemcpyAsync(s->d_bs, bs.data(), sizeof(double) * bs.size(), hipMemcpyHostToDevice, s->stream));
-    CLV_HIPC(launch_set_hyper(g.D, g.K, (int)C, s->d_hyper, s->d_bs, prior->omega2, s->replay, s->stream));
+    CLV_HIP(hipMemcpyAsync(s->d_bs, bs.data(), sizeof(double) * bs.size(), hipMemcpyHostToDevice, s->stream));
+    CLV_HIP(launch_set_hyper(g.D, g.K, g.n_chains, s->d_hyper, s->d_bs, s->prior.omega2, s->replay, s->stream));
   } else {
     s->pending_init_hyper = true;
   }
-  CLV_HIPC(hipStreamSynchronize(s->stream));
-#undef CLV_HIPC
+  // needed: bs must outlive its copy, and the caller may use the handle from another stream at once
+  CLV_HIP(hipStreamSynchronize(s->stream));
+  return CLV_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int clv_create(const clv_config* cfg, const clv_data* data, const clv_prior* prior, clv_sampler** out) {
+  if (!cfg || !data || !prior || !out) return fail(CLV_EINVAL, "null argument");
+  *out = nullptr;
+  clv_sampler* s = nullptr;
+  int rc = validate_and_derive(cfg, data, prior, &s);
+  if (rc) return rc;
+  const SweepEnv env = read_sweep_env();
+  rc = open_device_and_stream(s);
+  if (!rc) rc = decide_sweep_path(s, env);
+  if (!rc) rc = allocate_and_clear(s, env);
+  if (!rc) rc = upload_data_and_prior(s, data, prior);
+  if (!rc) rc = initial_state(s);
+  if (rc) {
+    clv_destroy(s);  // (owning members: whatever the steps had allocated)
+    return rc;
+  }
   *out = s;
   return CLV_OK;
 }
 
 void clv_destroy(clv_sampler* s) {
   if (!s) return;
-  (void)hipSetDevice(s->device);
+  (void)hipSetDevice(s->device);  // current while the members below free their memory
   if (s->stream) (void)hipStreamSynchronize(s->stream);
   if (s->ds) {  // no copy may still read the draws freed below
     stream_wait(s->ds);
@@ -824,42 +893,20 @@ void clv_destroy(clv_sampler* s) {
   if (s->graph_exec) (void)hipGraphExecDestroy(s->graph_exec);
   for (auto e : s->ev) (void)hipEventDestroy(e);
   if (s->done_ev) (void)hipEventDestroy(s->done_ev);
-  void* ptrs[] = {s->d_x, s->d_tx, s->d_T, s->d_cov, s->d_logs, s->d_lam, s->d_mu, s->d_hyper,
-                  s->d_block, s->d_prior, s->d_ctrl, s->d_level1, s->d_level2, s->d_loglik,
-                  s->d_sums, s->d_tape, s->d_bs, s->d_arrive, s->d_hvar, s->d_stamps};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  if (s->d_unit && s->d_unit != s->d_block) (void)hipFree(s->d_unit);
-  if (s->d_hyp2) (void)hipFree(s->d_hyp2);
-  for (void* p : {(void*)s->d_lam_alt, (void*)s->d_mu_alt, (void*)s->d_hyper_alt, (void*)s->d_sums_prev,
-                  (void*)s->d_pblock, (void*)s->d_qstore, (void*)s->d_pend, (void*)s->d_diag,
-                  (void*)s->d_clk})
-    if (p) (void)hipFree(p);
   if (s->h_abort) (void)hipHostFree(s->h_abort);
-  for (void* p : s->ipc_opened) (void)hipIpcCloseMemHandle(p);
-  if (s->d_mail) (void)hipFree(s->d_mail);
-  if (s->d_peers) (void)hipFree(s->d_peers);
-  if (s->d_wgmap) (void)hipFree(s->d_wgmap);
-  if (s->d_wgmap_split) (void)hipFree(s->d_wgmap_split);
-  if (s->own_stream && s->own) (void)hipStreamDestroy(s->own);
-  delete s;
+  forget_peers(s);  // before this rank's mail goes
+  const hipStream_t own = s->own;
+  delete s;  // every device buffer (the DevPtr members)
+  if (own) (void)hipStreamDestroy(own);  // last
 }
 
 int clv_set_replay_tape(clv_sampler* s, const double* tape, int64_t n_sweeps) {
   if (!s || !tape || n_sweeps < 1) return fail(CLV_EINVAL, "bad replay tape arguments");
   if (!s->replay) return fail(CLV_ESTATE, "sampler not created in replay mode");
   CLV_HIP(hipSetDevice(s->device));
-  if (s->d_tape) CLV_HIP(hipFree(s->d_tape));
-  s->d_tape = nullptr;
-  const size_t count = (size_t)s->g.n_chains * n_sweeps * clv_replay_sweep_stride(s);
-  CLV_HIP(dalloc(&s->d_tape, count));
-  CLV_HIP(hipMemcpy(s->d_tape, tape, count * sizeof(double), hipMemcpyHostToDevice));
+  CLV_HIP(s->d_tape.upload(tape, (size_t)s->g.n_chains * n_sweeps * clv_replay_sweep_stride(s)));
   s->tape_sweeps = n_sweeps;
-  if (s->graph_exec) {
-    CLV_HIP(hipGraphExecDestroy(s->graph_exec));
-    s->graph_exec = nullptr;
-  }
-  return CLV_OK;
+  return drop_graph(s);
 }
 
 int clv_hyper(clv_sampler* s, const double* gathered) {
@@ -909,7 +956,7 @@ int clv_sweep(clv_sampler* s) {
 int clv_partials(clv_sampler* s, double** ptr, int64_t* n_doubles, int32_t* stride) {
   if (!s) return fail(CLV_EINVAL, "null sampler");
   if (ptr) *ptr = s->d_unit;
-  if (n_doubles) *n_doubles = (int64_t)s->g.n_chains * s->g.units_per_rank * s->g.stride;
+  if (n_doubles) *n_doubles = (int64_t)unit_count(s->g);
   if (stride) *stride = s->g.stride;
   return CLV_OK;
 }
@@ -917,8 +964,7 @@ int clv_partials(clv_sampler* s, double** ptr, int64_t* n_doubles, int32_t* stri
 int clv_copy_partials(clv_sampler* s, void* dst) {
   if (!s || !dst) return fail(CLV_EINVAL, "null argument");
   CLV_HIP(hipSetDevice(s->device));
-  const size_t bytes = sizeof(double) * (size_t)s->g.n_chains * s->g.units_per_rank * s->g.stride;
-  CLV_HIP(hipMemcpyAsync(dst, s->d_unit, bytes, hipMemcpyDeviceToDevice, s->stream));
+  CLV_HIP(hipMemcpyAsync(dst, s->d_unit, sizeof(double) * unit_count(s->g), hipMemcpyDeviceToDevice, s->stream));
   return CLV_OK;
 }
 
@@ -979,7 +1025,7 @@ int clv_p2p_info(const clv_sampler* s, int64_t* out) {
   out[4] = s->p2p_capable ? 1 : 0;
   out[1] = s->p2p_ready ? 1 : 0;
   out[2] = s->d_mail ? (int64_t)sizeof(double) * 2 * s->g.world_size * s->g.n_chains * s->g.stride * s->g.units_per_rank : 0;
-  out[3] = (int64_t)(uintptr_t)s->d_mail;
+  out[3] = (int64_t)(uintptr_t)s->d_mail.p;
   out[5] = s->d_mail ? s->mail_kind : -1;
   return CLV_OK;
 }
@@ -999,16 +1045,10 @@ int clv_p2p_connect(clv_sampler* s, const void* handles, const uint64_t* ptrs) {
   if (!s->p2p_capable && !s->fx_capable) return fail(CLV_ESTATE, "no peer exchange for this sampler (world size 1 or replay mode)");
   CLV_HIP(hipSetDevice(s->device));
   CLV_HIP(hipStreamSynchronize(s->stream));
-  if (s->p2p_ready || !s->ipc_opened.empty()) {  // reconnect (after a failed step): drop the old mappings
-    s->p2p_ready = false;
-    for (void* p : s->ipc_opened) (void)hipIpcCloseMemHandle(p);
-    s->ipc_opened.clear();
-  }
-  {  // every slot of this rank's mail empty (a failed step may have left units of any rank there);
-     // the caller synchronises the ranks after connecting, before any rank runs
-    const int64_t nm = mail_slots(s->g.world_size, s->g.n_chains, s->g.stride, s->g.units_per_rank) + MAIL_TAIL;
-    CLV_HIP(hipMemsetAsync(s->d_mail, 0xFF, sizeof(double) * nm, s->stream));
-  }
+  forget_peers(s);  // reconnect (after a failed step): drop the old mappings
+  // every slot of this rank's mail empty (a failed step may have left units of any rank there);
+  // the caller synchronises the ranks after connecting, before any rank runs
+  CLV_HIP(fill_mail(s));
   const int W = s->g.world_size, r = s->cfg.rank;
   std::vector<double*> peers(W, nullptr);
   for (int q = 0; q < W; ++q) {
@@ -1047,9 +1087,7 @@ int clv_p2p_disconnect(clv_sampler* s) {
   if (!s) return fail(CLV_EINVAL, "null sampler");
   CLV_HIP(hipSetDevice(s->device));
   CLV_HIP(hipStreamSynchronize(s->stream));
-  s->p2p_ready = false;
-  for (void* p : s->ipc_opened) (void)hipIpcCloseMemHandle(p);
-  s->ipc_opened.clear();
+  forget_peers(s);
   if (s->d_peers) CLV_HIP(hipMemset(s->d_peers, 0, sizeof(double*) * s->g.world_size));
   return CLV_OK;
 }
@@ -1057,19 +1095,12 @@ int clv_p2p_disconnect(clv_sampler* s) {
 int clv_set_wait_timeout(clv_sampler* s, double ms) {
   if (!s || !(ms >= 1.0) || ms > 3.6e6) return fail(CLV_EINVAL, "wait timeout must be in [1 ms, 1 h]");
   s->wait_ticks = (uint64_t)(ms * 1e5);  // s_memrealtime: 100 MHz
-  if (s->graph_exec) {  // captured with the previous bound (kernel arguments)
-    CLV_HIP(hipGraphExecDestroy(s->graph_exec));
-    s->graph_exec = nullptr;
-  }
-  return CLV_OK;
+  return drop_graph(s);  // captured with the previous bound (kernel arguments)
 }
 
 int clv_set_stream(clv_sampler* s, uint64_t stream) {
   if (!s || !stream) return fail(CLV_EINVAL, "bad arguments");
-  if (s->graph_exec) {
-    CLV_HIP(hipGraphExecDestroy(s->graph_exec));  // captured on the previous stream
-    s->graph_exec = nullptr;
-  }
+  if (int rc = drop_graph(s)) return rc;  // captured on the previous stream
   s->stream = (hipStream_t)(uintptr_t)stream;  // caller-owned from now on
   return CLV_OK;
 }
@@ -1082,6 +1113,17 @@ int clv_note_sweeps(clv_sampler* s, int64_t n) {
 }
 
 }  // extern "C"
+
+// What an aborted persistent launch, an aborted fused exchange and clv_rollback share of "back to before
+// the launch" (lam / mu / hyper come back untouched, copied, swapped): Ctrl at s->sweeps_done, the saved sums.
+static int rewind_ctrl_and_sums(clv_sampler* s) {
+  Ctrl c{};
+  c.cur = s->sweeps_done;
+  CLV_HIP(hipMemcpy(s->d_ctrl, &c, sizeof(Ctrl), hipMemcpyHostToDevice));
+  if (s->d_sums_prev)
+    CLV_HIP(hipMemcpy(s->d_sums, s->d_sums_prev, sizeof(double) * sums_count(s->g), hipMemcpyDeviceToDevice));
+  return CLV_OK;
+}
 
 // Persistent path: one launch of persist_kernel for all n sweeps (see kernels.hip), in two halves
 // so that a group of shards in one process (group.hip) can have every shard's launch in flight
@@ -1098,13 +1140,12 @@ int clv::persist_launch(clv_sampler* s, int64_t n_sweeps) {
   if (n_sweeps == 0) return CLV_OK;
   if (s->slots_dirty) {  // a completed launch leaves every hand-off slot empty; else fill them
     // every hand-off slot empty (all-ones bytes: the sentinel NaN)
-    CLV_HIP(hipMemsetAsync(s->d_hyp2, 0xFF, sizeof(double) * 2 * g.n_chains * HS, s->stream));
-    CLV_HIP(hipMemsetAsync(s->d_pblock, 0xFF, sizeof(double) * g.n_chains * split_records(g.nb_local) * g.stride, s->stream));
+    CLV_HIP(hipMemsetAsync(s->d_hyp2, 0xFF, sizeof(double) * handoff_count(g), s->stream));
+    CLV_HIP(hipMemsetAsync(s->d_pblock, 0xFF, sizeof(double) * pblock_count(g), s->stream));
     s->slots_dirty = false;
   }
-  const size_t sums_bytes = sizeof(double) * (size_t)g.n_chains * CLV_N_SUM_STATS * g.n;
   if (s->d_sums_prev)  // an aborted (or rolled-back) launch restores the running sums from here
-    CLV_HIP(hipMemcpyAsync(s->d_sums_prev, s->d_sums, sums_bytes, hipMemcpyDeviceToDevice, s->stream));
+    CLV_HIP(hipMemcpyAsync(s->d_sums_prev, s->d_sums, sizeof(double) * sums_count(g), hipMemcpyDeviceToDevice, s->stream));
   SweepArgs a = sweep_args(s, 0, 1);
   const int64_t stride_c = (int64_t)g.n_chains * g.stride;
   a.pend_in = s->pend ? s->d_pend + s->pend_buf * stride_c : nullptr;
@@ -1168,11 +1209,7 @@ int clv::persist_wait(clv_sampler* s) {
     // the carried state was written to the *_alt buffers only: lam / mu / hyper still hold the
     // state this launch started from; restore the counters, flags and running sums
     *s->h_abort = 0;
-    Ctrl c{};
-    c.cur = s->sweeps_done;
-    CLV_HIP(hipMemcpy(s->d_ctrl, &c, sizeof(Ctrl), hipMemcpyHostToDevice));
-    const size_t sums_bytes = sizeof(double) * (size_t)g.n_chains * CLV_N_SUM_STATS * g.n;
-    if (s->d_sums_prev) CLV_HIP(hipMemcpy(s->d_sums, s->d_sums_prev, sums_bytes, hipMemcpyDeviceToDevice));
+    if (int rc = rewind_ctrl_and_sums(s)) return rc;
     s->slots_dirty = true;
     if (g.world_size > 1) s->p2p_ready = false;  // mail slots are in an unknown state now
     std::string diag = take_wait_diag(s);
@@ -1189,8 +1226,8 @@ int clv::persist_wait(clv_sampler* s) {
                                           : "persistent sweep kernel: a workgroup timed out waiting for its chain (not all "
                                             "resident?); state unchanged") + diag);
   }
-  std::swap(s->d_lam, s->d_lam_alt);
-  std::swap(s->d_mu, s->d_mu_alt);
+  s->d_lam.swap(s->d_lam_alt);
+  s->d_mu.swap(s->d_mu_alt);
   s->rb_pend = s->pend;  // (rollback: the hyper state this launch started from)
   s->rb_pend_buf = s->pend_buf;
   s->rb_hyper_swaps = 0;
@@ -1198,14 +1235,11 @@ int clv::persist_wait(clv_sampler* s) {
     s->pend = true;
     s->pend_buf ^= 1;
   } else {
-    std::swap(s->d_hyper, s->d_hyper_alt);
+    s->d_hyper.swap(s->d_hyper_alt);
     s->rb_hyper_swaps = 1;
     s->pend = false;
   }
-  if (s->graph_exec) {  // captured with the previous state pointers
-    CLV_HIP(hipGraphExecDestroy(s->graph_exec));
-    s->graph_exec = nullptr;
-  }
+  if (int rc = drop_graph(s)) return rc;  // captured with the previous state pointers
   s->sweeps_done += n_sweeps;
   s->last_persist_n = n_sweeps;
   return CLV_OK;
@@ -1223,14 +1257,10 @@ int clv::persist_flush(clv_sampler* s) {
   a.pend_out = nullptr;
   CLV_HIP(launch_persist_flush(a, s->sweeps_done + 1, s->stream));
   CLV_HIP(hipStreamSynchronize(s->stream));
-  std::swap(s->d_hyper, s->d_hyper_alt);
+  s->d_hyper.swap(s->d_hyper_alt);
   s->rb_hyper_swaps++;
   s->pend = false;
-  if (s->graph_exec) {
-    CLV_HIP(hipGraphExecDestroy(s->graph_exec));
-    s->graph_exec = nullptr;
-  }
-  return CLV_OK;
+  return drop_graph(s);
 }
 
 namespace {
@@ -1289,13 +1319,12 @@ int run_fused_exchange(clv_sampler* s, int64_t n_sweeps) {
   s->last_persist_n = 0;
   if (n_sweeps == 0) return CLV_OK;
   const Geometry& g = s->g;
-  const size_t nl = sizeof(double) * (size_t)g.n_chains * std::max<int64_t>(g.n, 1);
-  const size_t sums_bytes = sizeof(double) * (size_t)g.n_chains * CLV_N_SUM_STATS * g.n;
+  const size_t nl = sizeof(double) * state_count(g), nh = sizeof(double) * hyper_count(g);
   CLV_HIP(hipMemcpyAsync(s->d_lam_alt, s->d_lam, nl, hipMemcpyDeviceToDevice, s->stream));
   CLV_HIP(hipMemcpyAsync(s->d_mu_alt, s->d_mu, nl, hipMemcpyDeviceToDevice, s->stream));
-  CLV_HIP(hipMemcpyAsync(s->d_hyper_alt, s->d_hyper, sizeof(double) * g.n_chains * HS, hipMemcpyDeviceToDevice,
-                         s->stream));
-  if (s->d_sums_prev) CLV_HIP(hipMemcpyAsync(s->d_sums_prev, s->d_sums, sums_bytes, hipMemcpyDeviceToDevice, s->stream));
+  CLV_HIP(hipMemcpyAsync(s->d_hyper_alt, s->d_hyper, nh, hipMemcpyDeviceToDevice, s->stream));
+  if (s->d_sums_prev)
+    CLV_HIP(hipMemcpyAsync(s->d_sums_prev, s->d_sums, sizeof(double) * sums_count(g), hipMemcpyDeviceToDevice, s->stream));
   const int64_t before = s->sweeps_done;
   const int rc = enqueue_fused_sweeps(s, n_sweeps);
   CLV_HIP(hipStreamSynchronize(s->stream));
@@ -1309,14 +1338,11 @@ int run_fused_exchange(clv_sampler* s, int64_t n_sweeps) {
   // back to the state before the call (copies: a captured graph keeps the buffer addresses)
   CLV_HIP(hipMemcpy(s->d_lam, s->d_lam_alt, nl, hipMemcpyDeviceToDevice));
   CLV_HIP(hipMemcpy(s->d_mu, s->d_mu_alt, nl, hipMemcpyDeviceToDevice));
-  CLV_HIP(hipMemcpy(s->d_hyper, s->d_hyper_alt, sizeof(double) * g.n_chains * HS, hipMemcpyDeviceToDevice));
-  if (s->d_sums_prev) CLV_HIP(hipMemcpy(s->d_sums, s->d_sums_prev, sums_bytes, hipMemcpyDeviceToDevice));
+  CLV_HIP(hipMemcpy(s->d_hyper, s->d_hyper_alt, nh, hipMemcpyDeviceToDevice));
   *s->h_abort = 0;
   s->sweeps_done = before;
-  Ctrl c{};
-  c.cur = before;
-  CLV_HIP(hipMemcpy(s->d_ctrl, &c, sizeof(Ctrl), hipMemcpyHostToDevice));
-  CLV_HIP(hipMemset(s->d_arrive, 0, sizeof(uint32_t) * (g.n_chains + (int64_t)g.n_chains * g.units_per_rank)));
+  if (int rc2 = rewind_ctrl_and_sums(s)) return rc2;
+  CLV_HIP(hipMemset(s->d_arrive, 0, sizeof(uint32_t) * arrive_count(g)));
   s->p2p_ready = false;  // mail slots in an unknown state: clv_p2p_connect refills them
   if (rc) return rc;
   return fail(CLV_EHIP, "fused peer exchange: a wait timed out (a peer rank not running?); state unchanged" +
@@ -1404,7 +1430,7 @@ int clv_stream_draws(clv_sampler* s, double* level1) {
   s->ds_dest = level1;
   s->ds_next = 0;
   const Geometry& g = s->g;
-  stream_prefault(s->ds, s->device, level1, sizeof(double) * (size_t)g.n_chains * g.n_draws * g.n * (g.D + 2));
+  stream_prefault(s->ds, s->device, level1, sizeof(double) * level1_count(g));
   // draws of sweeps already run: the pool copies on the null stream, which does not order against
   // the sampler's non-blocking stream, so the sweeps enqueued there must have completed
   CLV_HIP(hipStreamSynchronize(s->stream));
@@ -1418,27 +1444,18 @@ int clv_rollback(clv_sampler* s) {
   if (s->last_persist_n <= 0) return fail(CLV_ESTATE, "nothing to roll back (the last call was not a completed persistent clv_run)");
   CLV_HIP(hipSetDevice(s->device));
   CLV_HIP(hipStreamSynchronize(s->stream));
-  std::swap(s->d_lam, s->d_lam_alt);
-  std::swap(s->d_mu, s->d_mu_alt);
+  s->d_lam.swap(s->d_lam_alt);
+  s->d_mu.swap(s->d_mu_alt);
   // the hyper state the launch started from: pending statistics (still in their buffer), or the
   // hyper buffer that was current then (in hyper_alt after an odd number of swaps since)
-  if (s->rb_hyper_swaps & 1) std::swap(s->d_hyper, s->d_hyper_alt);
+  if (s->rb_hyper_swaps & 1) s->d_hyper.swap(s->d_hyper_alt);
   s->pend = s->rb_pend;
   s->pend_buf = s->rb_pend_buf;
   s->rb_hyper_swaps = 0;
   s->sweeps_done -= s->last_persist_n;
   s->last_persist_n = 0;
-  Ctrl c{};
-  c.cur = s->sweeps_done;
-  CLV_HIP(hipMemcpy(s->d_ctrl, &c, sizeof(Ctrl), hipMemcpyHostToDevice));
-  if (s->d_sums_prev)
-    CLV_HIP(hipMemcpy(s->d_sums, s->d_sums_prev, sizeof(double) * (size_t)s->g.n_chains * CLV_N_SUM_STATS * s->g.n,
-                      hipMemcpyDeviceToDevice));
-  if (s->graph_exec) {
-    CLV_HIP(hipGraphExecDestroy(s->graph_exec));
-    s->graph_exec = nullptr;
-  }
-  return CLV_OK;
+  if (int rc = rewind_ctrl_and_sums(s)) return rc;
+  return drop_graph(s);
 }
 
 int clv_read_draws(clv_sampler* s, double* level1, double* level2, double* loglik) {
@@ -1458,7 +1475,7 @@ int clv_read_draws(clv_sampler* s, double* level1, double* level2, double* logli
       stream_enqueue(s);
       done = stream_wait(s->ds);
       // (draws beyond the stored ones are never written: zeros, as the device buffer holds)
-      const int64_t k = stored_count(s, s->sweeps_done);
+      const int64_t k = stored_draws(s);
       if (done && k < g.n_draws)
         for (size_t c = 0; c < C; ++c)
           std::memset(level1 + ((int64_t)c * g.n_draws + k) * g.n * (g.D + 2), 0,
@@ -1467,14 +1484,14 @@ int clv_read_draws(clv_sampler* s, double* level1, double* level2, double* logli
       stream_wait(s->ds);
     }
     if (s->d_level1 && !done) {
-      CLV_HIP(hipMemcpy(level1, s->d_level1, sizeof(double) * C * g.n_draws * g.n * (g.D + 2), hipMemcpyDeviceToHost));
+      CLV_HIP(s->d_level1.download(level1, level1_count(g)));
       if (s->ds && s->ds_dest == level1) stream_clear_failed(s->ds);  // the full copy repaired it
     }
   }
   if (level2 && s->d_level2)
-    CLV_HIP(hipMemcpy(level2, s->d_level2, sizeof(double) * C * g.n_draws * g.l2w, hipMemcpyDeviceToHost));
+    CLV_HIP(s->d_level2.download(level2, loglik_count(g) * g.l2w));
   if (loglik && s->d_loglik)
-    CLV_HIP(hipMemcpy(loglik, s->d_loglik, sizeof(double) * C * g.n_draws, hipMemcpyDeviceToHost));
+    CLV_HIP(s->d_loglik.download(loglik, loglik_count(g)));
   return CLV_OK;
 }
 
@@ -1486,7 +1503,7 @@ int clv_read_summary(clv_sampler* s, double* sums, int64_t* n_stored) {
   if (n_stored) *n_stored = stored_draws(s);
   if (sums) {
     if (!s->d_sums) return fail(CLV_ESTATE, "summaries need draw_sink == CLV_SINK_SUMMARY (or _PCT)");
-    CLV_HIP(hipMemcpy(sums, s->d_sums, sizeof(double) * g.n_chains * CLV_N_SUM_STATS * g.n, hipMemcpyDeviceToHost));
+    CLV_HIP(s->d_sums.download(sums, sums_count(g)));
   }
   return CLV_OK;
 }
@@ -1608,14 +1625,13 @@ int clv_debug_host_times(const clv_sampler* s, int64_t* out) {
 
 int clv_debug_philox(uint32_t k0, uint32_t k1, const uint32_t* ctr, int64_t n, uint32_t* out) {
   if (!ctr || !out || n < 0) return fail(CLV_EINVAL, "bad arguments");
-  uint32_t *dc = nullptr, *dout = nullptr;
-  CLV_HIP(dalloc(&dc, 4 * std::max<int64_t>(n, 1)));
-  CLV_HIP(dalloc(&dout, 4 * std::max<int64_t>(n, 1)));
+  DevPtr<uint32_t> dc, dout;
+  const size_t words = 4 * std::max<int64_t>(n, 1);
+  CLV_HIP(dc.alloc(words));
+  CLV_HIP(dout.alloc(words));
   CLV_HIP(hipMemcpy(dc, ctr, 16 * n, hipMemcpyHostToDevice));
   CLV_HIP(launch_debug_philox(k0, k1, dc, n, dout, nullptr));
-  CLV_HIP(hipMemcpy(out, dout, 16 * n, hipMemcpyDeviceToHost));
-  CLV_HIP(hipFree(dc));
-  CLV_HIP(hipFree(dout));
+  CLV_HIP(dout.download(out, 4 * n));
   return CLV_OK;
 }
 
@@ -1623,41 +1639,32 @@ int clv_debug_variates(uint64_t seed, int32_t chain, uint32_t sweep, int64_t n, 
                        float* ua, double* uz, double* ut, double* ea, double* ez, float* l2u) {
   if (n < 1 || S < 0) return fail(CLV_EINVAL, "bad arguments");
   const int64_t nS = std::max<int64_t>(n * S, 1);
-  float *dtl, *dtm, *dua, *dl2u;
-  double *duz, *dut, *dea, *dez;
-  CLV_HIP(dalloc(&dtl, nS));
-  CLV_HIP(dalloc(&dtm, nS));
-  CLV_HIP(dalloc(&dua, nS));
-  CLV_HIP(dalloc(&dl2u, nS));
-  CLV_HIP(dalloc(&duz, n));
-  CLV_HIP(dalloc(&dut, n));
-  CLV_HIP(dalloc(&dea, n));
-  CLV_HIP(dalloc(&dez, n));
+  DevPtr<float> dtl, dtm, dua, dl2u;
+  DevPtr<double> duz, dut, dea, dez;
+  for (DevPtr<float>* b : {&dtl, &dtm, &dua, &dl2u}) CLV_HIP(b->alloc(nS));
+  for (DevPtr<double>* b : {&duz, &dut, &dea, &dez}) CLV_HIP(b->alloc(n));
   CLV_HIP(launch_debug_variates(seed, chain, sweep, n, S, dtl, dtm, dua, dl2u, duz, dut, dea, dez, nullptr));
   if (S > 0) {
-    CLV_HIP(hipMemcpy(tl, dtl, sizeof(float) * n * S, hipMemcpyDeviceToHost));
-    CLV_HIP(hipMemcpy(tm, dtm, sizeof(float) * n * S, hipMemcpyDeviceToHost));
-    CLV_HIP(hipMemcpy(ua, dua, sizeof(float) * n * S, hipMemcpyDeviceToHost));
-    if (l2u) CLV_HIP(hipMemcpy(l2u, dl2u, sizeof(float) * n * S, hipMemcpyDeviceToHost));
+    CLV_HIP(dtl.download(tl, n * S));
+    CLV_HIP(dtm.download(tm, n * S));
+    CLV_HIP(dua.download(ua, n * S));
+    if (l2u) CLV_HIP(dl2u.download(l2u, n * S));
   }
-  CLV_HIP(hipMemcpy(uz, duz, sizeof(double) * n, hipMemcpyDeviceToHost));
-  CLV_HIP(hipMemcpy(ut, dut, sizeof(double) * n, hipMemcpyDeviceToHost));
-  CLV_HIP(hipMemcpy(ea, dea, sizeof(double) * n, hipMemcpyDeviceToHost));
-  CLV_HIP(hipMemcpy(ez, dez, sizeof(double) * n, hipMemcpyDeviceToHost));
-  for (void* p : {(void*)dtl, (void*)dtm, (void*)dua, (void*)dl2u, (void*)duz, (void*)dut, (void*)dea, (void*)dez})
-    CLV_HIP(hipFree(p));
+  CLV_HIP(duz.download(uz, n));
+  CLV_HIP(dut.download(ut, n));
+  CLV_HIP(dea.download(ea, n));
+  CLV_HIP(dez.download(ez, n));
   return CLV_OK;
 }
 
 int clv_debug_log2u_scan(uint64_t w_begin, uint64_t w_end, double* out) {
   if (!out || w_end > (1ull << 32) || w_begin >= w_end) return fail(CLV_EINVAL, "bad arguments");
   constexpr int NB = 4096;
-  double* dres = nullptr;
-  CLV_HIP(dalloc(&dres, 4 * NB));
-  CLV_HIP(launch_debug_log2u_scan(w_begin, w_end, NB, dres, nullptr));
   std::vector<double> r(4 * NB);
-  CLV_HIP(hipMemcpy(r.data(), dres, sizeof(double) * r.size(), hipMemcpyDeviceToHost));
-  CLV_HIP(hipFree(dres));
+  DevPtr<double> dres;
+  CLV_HIP(dres.alloc(r.size()));
+  CLV_HIP(launch_debug_log2u_scan(w_begin, w_end, NB, dres, nullptr));
+  CLV_HIP(dres.download(r.data(), r.size()));
   double mu = 0.0, ma = 0.0, wu = 0.0, mu_far = 0.0;
   for (int b = 0; b < NB; ++b) {
     if (r[4 * b] > mu) {
@@ -1676,69 +1683,54 @@ int clv_debug_log2u_scan(uint64_t w_begin, uint64_t w_end, double* out) {
 
 int clv_debug_t3(const uint32_t* words, int64_t n, int32_t packed, float* tl, float* tm) {
   if (!words || !tl || !tm || n < 1 || (packed != 0 && packed != 1)) return fail(CLV_EINVAL, "bad arguments");
-  uint32_t* dw = nullptr;
-  float *dl = nullptr, *dm = nullptr;
-  CLV_HIP(dalloc(&dw, 3 * n));
-  CLV_HIP(dalloc(&dl, n));
-  CLV_HIP(dalloc(&dm, n));
-  CLV_HIP(hipMemcpy(dw, words, 12 * n, hipMemcpyHostToDevice));
+  DevPtr<uint32_t> dw;
+  DevPtr<float> dl, dm;
+  CLV_HIP(dw.upload(words, 3 * n));
+  CLV_HIP(dl.alloc(n));
+  CLV_HIP(dm.alloc(n));
   CLV_HIP(launch_debug_t3(dw, n, packed, dl, dm, nullptr));
-  CLV_HIP(hipMemcpy(tl, dl, sizeof(float) * n, hipMemcpyDeviceToHost));
-  CLV_HIP(hipMemcpy(tm, dm, sizeof(float) * n, hipMemcpyDeviceToHost));
-  for (void* p : {(void*)dw, (void*)dl, (void*)dm}) CLV_HIP(hipFree(p));
+  CLV_HIP(dl.download(tl, n));
+  CLV_HIP(dm.download(tm, n));
   return CLV_OK;
 }
 
 int clv_debug_level2(int32_t D, int32_t K, const clv_prior* prior, const double* xty, const double* yty,
                      const double* iwn, const double* chi2, const double* z, double* beta, double* sigma) {
   if ((D != 2 && D != 3) || K < 1 || K > CLV_MAX_K || !prior) return fail(CLV_EINVAL, "bad arguments");
-  std::vector<double> pr(PRIOR_DOUBLES, 0.0);
-  for (int i = 0; i < K * K; ++i) {
-    pr[i] = prior->V[i];
-    pr[81 + i] = prior->chol_V[i];
-  }
-  for (int i = 0; i < K * D; ++i) pr[162 + i] = prior->A0B0[i];
-  for (int i = 0; i < D * D; ++i) pr[189 + i] = prior->S0_B0A0B0[i];
+  const std::vector<double> pr = pack_prior(prior, D, K);
   std::vector<double> in(K * D + D * D + 6 + D * K, 0.0);
   for (int i = 0; i < K * D; ++i) in[i] = xty[i];
   for (int i = 0; i < D * D; ++i) in[K * D + i] = yty[i];
   for (int i = 0; i < D * (D - 1) / 2; ++i) in[K * D + D * D + i] = iwn[i];
   for (int i = 0; i < D; ++i) in[K * D + D * D + 3 + i] = chi2[i];
   for (int i = 0; i < D * K; ++i) in[K * D + D * D + 6 + i] = z[i];
-  double *dpr, *din, *dout;
-  CLV_HIP(dalloc(&dpr, pr.size()));
-  CLV_HIP(dalloc(&din, in.size()));
-  CLV_HIP(dalloc(&dout, K * D + D * D));
-  CLV_HIP(hipMemcpy(dpr, pr.data(), sizeof(double) * pr.size(), hipMemcpyHostToDevice));
-  CLV_HIP(hipMemcpy(din, in.data(), sizeof(double) * in.size(), hipMemcpyHostToDevice));
-  CLV_HIP(launch_debug_level2(D, K, dpr, din, dout, nullptr));
   std::vector<double> o(K * D + D * D);
-  CLV_HIP(hipMemcpy(o.data(), dout, sizeof(double) * o.size(), hipMemcpyDeviceToHost));
+  DevPtr<double> dpr, din, dout;
+  CLV_HIP(dpr.upload(pr.data(), pr.size()));
+  CLV_HIP(din.upload(in.data(), in.size()));
+  CLV_HIP(dout.alloc(o.size()));
+  CLV_HIP(launch_debug_level2(D, K, dpr, din, dout, nullptr));
+  CLV_HIP(dout.download(o.data(), o.size()));
   for (int i = 0; i < K * D; ++i) beta[i] = o[i];
   for (int i = 0; i < D * D; ++i) sigma[i] = o[K * D + i];
-  CLV_HIP(hipFree(dpr));
-  CLV_HIP(hipFree(din));
-  CLV_HIP(hipFree(dout));
   return CLV_OK;
 }
 
 int clv_debug_hyper_variates(uint64_t seed, int32_t chain, uint32_t sweep, double df, int64_t n, double* chi2,
                              double* normals) {
   if (n < 1 || df < 2.0) return fail(CLV_EINVAL, "bad arguments");
-  double *dc, *dn;
-  CLV_HIP(dalloc(&dc, n));
-  CLV_HIP(dalloc(&dn, n));
+  DevPtr<double> dc, dn;
+  CLV_HIP(dc.alloc(n));
+  CLV_HIP(dn.alloc(n));
   CLV_HIP(launch_debug_hyper_variates(seed, chain, sweep, df, n, dc, dn, nullptr));
-  CLV_HIP(hipMemcpy(chi2, dc, sizeof(double) * n, hipMemcpyDeviceToHost));
-  CLV_HIP(hipMemcpy(normals, dn, sizeof(double) * n, hipMemcpyDeviceToHost));
-  CLV_HIP(hipFree(dc));
-  CLV_HIP(hipFree(dn));
+  CLV_HIP(dc.download(chi2, n));
+  CLV_HIP(dn.download(normals, n));
   return CLV_OK;
 }
 
 int clv_debug_persist_choice(int32_t D, int32_t K, int32_t n_chains, int64_t grid_wgs, int32_t blocks_per_cu,
                              int32_t n_cu) {
-  return persist_grid_fits(grid_wgs, blocks_per_cu, n_cu) && persist_worth(D, K, n_chains, grid_wgs, n_cu) ? 1 : 0;
+  return persist_grid_chosen(D, K, n_chains, grid_wgs, blocks_per_cu, n_cu, false) ? 1 : 0;
 }
 
 int clv_debug_persist_fits(int64_t grid_wgs, int32_t blocks_per_cu, int32_t n_cu) {
@@ -1750,7 +1742,36 @@ int clv_debug_split_fits(int32_t n_chains, int32_t nb, int32_t blocks_per_cu, in
 }
 
 int clv_debug_split_choice(int32_t n_chains, int32_t nb, int32_t blocks_per_cu, int32_t n_cu) {
-  return persist_split_fits(n_chains, nb, blocks_per_cu, n_cu) && persist_split_pays(n_chains, nb, n_cu) ? 1 : 0;
+  return split_chosen(n_chains, nb, blocks_per_cu, n_cu, false) ? 1 : 0;
+}
+
+int clv_debug_sweep_plan(const int64_t* in, int32_t* out) {
+  if (!in || !out) return fail(CLV_EINVAL, "null argument");
+  Geometry g{};
+  g.D = (int)in[0];
+  g.K = (int)in[1];
+  g.S = (int)in[2];
+  g.n_chains = (int)in[3];
+  g.nb_local = (int)in[4];
+  g.blocks_per_unit = (int)in[5];
+  g.n_units_global = in[6];
+  g.world_size = (int)in[7];
+  g.stride = g.K * g.D + g.D * (g.D + 1) / 2 + 1;
+  SweepResources r;
+  r.n_cu = (int)in[9];
+  r.block = Instance{(int)in[10], in[11]};
+  r.split = Instance{(int)in[12], in[13]};
+  r.relay = Instance{(int)in[14], in[15]};
+  SweepEnv e;
+  e.persistent = (int)in[16];
+  e.layout = (int)in[17];
+  e.relay = (int)in[18];
+  e.defer = in[19] != 0;
+  const SweepPlan p = plan_sweep(g, in[8] != 0, r, e);
+  const int32_t o[8] = {p.persistent, p.split, p.relay_steps, p.p2p_capable, p.p2p_persist_fits, p.fx_capable,
+                        p.defer, (p.need_split ? 1 : 0) | (p.need_relay ? 2 : 0)};
+  std::copy(o, o + 8, out);
+  return p.error ? fail(CLV_EINVAL, p.error) : CLV_OK;
 }
 
 int clv_debug_split_relay_plan(int32_t S, int32_t R, int32_t* out) {
@@ -1820,50 +1841,34 @@ int clv_debug_mh_step(int64_t n, const int32_t* x, const uint8_t* z, const doubl
                       const double* scale2, const float* log_u, double* out) {
   if (!x || !z || !T_cal || !tau || !mean || !prec3 || !cur_pt || !t3 || !scale2 || !log_u || !out || n < 1)
     return fail(CLV_EINVAL, "bad arguments");
-  int32_t *dx;
-  uint8_t* dz;
-  double *dT, *dtau, *dm, *dp, *dc, *ds, *dout;
-  float *dt3, *dlu;
-  CLV_HIP(hipMalloc(&dx, sizeof(int32_t) * n));
-  CLV_HIP(hipMalloc(&dz, n));
-  CLV_HIP(dalloc(&dT, n));
-  CLV_HIP(dalloc(&dtau, n));
-  CLV_HIP(dalloc(&dm, 2 * n));
-  CLV_HIP(dalloc(&dp, 3));
-  CLV_HIP(dalloc(&dc, 2 * n));
-  CLV_HIP(dalloc(&ds, 2));
-  CLV_HIP(dalloc(&dout, 7 * n));
-  CLV_HIP(hipMalloc(&dt3, sizeof(float) * 2 * n));
-  CLV_HIP(hipMalloc(&dlu, sizeof(float) * n));
-  CLV_HIP(hipMemcpy(dx, x, sizeof(int32_t) * n, hipMemcpyHostToDevice));
-  CLV_HIP(hipMemcpy(dz, z, n, hipMemcpyHostToDevice));
-  CLV_HIP(hipMemcpy(dT, T_cal, sizeof(double) * n, hipMemcpyHostToDevice));
-  CLV_HIP(hipMemcpy(dtau, tau, sizeof(double) * n, hipMemcpyHostToDevice));
-  CLV_HIP(hipMemcpy(dm, mean, sizeof(double) * 2 * n, hipMemcpyHostToDevice));
-  CLV_HIP(hipMemcpy(dp, prec3, sizeof(double) * 3, hipMemcpyHostToDevice));
-  CLV_HIP(hipMemcpy(dc, cur_pt, sizeof(double) * 2 * n, hipMemcpyHostToDevice));
-  CLV_HIP(hipMemcpy(ds, scale2, sizeof(double) * 2, hipMemcpyHostToDevice));
-  CLV_HIP(hipMemcpy(dt3, t3, sizeof(float) * 2 * n, hipMemcpyHostToDevice));
-  CLV_HIP(hipMemcpy(dlu, log_u, sizeof(float) * n, hipMemcpyHostToDevice));
+  DevPtr<int32_t> dx;
+  DevPtr<uint8_t> dz;
+  DevPtr<double> dT, dtau, dm, dp, dc, ds, dout;
+  DevPtr<float> dt3, dlu;
+  CLV_HIP(dx.upload(x, n));
+  CLV_HIP(dz.upload(z, n));
+  CLV_HIP(dT.upload(T_cal, n));
+  CLV_HIP(dtau.upload(tau, n));
+  CLV_HIP(dm.upload(mean, 2 * n));
+  CLV_HIP(dp.upload(prec3, 3));
+  CLV_HIP(dc.upload(cur_pt, 2 * n));
+  CLV_HIP(ds.upload(scale2, 2));
+  CLV_HIP(dt3.upload(t3, 2 * n));
+  CLV_HIP(dlu.upload(log_u, n));
+  CLV_HIP(dout.alloc(7 * n));
   CLV_HIP(launch_debug_mh(dx, dz, dT, dtau, dm, dp, dc, dt3, ds, dlu, n, dout, nullptr));
-  CLV_HIP(hipMemcpy(out, dout, sizeof(double) * 7 * n, hipMemcpyDeviceToHost));
-  for (void* p : {(void*)dx, (void*)dz, (void*)dT, (void*)dtau, (void*)dm, (void*)dp, (void*)dc, (void*)ds,
-                  (void*)dout, (void*)dt3, (void*)dlu})
-    CLV_HIP(hipFree(p));
+  CLV_HIP(dout.download(out, 7 * n));
   return CLV_OK;
 }
 
 }  // extern "C"
 static int debug_fast_fn(const double* x, int64_t n, double* out, bool log_fn) {
   if (!x || !out || n < 1) return fail(CLV_EINVAL, "bad arguments");
-  double *dx, *dout;
-  CLV_HIP(dalloc(&dx, n));
-  CLV_HIP(dalloc(&dout, n));
-  CLV_HIP(hipMemcpy(dx, x, sizeof(double) * n, hipMemcpyHostToDevice));
+  DevPtr<double> dx, dout;
+  CLV_HIP(dx.upload(x, n));
+  CLV_HIP(dout.alloc(n));
   CLV_HIP(launch_debug_exp(dx, n, dout, nullptr, log_fn));
-  CLV_HIP(hipMemcpy(out, dout, sizeof(double) * n, hipMemcpyDeviceToHost));
-  CLV_HIP(hipFree(dx));
-  CLV_HIP(hipFree(dout));
+  CLV_HIP(dout.download(out, n));
   return CLV_OK;
 }
 extern "C" {

@@ -203,7 +203,7 @@ int clv_group_create(clv_sampler* const* shards, int32_t n, int32_t exchange, cl
     return cleanup(fail(CLV_ESTATE, "peer exchange not possible (a shard's grid does not fit at once, or no peer access)"));
   if (p2p) {
     std::vector<uint64_t> ptrs(n);
-    for (int r = 0; r < n; ++r) ptrs[r] = (uint64_t)(uintptr_t)shards[r]->d_mail;
+    for (int r = 0; r < n; ++r) ptrs[r] = (uint64_t)(uintptr_t)shards[r]->d_mail.p;
     for (int r = 0; r < n; ++r) {
       int rc = clv_p2p_connect(shards[r], nullptr, ptrs.data());
       if (rc) return cleanup(rc);  // (destroy disconnects the shards connected so far)

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
 #include <condition_variable>
 #include <mutex>
@@ -24,15 +25,6 @@ int persist_flush(clv_sampler* s);  // the deferred level-2 draw, if one is pend
 // A persistent grid of grid_wgs workgroups fits at once (with a residency margin) on n_cu CUs
 // admitting blocks_per_cu of its workgroups each (capi.hip).
 bool persist_grid_fits(int64_t grid_wgs, int blocks_per_cu, int n_cu);
-bool persist_worth(int D, int K, int n_chains, int64_t grid_wgs, int n_cu);
-// The split layout (kernels.hip persist_kernel_split): one workgroup per CU, so a chain of nb
-// blocks takes split_wgs(nb) + 1 CUs.  persist_split_fits: nb within the layout's range and the
-// whole grid resident (its own rule, capi.hip); persist_split_pays: the block layout would put two
-// workgroups on some CU.  persist_split_layout: per physical workgroup the chain and the chain's
-// workgroup index (chain << 16 | p; p = split_wgs(nb): the level-2 workgroup; first wave row 6 p).
-bool persist_split_fits(int n_chains, int nb, int blocks_per_cu, int n_cu);
-bool persist_split_pays(int n_chains, int nb, int n_cu);
-std::vector<int32_t> persist_split_layout(int n_chains, int nb);
 
 // Level-1 draws streamed to a host buffer during the run (drawstream.hip): the pieces a sampler has
 // in flight in the process-wide copy pool, and whether any failed.
@@ -73,29 +65,40 @@ hipError_t launch_batch_fit(int D, int K, const SweepArgs* fits, const int2* wg_
                             hipEvent_t e1 = nullptr);
 hipError_t batch_fit_resources(int D, int K, int* vgprs, size_t* scratch_bytes, int* blocks_per_cu);
 
+// Owning device allocation, freed by hipFree on the device current at destruction: the sampler handle's
+// members, the test hooks' locals and (DevBuf, untyped) the analysis entry points' buffers.  Reads as its T*
+// (A.x = s->d_x, if (s->d_level1), s->d_arrive + k).  A buffer's element count is written once, at its alloc / upload.
 template <class T>
-hipError_t dalloc(T** p, size_t count) {
-  *p = nullptr;
-  if (count == 0) return hipSuccess;
-  return hipMalloc((void**)p, count * sizeof(T));
-}
-
-// Owning device allocation (freed on scope exit) and a scoped device switch, for the host-side
-// orchestration of the analysis / data-preparation entry points.
-struct DevBuf {
-  void* p = nullptr;
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  ~DevBuf() {
+struct DevPtr {
+  T* p = nullptr;
+  DevPtr() = default;
+  DevPtr(const DevPtr&) = delete;
+  DevPtr& operator=(const DevPtr&) = delete;
+  ~DevPtr() { reset(); }
+  operator T*() const { return p; }
+  template <class U> U* as() const { return (U*)p; }
+  void reset(T* adopt = nullptr) {  // adopt: memory of another allocator that hipFree releases
     if (p) (void)hipFree(p);
+    p = adopt;
   }
-  template <class T>
-  T* as() const {
-    return (T*)p;
+  void swap(DevPtr& o) { std::swap(p, o.p); }
+  hipError_t alloc(size_t count) {  // (count 0: null)
+    reset();
+    return count ? hipMalloc((void**)&p, count * sizeof(T)) : hipSuccess;
   }
+  hipError_t alloc(size_t count, int byte, hipStream_t st) {  // ... every byte set to `byte`, queued on st
+    const hipError_t e = alloc(count);
+    return e != hipSuccess || !count ? e : hipMemsetAsync(p, byte, count * sizeof(T), st);
+  }
+  hipError_t upload(const T* host, size_t count) {  // a device copy of host[count] (synchronous)
+    const hipError_t e = alloc(count);
+    return e != hipSuccess || !count ? e : hipMemcpy(p, host, count * sizeof(T), hipMemcpyHostToDevice);
+  }
+  hipError_t download(T* host, size_t count) const { return hipMemcpy(host, p, count * sizeof(T), hipMemcpyDeviceToHost); }
 };
+using DevBuf = DevPtr<void>;  // untyped: only p, as<U>() and reset() apply (the counted members need sizeof(T))
 
+// A scoped device switch, for the host-side orchestration of the analysis / data-preparation entry points.
 struct DeviceScope {
   int prev = -1;
   explicit DeviceScope(int dev) {
@@ -138,26 +141,28 @@ struct clv_sampler {
   int device = 0;
   hipStream_t stream = nullptr;
   hipStream_t own = nullptr;  // stream created by the sampler (destroyed with it)
-  bool own_stream = false;
 
-  int32_t* d_x = nullptr;
-  double *d_tx = nullptr, *d_T = nullptr, *d_cov = nullptr, *d_logs = nullptr;
-  double *d_lam = nullptr, *d_mu = nullptr, *d_hyper = nullptr;
-  double *d_block = nullptr, *d_unit = nullptr;
-  double* d_prior = nullptr;
-  clv::Ctrl* d_ctrl = nullptr;
-  uint32_t* d_arrive = nullptr;     // fused-tail arrival counters: [chain], then [chain][units_per_rank]
-  double* d_hyp2 = nullptr;         // persistent kernel: [2][chain][HS] hand-off slots
-  double* d_pblock = nullptr;       // persistent kernel: [chain][nb_local][stride] block-partial slots
+  // Every device allocation of the handle is a DevPtr member: destroying the handle frees it.
+  clv::DevPtr<int32_t> d_x;
+  clv::DevPtr<double> d_tx, d_T, d_cov, d_logs;
+  clv::DevPtr<double> d_lam, d_mu, d_hyper;
+  clv::DevPtr<double> d_block, d_unit_own;
+  double* d_unit = nullptr;         // the unit partials (a view): d_unit_own, or d_block when blocks_per_unit == 1
+  clv::DevPtr<double> d_prior;
+  clv::DevPtr<clv::Ctrl> d_ctrl;
+  clv::DevPtr<uint32_t> d_arrive;   // fused-tail arrival counters: [chain], then [chain][units_per_rank]
+  clv::DevPtr<double> d_hyp2;       // persistent kernel: [2][chain][HS] hand-off slots
+  clv::DevPtr<double> d_pblock;     // persistent kernel: [chain][nb_local][stride] block-partial slots
   // persistent kernel: the launch writes its carried state into the *_alt buffers; clv_run swaps
   // them in only when no wave aborted (an aborted launch leaves the state untouched), and
   // clv_rollback swaps them back (a sharded step that failed on another rank)
-  double *d_lam_alt = nullptr, *d_mu_alt = nullptr, *d_hyper_alt = nullptr;
-  double* d_sums_prev = nullptr;    // summary sink: the running sums before the last persistent launch
-  uint32_t* h_abort = nullptr;      // host-mapped copy of ctrl->abort (the kernel stores it on a timeout)
+  clv::DevPtr<double> d_lam_alt, d_mu_alt, d_hyper_alt;
+  clv::DevPtr<double> d_sums_prev;  // summary sink: the running sums before the last persistent launch
+  uint32_t* h_abort = nullptr;      // host-mapped copy of ctrl->abort (the kernel stores it on a timeout;
+                                    // hipHostMalloc: freed in clv_destroy)
   uint32_t* d_h_abort = nullptr;    // its device address
-  unsigned long long* d_diag = nullptr;  // wait-timeout record (kernels.hip report_wait), DIAG_WORDS
-  unsigned long long* d_clk = nullptr;   // shader-clock record [CLK_RING][2] (SweepArgs::clk)
+  clv::DevPtr<unsigned long long> d_diag;  // wait-timeout record (kernels.hip report_wait), DIAG_WORDS
+  clv::DevPtr<unsigned long long> d_clk;   // shader-clock record [CLK_RING][2] (SweepArgs::clk)
   int64_t clk_first = 0;            // first sweep of the last clv_run (clv_clock_ghz)
   uint64_t wait_ticks = 0;          // bound on every persistent-kernel wait (s_memrealtime ticks)
   bool slots_dirty = true;          // persistent hand-off slots need the sentinel fill (a completed
@@ -172,7 +177,7 @@ struct clv_sampler {
   bool defer = false;
   bool pend = false;                // the hyper state is the draw of d_pend[pend_buf], not d_hyper
   int pend_buf = 0;
-  double* d_pend = nullptr;
+  clv::DevPtr<double> d_pend;
   bool rb_pend = false;             // rollback: the pending state before the last persistent launch
   int rb_pend_buf = 0;
   int rb_hyper_swaps = 0;           // hyper / hyper_alt swaps since it (its hyper is in hyper_alt if odd)
@@ -181,23 +186,23 @@ struct clv_sampler {
   bool split = false;               // the persistent launch uses the split layout (persist_kernel_split)
   int relay_steps = 0;              // split layout: the relay instance's hand-over step (0: helper instance)
   bool split_reverted = false;      // a split launch aborted: block layout for the handle's lifetime
-  int32_t* d_wgmap_split = nullptr; // split grid: linear workgroup -> (chain << 16 | chain's workgroup)
+  clv::DevPtr<int32_t> d_wgmap_split;  // split grid: linear workgroup -> (chain << 16 | chain's workgroup)
   // world size > 1: persistent kernel with the peer (xGMI) exchange
   bool p2p_capable = false;         // the grid fits at once and the unit partials fit UMAIL
   bool p2p_persist_fits = false;    // (p2p_capable as chosen at create; clv_p2p_set_persistent may clear p2p_capable)
   bool fx_capable = false;          // fused peer exchange (launch-per-sweep, any shard size)
   bool p2p_ready = false;           // clv_p2p_connect done: clv_run runs persist_kernel
-  double* d_mail = nullptr;         // [2][world][chain][units_per_rank][stride]
+  clv::DevPtr<double> d_mail;       // [2][world][chain][units_per_rank][stride]
   int mail_kind = -1;               // the mail's memory: 0 uncached, 1 fine-grained, 2 plain device memory
-  double** d_peers = nullptr;       // [world] mail pointers (peers' opened IPC mappings, own d_mail)
-  int32_t* d_wgmap = nullptr;       // persistent grid: linear workgroup -> (chain << 16 | block)
+  clv::DevPtr<double*> d_peers;     // [world] mail pointers (peers' opened IPC mappings, own d_mail)
+  clv::DevPtr<int32_t> d_wgmap;     // persistent grid: linear workgroup -> (chain << 16 | block)
   std::vector<void*> ipc_opened;    // hipIpcOpenMemHandle mappings to close
-  double* d_hvar = nullptr;         // [chain][HV] precomputed hyper variates
-  unsigned long long* d_stamps = nullptr;  // CLV_STAMPS diagnostic build only
-  double *d_level1 = nullptr, *d_level2 = nullptr, *d_loglik = nullptr, *d_sums = nullptr;
-  float2* d_qstore = nullptr;       // CLV_SINK_SUMMARY_PCT: [chain][draw][n] (lambda, mu) float32
-  double* d_tape = nullptr;
-  double* d_bs = nullptr;  // staging for set_hyper
+  clv::DevPtr<double> d_hvar;       // [chain][HV] precomputed hyper variates
+  clv::DevPtr<unsigned long long> d_stamps;  // CLV_STAMPS diagnostic build only
+  clv::DevPtr<double> d_level1, d_level2, d_loglik, d_sums;
+  clv::DevPtr<float2> d_qstore;     // CLV_SINK_SUMMARY_PCT: [chain][draw][n] (lambda, mu) float32
+  clv::DevPtr<double> d_tape;
+  clv::DevPtr<double> d_bs;  // staging for set_hyper
   int64_t tape_sweeps = 0;
 
   bool pending_init_hyper = false;  // bivariate: the draw for sweep 1 is still due
@@ -229,6 +234,18 @@ struct clv_sampler {
 };
 
 namespace clv {
+
+// Element counts of the handle's buffers, each used at the allocation, the fill and the copies.
+inline size_t state_count(const Geometry& g) { return (size_t)g.n_chains * std::max<int64_t>(g.n, 1); }  // lam, mu: each
+inline size_t hyper_count(const Geometry& g) { return (size_t)g.n_chains * HS; }
+inline size_t sums_count(const Geometry& g) { return (size_t)g.n_chains * CLV_N_SUM_STATS * g.n; }  // running sums
+inline size_t arrive_count(const Geometry& g) { return (size_t)g.n_chains * (1 + g.units_per_rank); }  // arrival counters
+inline size_t handoff_count(const Geometry& g) { return 2 * hyper_count(g); }                          // hand-off slots
+inline size_t pblock_count(const Geometry& g) { return (size_t)g.n_chains * split_records(std::max(g.nb_local, 1)) * g.stride; }
+inline size_t unit_count(const Geometry& g) { return (size_t)g.n_chains * g.units_per_rank * g.stride; }
+inline size_t mail_count(const Geometry& g) { return mail_slots(g.world_size, g.n_chains, g.stride, g.units_per_rank) + MAIL_TAIL; }
+inline size_t loglik_count(const Geometry& g) { return (size_t)g.n_chains * g.n_draws; }
+inline size_t level1_count(const Geometry& g) { return loglik_count(g) * g.n * (g.D + 2); }
 
 // Draws per chain the run has stored so far: at most n_draws.
 inline int64_t stored_draws(const clv_sampler* s) {

@@ -114,6 +114,125 @@ def test_persistent_choice_by_grid_density():
     assert not pick(2, 2, 4, 505) and not pick(2, 5, 1, 505)                # does not fit at all
 
 
+# clv_debug_sweep_plan: the sweep path clv_create decides on.  Every row's expectation is read off
+# clv_create as it stood before the decision became one function (capi.hip at commit acce725, the
+# line range in each row's comment), not off plan_sweep.  Constants: CLV_BLOCK 256, PRE_STEPS 20,
+# SPLIT_MAX_NB 256, SPLIT_RELAY_STEPS 8 (the shipped build; relay default on), PERSIST_SCRATCH_MAX 64,
+# MAX_WORLD 64, UMAIL 2048 doubles; stride = K D + D (D + 1) / 2 + 1 (6 for D = 2, K = 1).
+# Base: c2's shape — bivariate, 20 MH steps, 4 chains x 93 blocks on 256 CUs, every instance at 2 (block)
+# or 1 (split) workgroups per CU and 0 B of scratch: persistent, split layout, relay instance, deferred.
+_PLAN_BASE = dict(D=2, K=1, S=20, C=4, nb=93, bpu=1, nug=93, world=1, replay=0, n_cu=256, bpc=2, scratch=0,
+                  s_bpc=1, s_scratch=0, r_bpc=1, r_scratch=0, persistent=-1, layout=0, relay=-1, defer=1)
+_PLAN_KEYS = ("persistent", "split", "relay_steps", "p2p_capable", "p2p_persist_fits", "fx_capable", "defer", "need")
+_PEER = dict(world=2, C=1, nb=100, nug=200)  # a world-2 shard inside every peer bound: both exchanges capable
+_PEER_ON = dict(p2p_capable=1, p2p_persist_fits=1, fx_capable=1)
+_FX_ONLY = dict(fx_capable=1)
+_BLOCK = dict(persistent=1, defer=1)                          # persistent, block layout
+_SPLIT = dict(persistent=1, defer=1, split=1)                 # ... split layout, helper instance
+_RELAY = dict(persistent=1, defer=1, split=1, relay_steps=8)  # ... relay instance
+_NO_SPLIT = dict(C=1, nb=100)  # fits both layouts, and the block layout does not double up (101 <= 256)
+_PLAN_ROWS = [
+    ({}, _RELAY),                                                             # 582-596, 601-611, 622-627, 684-686
+    (dict(replay=1), {}),                                                     # 582: replay is never persistent
+    (dict(bpu=2, nug=47), {}),                                                # 582: bpu == 1
+    (dict(C=1, nb=512, nug=512, n_cu=304), _BLOCK),                           # 582: nb_local <= 2 CLV_BLOCK (601: > 256, no split)
+    (dict(C=1, nb=513, nug=513, n_cu=304), {}),                               # 582 (its grid of 514 would fit 599 slots)
+    (dict(nb=0, nug=1), {}),                                                  # 582: nb_local > 0
+    (dict(D=3, K=2, scratch=64), _BLOCK),                                     # 594: scratch <= PERSIST_SCRATCH_MAX
+    (dict(D=3, K=2, scratch=65), {}),                                         # 594
+    (dict(D=3, K=2, scratch=65, persistent=1), _BLOCK),                       # 593-594: forced past the scratch bound
+    (dict(D=3, K=2, scratch=64, persistent=1), _BLOCK),                       # 593-594
+    (dict(D=3, K=2, scratch=0, persistent=0), {}),                            # 594: "0" never
+    (dict(D=3, K=2, scratch=65, persistent=0), {}),                           # 594
+    (dict(C=1, nb=504, nug=504, persistent=1), {}),                           # 594: forcing does not override the fit (505 > 504)
+    (dict(C=1, nb=503, nug=503, persistent=1), _BLOCK),                       # 594, 601
+    (dict(n_cu=0, bpc=2, scratch=-1, persistent=1), {}),                      # 585-589, 594: a failed query, never persistent
+    (dict(D=3, K=2, layout=2), _BLOCK),                                       # 601: D = 3 is never split
+    (dict(S=20), _RELAY),                                                     # 601: S <= PRE_STEPS
+    (dict(S=21, layout=2), _BLOCK),                                           # 601: S = PRE_STEPS + 1, even forced
+    (dict(C=1, nb=256, nug=256), _RELAY),                                     # 601: nb_local == SPLIT_MAX_NB (172 CUs of 252; 257 > 256 pays)
+    (dict(C=1, nb=257, nug=257, layout=2), _BLOCK),                           # 601: SPLIT_MAX_NB + 1
+    (dict(_NO_SPLIT), _BLOCK),                                                # 608-610: split does not pay
+    (dict(_NO_SPLIT, layout=2), _RELAY),                                      # 610: forced where it does not pay
+    (dict(_NO_SPLIT, layout=1), _BLOCK),                                      # 608
+    (dict(layout=1), _BLOCK),                                                 # 608: block forced where split pays
+    (dict(layout=1, s_scratch=-2), _BLOCK),                                   # 608: ... and the helper instance is not queried
+    (dict(s_scratch=8), _BLOCK),                                              # 608: split with scratch is declined
+    (dict(s_scratch=8, layout=2), _BLOCK),                                    # 608: ... forced too
+    (dict(s_scratch=-1, s_bpc=0), _BLOCK),                                    # 608, 612-613: a failed query is "not capable"
+    (dict(C=4, nb=94, nug=94), _BLOCK),                                       # 609: 4 x 64 workgroups > 252 CUs, split does not fit
+    (dict(s_scratch=-2), dict(_BLOCK, need=1)),                               # 608: the decision asks for the helper instance
+    (dict(S=8), _SPLIT),                                                      # 622: S == SPLIT_RELAY_STEPS is not relayed
+    (dict(S=8, relay=1, r_scratch=-2), _SPLIT),                               # 622: ... forced neither, and no query
+    (dict(S=8, relay=0), _SPLIT),                                             # 622
+    (dict(S=9), _RELAY),                                                      # 622: SPLIT_RELAY_STEPS + 1, default on
+    (dict(S=9, relay=1), _RELAY),                                             # 622
+    (dict(S=9, relay=0), _SPLIT),                                             # 622
+    (dict(S=9, relay=0, r_scratch=-2), _SPLIT),                               # 622: the relay instance is not queried
+    (dict(S=9, r_scratch=-2), dict(_SPLIT, need=2)),                          # 625: the decision asks for the relay instance
+    (dict(S=9, r_scratch=16), _SPLIT),                                        # 625: relay instance with scratch
+    (dict(S=9, relay=1, r_scratch=16), _SPLIT),                               # 625: ... forced too
+    (dict(S=9, r_scratch=-1, r_bpc=0), _SPLIT),                               # 625, 628-629: failed query
+    (dict(S=9, r_bpc=0), _SPLIT),                                             # 626: the relay instance does not fit
+    (dict(S=9, layout=1, relay=1), _BLOCK),                                   # 622: no relay without the split layout
+    (dict(defer=0), dict(_RELAY, defer=0)),                                   # 684-687: CLV_DEFER=0
+    (dict(D=3, K=2, scratch=65, defer=1), {}),                                # 684: deferred draws only with the persistent kernel
+    (dict(_PEER), _PEER_ON),                                                  # 636-650, 653-654
+    (dict(_PEER, nug=512), _PEER_ON),                                         # 636, 653: n_units_global <= 2 CLV_BLOCK
+    (dict(_PEER, nug=513), {}),                                               # 636, 653: ... bounds both exchanges
+    (dict(_PEER, bpu=64), _PEER_ON),                                          # 637: blocks_per_unit <= 64
+    (dict(_PEER, bpu=128), _FX_ONLY),                                         # 637
+    (dict(_PEER, nb=341, nug=500), _PEER_ON),                                 # 637: 6 x 341 = 2046 <= UMAIL
+    (dict(_PEER, nb=342, nug=500), _FX_ONLY),                                 # 637: 6 x 342 = 2052
+    (dict(_PEER, nb=512, bpu=2, nug=512, n_cu=304), _PEER_ON),                # 636-637: 6 x 256 units, 513 workgroups fit
+    (dict(_PEER, nb=513, bpu=2, nug=512, n_cu=304), _FX_ONLY),                # 636: nb_local <= 2 CLV_BLOCK
+    (dict(_PEER, world=64), _PEER_ON),                                        # 636, 653: world_size <= MAX_WORLD
+    (dict(_PEER, world=65), {}),                                              # 636, 653: neither peer path
+    (dict(_PEER, persistent=0), _FX_ONLY),                                    # 644-647: "0": the fused exchange instead
+    (dict(_PEER, scratch=65), _FX_ONLY),                                      # 647
+    (dict(_PEER, scratch=65, persistent=1), _PEER_ON),                        # 646-647
+    (dict(_PEER, nb=0), _FX_ONLY),                                            # 636: nb_local > 0; 653: an empty shard still exchanges
+    (dict(_PEER, defer=1, layout=2), _PEER_ON),                               # 601, 684: no split layout, no deferred draw with peers
+    (dict(_PEER, C=4, nb=126, nug=252), _FX_ONLY),                            # 647: the grid of 4 x 127 = 508 does not fit
+]
+# a rejected knob fails the create only on the branch that reads it (601-605, 618-621)
+_PLAN_REJECTED = [
+    (dict(layout=-1), "CLV_PERSIST_LAYOUT must be block or split"),           # 604-605
+    (dict(layout=-1, relay=2), "CLV_PERSIST_LAYOUT must be block or split"),  # 604 comes first
+    (dict(relay=2), "CLV_SPLIT_RELAY must be 0 or 1"),                        # 620-621
+    (dict(relay=2, layout=1), "CLV_SPLIT_RELAY must be 0 or 1"),              # 620: read with the block layout forced too
+    (dict(relay=2, S=8), "CLV_SPLIT_RELAY must be 0 or 1"),                   # 620: ... and where nothing would be relayed
+]
+_PLAN_NOT_READ = [dict(layout=-1, relay=2, S=21), dict(layout=-1, relay=2, D=3, K=2), dict(layout=-1, relay=2, persistent=0),
+                  dict(layout=-1, relay=2, replay=1), dict(_PEER, layout=-1, relay=2), dict(layout=-1, C=1, nb=257, nug=257)]
+
+
+def _sweep_plan(over):
+    from mcmc_clv_model_amd import _lib
+    L = _lib.lib()
+    v = dict(_PLAN_BASE, **over)
+    order = ("D", "K", "S", "C", "nb", "bpu", "nug", "world", "replay", "n_cu", "bpc", "scratch", "s_bpc", "s_scratch",
+             "r_bpc", "r_scratch", "persistent", "layout", "relay", "defer")
+    assert set(v) == set(order)
+    out = (ctypes.c_int32 * 8)()
+    rc = L.clv_debug_sweep_plan((ctypes.c_int64 * 20)(*[v[k] for k in order]), out)
+    return rc, dict(zip(_PLAN_KEYS, out)), L.clv_last_error().decode()
+
+
+@pytest.mark.parametrize("over,want", _PLAN_ROWS)
+def test_sweep_plan_table(over, want):
+    rc, got, _ = _sweep_plan(over)
+    assert rc == 0 and got == dict(dict.fromkeys(_PLAN_KEYS, 0), **want), (over, got)
+
+
+def test_sweep_plan_rejects_knobs_only_where_clv_create_reads_them():
+    for over, message in _PLAN_REJECTED:
+        rc, _, err = _sweep_plan(over)
+        assert rc == -1 and err == message, (over, rc, err)  # CLV_EINVAL
+    for over in _PLAN_NOT_READ:
+        assert _sweep_plan(over)[0] == 0, over
+
+
 def test_no_cpu_fallback_without_gpu():
     """The product path raises instead of silently running on the CPU."""
     from mcmc_clv_model_amd import _lib, mcmc_draw_parameters
