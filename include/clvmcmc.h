@@ -216,7 +216,13 @@ int clv_split_relay_steps(const clv_sampler* s, int32_t* out);
  * must call it with the same n.  A rank that waits longer than the bound (10 s by default,
  * CLV_WAIT_TIMEOUT_MS) for its peers fails with CLV_EHIP and keeps its state from before the call;
  * ranks whose call completed undo it with clv_rollback, and clv_p2p_connect may be called again
- * (it refills this rank's mail) to resume the peer exchange. */
+ * (it refills this rank's mail) to resume the peer exchange.
+ * A shard plan with an empty shard (no customers: clv_debug_world_has_empty_shard) takes the fused
+ * exchange on every rank.  The empty rank launches one workgroup per chain that draws its level 2
+ * from its mail; no rank waits for units of its, so the other ranks' hosts hold each sweep launch
+ * until every empty rank has started the sweep before it (one host round trip per sweep, same bound).
+ * clv_set_state and clv_rollback, which set the sweep count back, are called with every rank's
+ * launches complete and the ranks brought back in step before the next clv_run, as after a connect. */
 #define CLV_IPC_HANDLE_BYTES 64
 int clv_p2p_info(const clv_sampler* s, int64_t* out);
 int clv_p2p_export(clv_sampler* s, void* handle);
@@ -381,6 +387,10 @@ int clv_debug_split_stamps(clv_sampler* s, uint64_t* out);
  * instances whose resources the decision still waits for (1 helper | 2 relay; their fields stay 0).
  * CLV_EINVAL with clv_create's message where clv_create rejects a knob. */
 int clv_debug_sweep_plan(const int64_t* in, int32_t* out);
+/* Host only: 1 if the shard plan (n_global, world_size, blocks_per_rank) leaves its last rank, and
+ * maybe more, without customers.  clv_create then turns the persistent peer exchange off on every rank
+ * of that world (the empty rank has no grid to keep resident): all of them take the fused exchange. */
+int clv_debug_world_has_empty_shard(int64_t n_global, int32_t world_size, int32_t blocks_per_rank);
 
 /* ---- In-process multi-device runs (SURVEY.md §8b devices=, §8e) ----
  * A group drives the n shards of one problem from one host thread: shards[r] = the sampler of rank

@@ -143,6 +143,7 @@ def lib() -> ctypes.CDLL:
                                         POINTER(c_float), dp, POINTER(c_float), dp]),
         "clv_debug_wg_map": (c_int32, [c_int32, c_int32, c_int32, POINTER(c_int32)]),
         "clv_debug_sweep_plan": (c_int32, [POINTER(c_int64), POINTER(c_int32)]),
+        "clv_debug_world_has_empty_shard": (c_int32, [c_int64, c_int32, c_int32]),
         "clv_debug_persist_choice": (c_int32, [c_int32, c_int32, c_int32, c_int64, c_int32, c_int32]),
         "clv_debug_persist_fits": (c_int32, [c_int64, c_int32, c_int32]),
         "clv_group_create": (c_int32, [POINTER(sp), c_int32, c_int32, POINTER(sp)]),

@@ -458,6 +458,7 @@ int clv_level1_summary(int32_t device, const double* level1, int64_t n_draws, in
 }
 
 int clv_level1_summary_sampler(clv_sampler* s, double mu_cap, double* out) {
+  if (s && s->g.n == 0 && s->g.world_size > 1) return CLV_OK;  // an empty shard of a plan: no customer rows
   if (s && !s->d_level1 && s->d_qstore) {  // CLV_SINK_SUMMARY_PCT
     if (!out) return fail(CLV_EINVAL, "null argument");
     if (mu_cap != CLV_SUMMARY_MU_CAP) return fail(CLV_EINVAL, "a summary sampler's capped mean uses mu_cap = CLV_SUMMARY_MU_CAP");

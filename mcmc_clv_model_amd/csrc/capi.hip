@@ -93,7 +93,7 @@ SweepArgs sweep_args(clv_sampler* s, int init, int fuse = 0) {
   a.diag = s->d_diag;
   a.clk = s->d_clk;
   a.h = hyper_args(s, nullptr, 0);
-  if (fuse) a.h.hvar = s->replay ? nullptr : s->d_hvar;
+  if (fuse) a.h.hvar = (s->replay || s->g.nb_local == 0) ? nullptr : s->d_hvar;  // (as hyper_args: no workgroup, no precomputed variates)
   return a;
 }
 
@@ -536,6 +536,14 @@ bool persist_shape(const Geometry& g, bool replay) {
          (int64_t)g.stride * ((g.nb_local + bpu - 1) / bpu) <= UMAIL;
 }
 
+// A world whose last rank (and maybe more) has no customers: shard r is [r * blocks_per_rank * BLOCK, ...)
+// of n_global, so distributed.plan gives one whenever the ranks' blocks overshoot by a rank or more
+// (2,357 customers on 8 ranks: ranks 5-7).  An empty shard has no resident grid; it takes the fused
+// exchange, and so does every rank of its world — each decides from the plan alone, so all decide alike.
+bool world_has_empty_shard(int64_t n_global, int world, int blocks_per_rank) {
+  return world > 1 && (int64_t)(world - 1) * blocks_per_rank * BLOCK >= n_global;
+}
+
 // The two rules the CPU tests pin through clv_debug_persist_choice / clv_debug_split_choice.
 bool persist_grid_chosen(int D, int K, int n_chains, int64_t grid_wgs, int blocks_per_cu, int n_cu, bool force) {
   return persist_grid_fits(grid_wgs, blocks_per_cu, n_cu) && (force || persist_worth(D, K, n_chains, grid_wgs, n_cu));
@@ -696,6 +704,7 @@ int decide_sweep_path(clv_sampler* s, const SweepEnv& env) {
     p = plan_sweep(g, s->replay, r, env);
   }
   if (p.error) return fail(CLV_EINVAL, p.error);
+  if (world_has_empty_shard(g.n_global, g.world_size, g.blocks_per_rank)) p.p2p_capable = p.p2p_persist_fits = false;
   s->persistent = p.persistent;
   s->split = p.split;
   s->relay_steps = p.relay_steps;
@@ -893,6 +902,7 @@ void clv_destroy(clv_sampler* s) {
   if (s->graph_exec) (void)hipGraphExecDestroy(s->graph_exec);
   for (auto e : s->ev) (void)hipEventDestroy(e);
   if (s->done_ev) (void)hipEventDestroy(s->done_ev);
+  if (s->poll_stream) (void)hipStreamDestroy(s->poll_stream);
   if (s->h_abort) (void)hipHostFree(s->h_abort);
   forget_peers(s);  // before this rank's mail goes
   const hipStream_t own = s->own;
@@ -1069,6 +1079,7 @@ int clv_p2p_connect(clv_sampler* s, const void* handles, const uint64_t* ptrs) {
   CLV_HIP(hipMemcpy(s->d_peers, peers.data(), sizeof(double*) * W, hipMemcpyHostToDevice));
   CLV_HIP(hipStreamSynchronize(s->stream));  // the mail's sentinel fill has landed
   s->p2p_ready = true;
+  s->fx_epoch = s->sweeps_done;
   return CLV_OK;
 }
 
@@ -1122,6 +1133,18 @@ static int rewind_ctrl_and_sums(clv_sampler* s) {
   CLV_HIP(hipMemcpy(s->d_ctrl, &c, sizeof(Ctrl), hipMemcpyHostToDevice));
   if (s->d_sums_prev)
     CLV_HIP(hipMemcpy(s->d_sums, s->d_sums_prev, sizeof(double) * sums_count(s->g), hipMemcpyDeviceToDevice));
+  return CLV_OK;
+}
+
+// The sweep count is set back (clv_set_state, clv_rollback) with every rank's launches complete, so every mail
+// slot is empty: wait_for_empty_ranks starts over from here, and the progress words of the sweeps now undone
+// are cleared so that they cannot pass for the sweeps to come.  (The peers post again only after the caller
+// has brought the ranks back in step, as after clv_p2p_connect.)
+static int restart_fx_epoch(clv_sampler* s) {
+  s->fx_epoch = s->sweeps_done;
+  if (s->d_mail)
+    CLV_HIP(hipMemset(s->d_mail + mail_slots(s->g.world_size, s->g.n_chains, s->g.stride, s->g.units_per_rank), 0xFF,
+                      sizeof(double) * MAIL_TAIL));
   return CLV_OK;
 }
 
@@ -1310,6 +1333,38 @@ int enqueue_fused_sweeps(clv_sampler* s, int64_t n_sweeps) {
   return CLV_OK;
 }
 
+// A world with an empty shard, on a rank that has customers.  The mail's slots of one parity are reused two
+// sweeps later, and what makes that safe is that the ranks wait for each other: a rank stores its units of
+// sweep s + 2 after its draw of s + 1, which waited for every peer's units of s + 1, stored after that
+// peer's draw of s had read and emptied its slots.  Nobody waits for an empty rank (it has no unit below
+// n_units_global), so nothing would keep the others from running ahead of it and storing sweep s + 2 over
+// the units of sweep s it has not read yet.  The host holds them back instead: sweep s is launched only once
+// every empty rank's progress word in this rank's mail (kernels.hip post_progress) shows that it has started
+// sweep s - 1, so its launch of s - 2, slot resets included, has ended.  The first two sweeps after fx_epoch
+// find every slot empty.  Bounded like the in-kernel waits; such worlds are small (at most about world_size^2
+// blocks), so one host round trip per sweep is their whole cost.
+int wait_for_empty_ranks(clv_sampler* s, int64_t sweep) {
+  const Geometry& g = s->g;
+  if (sweep <= s->fx_epoch + 2) return CLV_OK;
+  const int64_t per_rank = (int64_t)g.blocks_per_rank * BLOCK;
+  const int first = (int)((g.n_global + per_rank - 1) / per_rank);  // ranks first .. world_size - 1 are empty
+  std::vector<int64_t> prog((size_t)(g.world_size - first), -1);
+  const double* words = s->d_mail + mail_slots(g.world_size, g.n_chains, g.stride, g.units_per_rank) + first;
+  if (!s->poll_stream) CLV_HIP(hipStreamCreateWithFlags(&s->poll_stream, hipStreamNonBlocking));
+  const int64_t t0 = host_now_ns(), bound_ns = (int64_t)s->wait_ticks * 10;  // (ticks of 100 MHz)
+  for (;;) {
+    CLV_HIP(hipMemcpyAsync(prog.data(), words, sizeof(int64_t) * prog.size(), hipMemcpyDeviceToHost, s->poll_stream));
+    CLV_HIP(hipStreamSynchronize(s->poll_stream));
+    size_t behind = 0;
+    while (behind < prog.size() && prog[behind] >= sweep - 1) ++behind;  // (-1: that rank has not polled yet)
+    if (behind == prog.size()) return CLV_OK;
+    if (host_now_ns() - t0 > bound_ns)
+      return fail(CLV_EHIP, "fused peer exchange: a wait timed out (a peer rank not running?); state unchanged [host wait: sweep " +
+                                std::to_string(sweep) + ", empty rank " + std::to_string(first + (int)behind) +
+                                " last polled for sweep " + (prog[behind] < 0 ? std::string("none") : std::to_string(prog[behind])) + "]");
+  }
+}
+
 // World size > 1 without a resident grid: n launches of the sweep kernel whose fused tail
 // exchanges unit partials through the peers' mail (kernels.hip sweep_body, FX).  The state before
 // the call is kept in the persistent path's *_alt buffers, so that a call in which a wait times out
@@ -1326,7 +1381,15 @@ int run_fused_exchange(clv_sampler* s, int64_t n_sweeps) {
   if (s->d_sums_prev)
     CLV_HIP(hipMemcpyAsync(s->d_sums_prev, s->d_sums, sizeof(double) * sums_count(g), hipMemcpyDeviceToDevice, s->stream));
   const int64_t before = s->sweeps_done;
-  const int rc = enqueue_fused_sweeps(s, n_sweeps);
+  int rc = CLV_OK;
+  if (g.nb_local > 0 && world_has_empty_shard(g.n_global, g.world_size, g.blocks_per_rank)) {
+    for (int64_t k = 0; k < n_sweeps && rc == CLV_OK; ++k) {  // (an empty rank itself waits in its kernel, as every rank does)
+      rc = wait_for_empty_ranks(s, s->sweeps_done + 1);
+      if (rc == CLV_OK) rc = enqueue_fused_sweeps(s, 1);
+    }
+  } else {
+    rc = enqueue_fused_sweeps(s, n_sweeps);
+  }
   CLV_HIP(hipStreamSynchronize(s->stream));
   const bool aborted = __atomic_load_n(s->h_abort, __ATOMIC_ACQUIRE) != 0;
   if (rc == CLV_OK && !aborted) {
@@ -1454,6 +1517,7 @@ int clv_rollback(clv_sampler* s) {
   s->rb_hyper_swaps = 0;
   s->sweeps_done -= s->last_persist_n;
   s->last_persist_n = 0;
+  if (int rc = restart_fx_epoch(s)) return rc;
   if (int rc = rewind_ctrl_and_sums(s)) return rc;
   return drop_graph(s);
 }
@@ -1501,7 +1565,8 @@ int clv_read_summary(clv_sampler* s, double* sums, int64_t* n_stored) {
   CLV_HIP(hipStreamSynchronize(s->stream));
   const Geometry& g = s->g;
   if (n_stored) *n_stored = stored_draws(s);
-  if (sums) {
+  const bool summary_sink = s->cfg.draw_sink == CLV_SINK_SUMMARY || s->cfg.draw_sink == CLV_SINK_SUMMARY_PCT;
+  if (sums && !(summary_sink && g.n == 0)) {  // (an empty shard's sums have no columns: nothing to copy)
     if (!s->d_sums) return fail(CLV_ESTATE, "summaries need draw_sink == CLV_SINK_SUMMARY (or _PCT)");
     CLV_HIP(s->d_sums.download(sums, sums_count(g)));
   }
@@ -1560,6 +1625,7 @@ int clv_set_state(clv_sampler* s, const double* lambdas, const double* mus, cons
   CLV_HIP(hipStreamSynchronize(s->stream));
   s->sweeps_done = sweeps_done;
   s->last_persist_n = 0;
+  if (int rc = restart_fx_epoch(s)) return rc;
   stream_rewind(s);
   return CLV_OK;
 }
@@ -1743,6 +1809,10 @@ int clv_debug_split_fits(int32_t n_chains, int32_t nb, int32_t blocks_per_cu, in
 
 int clv_debug_split_choice(int32_t n_chains, int32_t nb, int32_t blocks_per_cu, int32_t n_cu) {
   return split_chosen(n_chains, nb, blocks_per_cu, n_cu, false) ? 1 : 0;
+}
+
+int clv_debug_world_has_empty_shard(int64_t n_global, int32_t world, int32_t blocks_per_rank) {
+  return world_has_empty_shard(n_global, world, blocks_per_rank) ? 1 : 0;
 }
 
 int clv_debug_sweep_plan(const int64_t* in, int32_t* out) {

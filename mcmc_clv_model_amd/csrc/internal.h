@@ -192,6 +192,12 @@ struct clv_sampler {
   bool p2p_persist_fits = false;    // (p2p_capable as chosen at create; clv_p2p_set_persistent may clear p2p_capable)
   bool fx_capable = false;          // fused peer exchange (launch-per-sweep, any shard size)
   bool p2p_ready = false;           // clv_p2p_connect done: clv_run runs persist_kernel
+  // A world with an empty shard (fused exchange only): nobody waits for an empty rank's units, so the
+  // other ranks' hosts hold each sweep launch until every empty rank has started the sweep before it
+  // (capi.hip wait_for_empty_ranks).  fx_epoch: the sweep count when the mail was last known empty on
+  // every rank (connect, set_state, rollback); poll_stream: the stream the progress words are read on.
+  int64_t fx_epoch = 0;
+  hipStream_t poll_stream = nullptr;
   clv::DevPtr<double> d_mail;       // [2][world][chain][units_per_rank][stride]
   int mail_kind = -1;               // the mail's memory: 0 uncached, 1 fine-grained, 2 plain device memory
   clv::DevPtr<double*> d_peers;     // [world] mail pointers (peers' opened IPC mappings, own d_mail)

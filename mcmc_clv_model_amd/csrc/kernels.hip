@@ -1864,6 +1864,99 @@ __device__ __forceinline__ void cust_store(const Cust<D, K, CL>& u, const CustOu
 
 static_assert(BLOCK == EXP_TAB_N, "the sweep kernel stages the exp table with one entry per lane");
 
+// The fused peer exchange's level-2 draw of chain c after sweep s, by one NT-thread workgroup: the
+// last-arriving sweep workgroup of the chain (sweep_body), or, on a rank without customers, where no
+// sweep workgroup runs, fx_empty_kernel's.
+template <int D, int K, bool REPLAY, int NS, int NT>
+__device__ __forceinline__ void fx_level2(const SweepArgs& a, int c, int64_t s, double (*red)[NS], double* tot,
+                                          double* var_iw, double* var_chi, double* var_noise, L2Scratch* l2) {
+  const Geometry& g = a.g;
+  const int64_t mail_rank = (int64_t)g.n_chains * g.units_per_rank * NS;
+  hyper_variates<D, K, REPLAY>(a.h, c, s, var_iw, var_chi, var_noise, l2);
+  // every rank's units of sweep s from this rank's mail: lane u reads units u, u + NT
+  // (n_units_global <= 2 NT) and sums them in that order — hyper_sum_units' order, so the
+  // result is the all-gather path's bit for bit; then it empties its slots for sweep s + 2
+  const int64_t u0 = threadIdx.x, u1 = threadIdx.x + NT;
+  const bool h0 = u0 < g.n_units_global, h1 = u1 < g.n_units_global;
+  const double* mb = a.mail + (int64_t)(s & 1) * g.world_size * mail_rank + (int64_t)c * g.units_per_rank * NS;
+  double* p0 = (double*)mb + (u0 / g.units_per_rank) * mail_rank + (u0 % g.units_per_rank) * NS;
+  double* p1 = (double*)mb + (u1 / g.units_per_rank) * mail_rank + (u1 % g.units_per_rank) * NS;
+  const double* q0 = h0 ? p0 : mb;
+  const double* q1 = h1 ? p1 : mb;
+  __shared__ uint32_t s_fx_abort;
+  if (threadIdx.x == 0) {
+    s_fx_abort = 0;
+    post_progress(a, a.peers, s);
+  }
+  __syncthreads();
+  // statistics in chunks of FXC (all NS at once for small NS): the polled values of a chunk
+  // and the lane's finished sums are live together, not 2 NS polled values (c5: NS = 34)
+  constexpr int FXC = NS <= 16 ? NS : 12;
+  double acc[NS];
+  bool timed_out = false;
+#pragma unroll
+  for (int j0 = 0; j0 < NS; j0 += FXC) {
+    double v0[FXC], v1[FXC];
+    const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
+    for (uint32_t poll = 0; !timed_out; ++poll) {
+      bool ok = true;
+#pragma unroll
+      for (int q = 0; q < FXC; ++q) {
+        if (j0 + q < NS) {
+          v0[q] = ld_sys(q0 + j0 + q);
+          v1[q] = ld_sys(q1 + j0 + q);
+          ok = ok & (!h0 | slot_full(v0[q])) & (!h1 | slot_full(v1[q]));
+        }
+      }
+      if (__all(ok)) break;
+      const int ws = wait_state(a, t0, poll, a.wait_ticks);
+      if (ws == WAIT_OBSERVED) {
+        timed_out = true;
+      } else if (ws == WAIT_EXPIRED) {
+        timed_out = true;
+        int64_t mu_ = -1;
+        int mj = -1;
+        uint64_t mb = 0;
+#pragma unroll
+        for (int q = FXC - 1; q >= 0; --q) {  // the lane's first missing slot
+          if (j0 + q < NS) {
+            if (h1 && !slot_full(v1[q])) { mu_ = u1; mj = j0 + q; mb = dbits(v1[q]); }
+            if (h0 && !slot_full(v0[q])) { mu_ = u0; mj = j0 + q; mb = dbits(v0[q]); }
+          }
+        }
+        report_wait(a, WAIT_FX_MAIL, s, c, ok, mu_, mj, mb, poll, t0);
+        raise_abort(a);
+      } else {
+        __builtin_amdgcn_s_sleep(1);
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < FXC; ++q) {
+      if (j0 + q < NS) {
+        acc[j0 + q] = 0.0;
+        if (h0) acc[j0 + q] += v0[q];
+        if (h1) acc[j0 + q] += v1[q];
+      }
+    }
+  }
+  if (timed_out) s_fx_abort = 1;
+  __syncthreads();
+  if (!s_fx_abort) {
+    // the slots of sweep s empty again for sweep s + 2 (written only after the next kernel
+    // boundary): every rank's [unit][stat] run of this (parity, chain), coalesced, by
+    // wavefronts 1-3 while wavefront 0 draws — lane-per-unit resets wrote one double of a
+    // different line per lane and instruction ahead of the draw (c5 at 8 ranks: 306 units x
+    // 34 statistics; round 6, as the persistent kernel's slots)
+    const int nrun = g.units_per_rank * NS;
+    hyper_finish<D, K, REPLAY, NS, NT>(a.h, c, s, 0, acc, red, tot, var_iw, var_chi, var_noise, l2, [&] {
+      for (int e = (int)threadIdx.x - 64; e >= 0 && e < g.world_size * nrun; e += NT - 64) {
+        const int q = e / nrun;
+        st_sys((double*)mb + (int64_t)q * mail_rank + (e - q * nrun), slot_empty());
+      }
+    });
+  }
+}
+
 // FX: the fused peer exchange (world size > 1 after clv_p2p_connect) compiled in — instances of
 // their own, launched for sharded runs only (compiled into the world-size-1 kernels it cost c4 /
 // c5 1.8% / 1.6% per sweep).
@@ -2131,89 +2224,7 @@ __device__ __forceinline__ void sweep_body(const SweepArgs& a) {
       if (!fx) {
         hyper_body<D, K, REPLAY, NS, NT>(a.h, c, s, 0, units, red, tot, var_iw, var_chi, var_noise, &l2);
       } else {
-        hyper_variates<D, K, REPLAY>(a.h, c, s, var_iw, var_chi, var_noise, &l2);
-        // every rank's units of sweep s from this rank's mail: lane u reads units u, u + NT
-        // (n_units_global <= 2 NT) and sums them in that order — hyper_sum_units' order, so the
-        // result is the all-gather path's bit for bit; then it empties its slots for sweep s + 2
-        const int64_t u0 = threadIdx.x, u1 = threadIdx.x + NT;
-        const bool h0 = u0 < g.n_units_global, h1 = u1 < g.n_units_global;
-        const double* mb = a.mail + (int64_t)(s & 1) * g.world_size * mail_rank + (int64_t)c * g.units_per_rank * NS;
-        double* p0 = (double*)mb + (u0 / g.units_per_rank) * mail_rank + (u0 % g.units_per_rank) * NS;
-        double* p1 = (double*)mb + (u1 / g.units_per_rank) * mail_rank + (u1 % g.units_per_rank) * NS;
-        const double* q0 = h0 ? p0 : mb;
-        const double* q1 = h1 ? p1 : mb;
-        __shared__ uint32_t s_fx_abort;
-        if (threadIdx.x == 0) {
-          s_fx_abort = 0;
-          post_progress(a, a.peers, s);
-        }
-        __syncthreads();
-        // statistics in chunks of FXC (all NS at once for small NS): the polled values of a chunk
-        // and the lane's finished sums are live together, not 2 NS polled values (c5: NS = 34)
-        constexpr int FXC = NS <= 16 ? NS : 12;
-        double acc[NS];
-        bool timed_out = false;
-#pragma unroll
-        for (int j0 = 0; j0 < NS; j0 += FXC) {
-          double v0[FXC], v1[FXC];
-          const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
-          for (uint32_t poll = 0; !timed_out; ++poll) {
-            bool ok = true;
-#pragma unroll
-            for (int q = 0; q < FXC; ++q) {
-              if (j0 + q < NS) {
-                v0[q] = ld_sys(q0 + j0 + q);
-                v1[q] = ld_sys(q1 + j0 + q);
-                ok = ok & (!h0 | slot_full(v0[q])) & (!h1 | slot_full(v1[q]));
-              }
-            }
-            if (__all(ok)) break;
-            const int ws = wait_state(a, t0, poll, a.wait_ticks);
-            if (ws == WAIT_OBSERVED) {
-              timed_out = true;
-            } else if (ws == WAIT_EXPIRED) {
-              timed_out = true;
-              int64_t mu_ = -1;
-              int mj = -1;
-              uint64_t mb = 0;
-#pragma unroll
-              for (int q = FXC - 1; q >= 0; --q) {  // the lane's first missing slot
-                if (j0 + q < NS) {
-                  if (h1 && !slot_full(v1[q])) { mu_ = u1; mj = j0 + q; mb = dbits(v1[q]); }
-                  if (h0 && !slot_full(v0[q])) { mu_ = u0; mj = j0 + q; mb = dbits(v0[q]); }
-                }
-              }
-              report_wait(a, WAIT_FX_MAIL, s, c, ok, mu_, mj, mb, poll, t0);
-              raise_abort(a);
-            } else {
-              __builtin_amdgcn_s_sleep(1);
-            }
-          }
-#pragma unroll
-          for (int q = 0; q < FXC; ++q) {
-            if (j0 + q < NS) {
-              acc[j0 + q] = 0.0;
-              if (h0) acc[j0 + q] += v0[q];
-              if (h1) acc[j0 + q] += v1[q];
-            }
-          }
-        }
-        if (timed_out) s_fx_abort = 1;
-        __syncthreads();
-        if (!s_fx_abort) {
-          // the slots of sweep s empty again for sweep s + 2 (written only after the next kernel
-          // boundary): every rank's [unit][stat] run of this (parity, chain), coalesced, by
-          // wavefronts 1-3 while wavefront 0 draws — lane-per-unit resets wrote one double of a
-          // different line per lane and instruction ahead of the draw (c5 at 8 ranks: 306 units x
-          // 34 statistics; round 6, as the persistent kernel's slots)
-          const int nrun = g.units_per_rank * NS;
-          hyper_finish<D, K, REPLAY, NS, NT>(a.h, c, s, 0, acc, red, tot, var_iw, var_chi, var_noise, &l2, [&] {
-            for (int e = (int)threadIdx.x - 64; e >= 0 && e < g.world_size * nrun; e += NT - 64) {
-              const int q = e / nrun;
-              st_sys((double*)mb + (int64_t)q * mail_rank + (e - q * nrun), slot_empty());
-            }
-          });
-        }
+        fx_level2<D, K, REPLAY, NS, NT>(a, c, s, red, tot, var_iw, var_chi, var_noise, &l2);
       }
       if (threadIdx.x == 0) CLV_STAMP(a.stamps, s, 3, false);
     }
@@ -2232,9 +2243,40 @@ __global__ __launch_bounds__(BLOCK, 4) void sweep_kernel_occ4(SweepArgs a) {
   sweep_body<D, K, REPLAY, FX>(a);
 }
 
+// The fused peer exchange on a rank without customers (an empty shard of the plan: nb_local == 0).  No
+// sweep workgroup runs there, so one workgroup per chain stands in for the chain's last-arriving one:
+// it draws the rank's level 2 of this sweep from its mail and advances the sweep counter (a.h.hvar
+// null: it draws its own variates, the values a sweep workgroup would have precomputed).
+template <int D, int K>
+__global__ __launch_bounds__(BLOCK) void fx_empty_kernel(SweepArgs a) {
+  constexpr int NS = K * D + D * (D + 1) / 2 + 1;
+  __shared__ double red[BLOCK / 64][NS];
+  __shared__ double tot[NS];
+  __shared__ double var_iw[4], var_chi[4], var_noise[32];
+  __shared__ L2Scratch l2;
+  if (__hip_atomic_load(&a.ctrl_rw->abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;  // (as sweep_body)
+  const int64_t s = a.ctrl->cur + 1;
+  fx_level2<D, K, false, NS, BLOCK>(a, blockIdx.x, s, red, tot, var_iw, var_chi, var_noise, &l2);
+}
+
+template <int D, int K>
+hipError_t launch_fx_empty_t(const SweepArgs& a, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
+  if (e0) hipExtLaunchKernelGGL((fx_empty_kernel<D, K>), dim3(a.g.n_chains), dim3(BLOCK), 0, st, e0, e1, 0, a);
+  else hipLaunchKernelGGL((fx_empty_kernel<D, K>), dim3(a.g.n_chains), dim3(BLOCK), 0, st, a);
+  return hipGetLastError();
+}
+
 // One instance per (D, K, REPLAY, FX): the occupancy variant SweepOcc picks (only that one compiled).
 template <int D, int K, bool REPLAY, bool FX>
 hipError_t launch_sweep_t(const SweepArgs& a, hipStream_t st, hipEvent_t e0, hipEvent_t e1) {
+  if (a.g.nb_local == 0) {  // an empty shard: a grid of no workgroups is not a launch
+    if constexpr (FX) return launch_fx_empty_t<D, K>(a, st, e0, e1);
+    if (a.fuse) return hipErrorInvalidConfiguration;  // (world size 1: nothing would draw level 2)
+    // its block partials stay the zeros of the allocation; the events still bracket the sweep
+    if (e0 && hipEventRecord(e0, st) != hipSuccess) return hipGetLastError();
+    if (e1 && hipEventRecord(e1, st) != hipSuccess) return hipGetLastError();
+    return hipSuccess;
+  }
   const dim3 grid(a.g.nb_local, a.g.n_chains);
   const dim3 block(BLOCK);
   // e0/e1: hipExtLaunchKernelGGL records the dispatch's own start/end timestamps into the events
@@ -4086,6 +4128,7 @@ hipError_t persist_scratch_bytes(int D, int K, bool p2p, size_t* bytes) {
 
 hipError_t launch_group(const GroupArgs& a, hipStream_t st) {
   const int units_local = (a.g.nb_local + a.g.blocks_per_unit - 1) / a.g.blocks_per_unit;
+  if (units_local == 0) return hipSuccess;  // an empty shard: its unit partials stay the zeros of the allocation
   hipLaunchKernelGGL(group_kernel, dim3(units_local, a.g.n_chains), dim3(64), 0, st, a);
   return hipGetLastError();
 }

@@ -350,6 +350,7 @@ def _grid_case(D, K, n, chains, bpu, modes, seed, geometry, drop):
 # customer ranges [lo, hi) left out of the level-2 model and the log-likelihood mean by the power
 # checks (blocks 0, 256 and the last; or the whole last unit).
 _N300, _N600, _N41 = 299 * BLOCK + 1, 599 * BLOCK + 1, 10300
+_BOTH_KERNELS = dict(default=True, launch_per_sweep=False)
 _BLOCKS_300 = {"block 0": (0, BLOCK), "block 256": (256 * BLOCK, 257 * BLOCK), "last block": (299 * BLOCK, _N300)}
 GRID_CASES = {
     # persistent: lanes 0..43 of the level-2 workgroup hold two blocks, level-2 workgroup alone on its
@@ -370,7 +371,24 @@ GRID_CASES = {
     "g_bi5_u16": _grid_case(2, 5, _N41, 2, 16, dict(default=False), 3106, (41, 16, 3, 3), {"last unit": (2 * 16 * BLOCK, _N41)}),
     # the same through the NS > 16 branch (NS = 34, covariates in LDS)
     "g_tri9_u16": _grid_case(3, 9, _N41, 2, 16, dict(default=False), 3107, (41, 16, 3, 3), {"last unit": (2 * 16 * BLOCK, _N41)}),
+    # The unsharded side of tests/shard_edge_cases.py, row by row (D, K, N, blocks_per_unit): the sharded
+    # exchanges are held to these runs bit for bit, so these runs are held to the model.  Small grids: a
+    # last block of one lane, a single full block, a 44-lane block; 6 / 10 blocks as 6 / 10 units; and
+    # blocks_per_unit 4 and 2 set explicitly at 6 and 5 blocks (fused tail with unit arrival counters:
+    # a last unit of 2 of 4 blocks / 1 of 2 blocks over zero padding).
+    "g_bi2_257": _grid_case(2, 2, 257, 2, 0, _BOTH_KERNELS, 3111, (2, 1, 2, 2), {"last block": (BLOCK, 257)}),
+    "g_bi1_256": _grid_case(2, 1, 256, 2, 0, _BOTH_KERNELS, 3112, (1, 1, 1, 1), {"wave rows 2-3": (BLOCK // 2, BLOCK)}),
+    "g_tri3_300": _grid_case(3, 3, 300, 2, 0, _BOTH_KERNELS, 3113, (2, 1, 2, 2), {"last block": (BLOCK, 300)}),
+    "g_bi2_1281": _grid_case(2, 2, 1281, 2, 0, _BOTH_KERNELS, 3114, (6, 1, 6, 6),
+                             {"block 4": (4 * BLOCK, 5 * BLOCK), "last block": (5 * BLOCK, 1281)}),
+    "g_tri3_1281_u4": _grid_case(3, 3, 1281, 2, 4, dict(default=False), 3115, (6, 4, 2, 2), {"last unit": (4 * BLOCK, 1281)}),
+    "g_bi5_1025_u2": _grid_case(2, 5, 1025, 2, 2, dict(default=False), 3116, (5, 2, 3, 3), {"last unit": (4 * BLOCK, 1025)}),
+    "g_bi2_abe": dict(_grid_case(2, 2, 2357, 2, 0, _BOTH_KERNELS, 3117, (10, 1, 10, 10), {"last block": (9 * BLOCK, 2357)}),
+                      covs=["first_sales_scaled"], data=("abe", 2357, 0)),  # the sample itself, not the tiled frame
 }
+# the GRID_CASES row of each tests/shard_edge_cases.py case
+SHARD_EDGE_GRID = dict(one_lane="g_bi2_257", exact_empty="g_bi1_256", two_empty="g_tri3_300", tail_empty="g_bi2_1281",
+                       part_unit="g_tri3_1281_u4", part_unit3="g_bi5_1025_u2", abe_world8="g_bi2_abe")
 GRID_RUNS = [(n, m) for n, c in GRID_CASES.items() for m in c["modes"]]
 
 

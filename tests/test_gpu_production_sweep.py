@@ -68,6 +68,9 @@ The same comparison is pointed at the rest of the kernel by two more tables of p
   of 306,690 lanes set aside at g_bi2_600u, none elsewhere; tau 6.8e-15, lambda 2.7e-15, mu 3.6e-15,
   eta 2.0e-15, log-likelihood 2.6e-16, level-2 record 5.4e-13 beyond the absolute term (beta 1.0e-10,
   Sigma 9.6e-10 elementwise on entries near zero).  All 45 runs together take 5 s.
+  Seven more rows (philox_sweep_ref.SHARD_EDGE_GRID, 12 runs) are the unsharded side of
+  tests/test_gpu_shard_edges.py, which holds every sharded exchange to them bit for bit: 1, 2, 6 and 10
+  blocks with a last block of 1 / 256 / 44 / 53 lanes, and blocks_per_unit 4 and 2 at 6 and 5 blocks.
 """
 import ctypes
 
