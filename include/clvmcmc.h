@@ -975,6 +975,31 @@ int clv_pnbd_dert(clv_pnbd* h, const double* params, double delta, double horizo
 int clv_dert_integral(int32_t device, int64_t n, const double* s, const double* B, const double* delta,
                       const double* horizon, double* out);
 
+/* ---- The integral I past the series' term cap (csrc/pnbd.hip) ----
+ * The series of clv_pnbd_eval needs about 36.7 / (-ln z) terms, z = |alpha_i - beta_i| /
+ * (max(alpha_i, beta_i) + t): 2,048 terms end at z of about 0.98, and a covariate that moves
+ * alpha_i / beta_i by orders of magnitude passes that.  The second evaluation integrates I itself by
+ * 16-point Gauss-Legendre panels of a positive integrand in d = log((m + y) / (m + t_x)), m =
+ * min(alpha_i, beta_i), measured from the lower limit; the gradient is taken under the integral at the
+ * same nodes.  It converges for every z < 1 and forms no difference of two series.
+ * clv_pnbd_set_integral chooses, per handle, how clv_pnbd_eval, _eval_cov, _customers,
+ * _customers_cov and clv_pnbd_dert evaluate I:
+ *   CLV_PNBD_INTEGRAL_SERIES      the series for every customer: the default, and the behaviour of a
+ *                                 handle that never called this entry, bit for bit (NaN and a count at
+ *                                 the term cap);
+ *   CLV_PNBD_INTEGRAL_AUTO        the series, with the same bits, for a customer with z(t_x) <= 0.9, the
+ *                                 quadrature for every other customer with t_x < T;
+ *   CLV_PNBD_INTEGRAL_QUADRATURE  the quadrature for every customer with t_x < T.
+ * In the last two modes a customer is counted in *n_unconverged only when a result is not finite (an
+ * alpha_i that underflowed to 0).  CLV_EINVAL for another mode or a null handle, before any device
+ * call. */
+enum {
+  CLV_PNBD_INTEGRAL_SERIES = 0,
+  CLV_PNBD_INTEGRAL_AUTO = 1,
+  CLV_PNBD_INTEGRAL_QUADRATURE = 2
+};
+int clv_pnbd_set_integral(clv_pnbd* h, int32_t mode);
+
 /* ---- Gamma-Gamma spend model by maximum likelihood (csrc/gg.hip) ----
  * Fader, Hardie & Lee (2005), "RFM and CLV", and Fader & Hardie (2013), "The Gamma-Gamma model of
  * monetary value", equation (1a): customer i with mean spend m_i > 0 over n_i >= 1 transactions,

@@ -229,6 +229,7 @@ def lib() -> ctypes.CDLL:
         "clv_pnbd_customers_cov": (c_int32, [sp, dp, c_double, dp]),
         "clv_pnbd_track_cov": (c_int32, [c_int32, c_int64, dp, dp, c_int32, dp, c_int32, dp, c_int32, dp, dp]),
         "clv_pnbd_dert": (c_int32, [sp, dp, c_double, c_double, dp]),
+        "clv_pnbd_set_integral": (c_int32, [sp, c_int32]),
         "clv_dert_integral": (c_int32, [c_int32, c_int64, dp, dp, dp, dp, dp]),
         "clv_gg_create": (c_int32, [c_int32, c_int64, POINTER(c_int32), dp, dp, POINTER(sp)]),
         "clv_gg_destroy": (None, [sp]),

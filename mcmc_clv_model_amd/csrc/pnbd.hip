@@ -9,6 +9,10 @@
 //   clv_pnbd_set_covariates      time-invariant covariates (Fader & Hardie 2007) resident in the handle
 //   clv_pnbd_eval_cov / _customers_cov / _track_cov   the same three with alpha_i = alpha0 exp(-gamma1' z_i),
 //                                beta_i = beta0 exp(-gamma2' z_i): DESIGN.md section 4m
+//   clv_pnbd_set_integral        how the handle's evaluations form I: the series below (the default), or a
+//                                Gauss-Legendre quadrature of I itself for the customers the series cannot
+//                                reach (z(t_x) above 0.9 in "auto", everyone in "quadrature"): DESIGN.md
+//                                section 4o, pnbd_si_quadrature; float64 model: tests/pnbd_tail_ref.py
 //
 // Per customer, with theta = (r, alpha, s, beta), a = r + s + x, M = max(alpha, beta) and
 // z(t) = |alpha - beta| / (M + t) in [0, 1):
@@ -32,6 +36,7 @@
 #include <cmath>
 #include <limits>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "gauss_legendre.h"
@@ -53,6 +58,7 @@ struct clv_pnbd {
   DevBuf z1, z2;
   DevBuf partc;  // [nb][PNBD_NS + k1 + k2]
   DevBuf outc;   // [PNBD_NS + k1 + k2]
+  int32_t integral = CLV_PNBD_INTEGRAL_SERIES;  // clv_pnbd_set_integral
 };
 
 namespace {
@@ -62,6 +68,14 @@ constexpr int PNBD_TERM_CAP = 2048;   // series terms after u_0 (reaches z of ab
 constexpr double PNBD_EPS = 0x1p-53;  // relative remainder at which the series stops
 constexpr int PNBD_MAX_COV = 8;      // covariate columns per process
 constexpr int PNBD_COV_GROUP = 8;     // covariate sums reduced per pass over the LDS tile
+// How I is evaluated (clv_pnbd_set_integral): a template parameter of the kernel family, as Src is, so the
+// series instances are the code they were before the quadrature existed.
+constexpr int PNBD_SERIES = CLV_PNBD_INTEGRAL_SERIES, PNBD_AUTO = CLV_PNBD_INTEGRAL_AUTO,
+              PNBD_QUADRATURE = CLV_PNBD_INTEGRAL_QUADRATURE;
+constexpr double PNBD_Z_SWITCH = 0.9;   // auto: the series up to this z(t_x) (at most about 370 terms), the quadrature past it
+constexpr double PNBD_Q_SLOPE = 4.0;    // a panel is at most PNBD_Q_SLOPE / |d log integrand / dd| wide, and at most 1
+constexpr double PNBD_Q_SPAN = 40.0;    // the panels may stop once the integrand is exp(-40) below its start
+constexpr int PNBD_Q_PANEL_CAP = 4096;  // never reached by a finite width: the integrand falls at least as exp(-(r + s + x) d)
 
 struct Params {
   double r, a, s, b;
@@ -134,13 +148,84 @@ __host__ __device__ inline LogH pnbd_log_h(double t, double x, const Params& p) 
   return o;
 }
 
+// log(s I) and d log(s I) / d(r, alpha, s, beta) by Gauss-Legendre quadrature of I itself, for t_x < T and any
+// z.  With m = min(alpha, beta), Delta = |alpha - beta|, e0 = m + t_x and
+// d = log((m + y) / e0) the integrand over its value at t_x is
+//   g(d) = exp((1 - p_m) d - p_M log1p(q expm1(d))),  q = e0 / (e0 + Delta) = 1 - z(t_x),
+// p_m the exponent of the factor with the smaller offset (r + x or s + 1), p_M the other one: positive,
+// analytic in d (the nearest singularity is pi off the real axis) and free of both scales.  The panels walk d
+// from 0 to log1p((T - t_x) / e0) -- the offset, never log(m + y) itself, so a width of 1e-12 keeps its
+// digits -- each at most 1 wide and at most PNBD_Q_SLOPE / |g' / g| wide, and stop early where g has fallen
+// by exp(-PNBD_Q_SPAN) and a panel no longer changes the sum.  The gradient is taken under the integral at
+// the same nodes: the means under g of log(m + y) = log e0 + d, log(M + y) = log(e0 + Delta) + log1p(q expm1(d))
+// and the two reciprocals.  No difference of two H values is formed.  ok = false: alpha_i or beta_i is not a
+// positive finite number any more.
+__host__ __device__ inline bool pnbd_si_quadrature(double x, double tx, double T, const Params& p, double* logsI,
+                                                   double dI[4]) {
+  constexpr double X[CLV_GL_Q] = CLV_GL_X_INIT, W[CLV_GL_Q] = CLV_GL_W_INIT;
+  const bool swap = p.a < p.b;  // alpha is the smaller offset
+  const double m = swap ? p.a : p.b;
+  const double pm = swap ? p.r + x : p.s + 1.0, pM = swap ? p.s + 1.0 : p.r + x;
+  const double e0 = m + tx, eD = e0 + fabs(p.a - p.b);
+  const double D = log1p((T - tx) / e0);
+  if (!(e0 > 0.0) || !(eD < INFINITY) || !(D < INFINITY)) return false;
+  const double q = e0 / eD;
+  double d = 0.0, Q = 0.0, Sd = 0.0, SL = 0.0, Sm = 0.0, SM = 0.0;
+  bool grew = true;
+  for (int k = 0; k < PNBD_Q_PANEL_CAP && d < D; ++k) {
+    const double em = expm1(d);
+    if ((1.0 - pm) * d - pM * log1p(q * em) < -PNBD_Q_SPAN && !grew) break;
+    const double slope = (1.0 - pm) - pM * (q * (em + 1.0) / (1.0 + q * em));
+    double hi = d + fmin(1.0, PNBD_Q_SLOPE / fabs(slope));
+    if (!(hi < D)) hi = D;
+    const double mid = 0.5 * (d + hi), half = 0.5 * (hi - d);
+    double c = 0.0, cd = 0.0, cL = 0.0, cm = 0.0, cM = 0.0;
+    for (int j = 0; j < CLV_GL_Q; ++j) {
+      const double dj = mid + half * X[j];
+      const double ej = expm1(dj), u = q * ej;
+      const double Lj = log1p(u);
+      const double g = W[j] * exp((1.0 - pm) * dj - pM * Lj);
+      c += g;
+      cd += g * dj;
+      cL += g * Lj;
+      cm += g / (e0 * (ej + 1.0));
+      cM += g / (eD * (1.0 + u));
+    }
+    const double nQ = Q + c * half;
+    grew = nQ != Q;
+    Q = nQ;
+    Sd += cd * half;
+    SL += cL * half;
+    Sm += cm * half;
+    SM += cM * half;
+    d = hi;
+  }
+  *logsI = -INFINITY;
+  for (int j = 0; j < 4; ++j) dI[j] = 0.0;
+  if (Q > 0.0) {
+    const double l0 = log(e0), lD = log(eD);
+    *logsI = log(p.s) + (((1.0 - pm) * l0 - pM * lD) + log(Q));
+    const double lm = l0 + Sd / Q, lM = lD + SL / Q, im = Sm / Q, iM = SM / Q;
+    const double rx = p.r + x, s1 = p.s + 1.0;
+    dI[0] = -(swap ? lm : lM);
+    dI[1] = -rx * (swap ? im : iM);
+    dI[2] = -(swap ? lM : lm) + 1.0 / p.s;
+    dI[3] = -s1 * (swap ? iM : im);
+  }
+  return true;
+}
+
 // One customer: log L, its gradient with respect to log(r, alpha, s, beta), and P(alive) =
-// A / (A + s I) with A the survivor term.  A series that hit the cap makes all of them NaN.
+// A / (A + s I) with A the survivor term.  A series that hit the cap makes all of them NaN.  MODE: where
+// s I comes from.  PNBD_SERIES: the series, whatever it needs.  PNBD_AUTO: the series as above where
+// z(t_x) <= PNBD_Z_SWITCH, the quadrature otherwise.  PNBD_QUADRATURE: the quadrature wherever t_x < T.
+// On the quadrature path conv = every result is finite.
 struct Point {
   double logL, g[4], p_alive;
   bool conv;
 };
 
+template <int MODE = PNBD_SERIES>
 __host__ __device__ inline Point pnbd_point(int32_t xi, double tx, double T, const Params& p) {
   const double x = (double)xi, rx = p.r + x;
   double dig = 0.0;  // psi(r + x) - psi(r)
@@ -151,7 +236,13 @@ __host__ __device__ inline Point pnbd_point(int32_t xi, double tx, double T, con
   double logsI = -INFINITY;
   double dI[4] = {0.0, 0.0, 0.0, 0.0};
   bool conv = true;
-  if (tx < T) {
+  bool quad = false;
+  if constexpr (MODE == PNBD_QUADRATURE) quad = tx < T;
+  if constexpr (MODE == PNBD_AUTO)
+    quad = tx < T && !(fabs(p.a - p.b) / ((p.a < p.b ? p.b : p.a) + tx) <= PNBD_Z_SWITCH);
+  if (MODE != PNBD_SERIES && quad) {
+    if (!pnbd_si_quadrature(x, tx, T, p, &logsI, dI)) logsI = std::numeric_limits<double>::quiet_NaN();
+  } else if (tx < T) {
     const LogH h1 = pnbd_log_h(tx, x, p), h2 = pnbd_log_h(T, x, p);
     conv = h1.conv && h2.conv;
     const double d = h2.lh - h1.lh;
@@ -175,6 +266,11 @@ __host__ __device__ inline Point pnbd_point(int32_t xi, double tx, double T, con
   const double scale[4] = {p.r, p.a, p.s, p.b};
   for (int j = 0; j < 4; ++j) o.g[j] = (base[j] + wA * dA[j] + wI * dI[j]) * scale[j];
   o.p_alive = wA;
+  if (MODE != PNBD_SERIES && quad) {
+    conv = (o.logL - o.logL == 0.0) & (wA - wA == 0.0);
+    for (int j = 0; j < 4; ++j) conv = conv & (o.g[j] - o.g[j] == 0.0);
+    o.conv = conv;
+  }
   if (!conv) {
     const double nan = std::numeric_limits<double>::quiet_NaN();
     o.logL = o.p_alive = nan;
@@ -230,7 +326,7 @@ struct CovSource {
 // w g_logbeta,i (-z2[k - k1][i]) after them, through the tile in groups of PNBD_COV_GROUP rows (the tile
 // is 8 rows high then, 7 without); a row's tree does not see the other rows, so the grouping is not in
 // the bits, and the first seven are the plain instance's.
-template <class Src>
+template <class Src, int MODE>
 __global__ __launch_bounds__(256) void pnbd_eval_kernel(const int32_t* x, const double* tx, const double* T,
                                                         const double* w, int64_t n, int64_t nb, Src src,
                                                         double* part /*[nb][PNBD_NS + k1 + k2]*/) {
@@ -244,7 +340,7 @@ __global__ __launch_bounds__(256) void pnbd_eval_kernel(const int32_t* x, const 
     double v[PNBD_NS] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     if (i < n) {
       const Params p = src.at(i);
-      const Point q = pnbd_point(x[i], tx[i], T[i], p);
+      const Point q = pnbd_point<MODE>(x[i], tx[i], T[i], p);
       const double wi = w ? w[i] : 1.0;
       v[0] = wi * q.logL;
       for (int j = 0; j < 4; ++j) v[1 + j] = wi * q.g[j];
@@ -275,14 +371,14 @@ __global__ __launch_bounds__(256) void pnbd_eval_kernel(const int32_t* x, const 
 
 // out[i] = log L, P(alive), E[Y(t*) | x, t_x, T]; with covariates E[Y(t*) | x, t_x, T, z_i] and then the
 // score components d log L_i / d log(r, alpha_i, s, beta_i).
-template <class Src>
+template <class Src, int MODE>
 __global__ __launch_bounds__(256) void pnbd_customers_kernel(const int32_t* x, const double* tx, const double* T,
                                                              int64_t n, Src src, double t_star,
                                                              double* out /*[n][3], with covariates [n][7]*/) {
   constexpr int W = Src::COV ? 7 : 3;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     const Params p = src.at(i);
-    const Point q = pnbd_point(x[i], tx[i], T[i], p);
+    const Point q = pnbd_point<MODE>(x[i], tx[i], T[i], p);
     const double Ti = T[i];
     out[i * W + 0] = q.logL;
     out[i * W + 1] = q.p_alive;
@@ -361,13 +457,14 @@ __host__ __device__ inline double pnbd_dert_integral(double s, double B, double 
 }
 
 // out[i] = P(alive), DERT = P(alive) (r + x) / (alpha_i + T) J(s, beta_i + T, delta, H).
+template <int MODE>
 __global__ __launch_bounds__(256) void pnbd_dert_kernel(const int32_t* x, const double* tx, const double* T,
                                                         int64_t n, CovSource src, double delta, double H,
                                                         double* out /*[n][2]*/) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     const Params p = src.at(i);
     const double Ti = T[i];
-    const Point q = pnbd_point(x[i], tx[i], Ti, p);
+    const Point q = pnbd_point<MODE>(x[i], tx[i], Ti, p);
     out[i * 2 + 0] = q.p_alive;
     out[i * 2 + 1] = q.p_alive * (p.r + (double)x[i]) / (p.a + Ti) * pnbd_dert_integral(p.s, p.b + Ti, delta, H);
   }
@@ -433,6 +530,16 @@ int check_track_values(int64_t n, const double* birth_week, const double* times,
   return CLV_OK;
 }
 
+// f(integral constant of the handle's mode): the kernel instance is chosen on the host.
+template <class F>
+void with_integral(const clv_pnbd* h, F f) {
+  switch (h->integral) {
+    case PNBD_AUTO: f(std::integral_constant<int, PNBD_AUTO>{}); break;
+    case PNBD_QUADRATURE: f(std::integral_constant<int, PNBD_QUADRATURE>{}); break;
+    default: f(std::integral_constant<int, PNBD_SERIES>{}); break;
+  }
+}
+
 CovSource cov_source(const clv_pnbd* h, const CovParams& c) {
   return CovSource{c, h->z1.as<const double>(), h->z2.as<const double>(), h->n};
 }
@@ -446,9 +553,11 @@ int eval_sums(clv_pnbd* h, const Src& src, int nc, const DevBuf& part, const Dev
   double res[PNBD_NS + 2 * PNBD_MAX_COV];
   int rc = launch_sums(
       [&] {
-        hipLaunchKernelGGL(pnbd_eval_kernel<Src>, dim3(grid_for(h->nb)), dim3(256), 0, nullptr, h->x.as<const int32_t>(),
-                           h->tx.as<const double>(), h->T.as<const double>(), h->w.as<const double>(), h->n, h->nb, src,
-                           part.as<double>());
+        with_integral(h, [&](auto mode) {
+          hipLaunchKernelGGL((pnbd_eval_kernel<Src, decltype(mode)::value>), dim3(grid_for(h->nb)), dim3(256), 0, nullptr,
+                             h->x.as<const int32_t>(), h->tx.as<const double>(), h->T.as<const double>(),
+                             h->w.as<const double>(), h->n, h->nb, src, part.as<double>());
+        });
       },
       part.as<const double>(), h->nb, PNBD_NS + nc, 1, out.as<double>(), res);
   if (rc) return rc;
@@ -463,8 +572,10 @@ template <class Src>
 int customer_rows(clv_pnbd* h, const Src& src, double t_star, double* out) {
   DeviceScope ds(h->device);
   return launch_rows((Src::COV ? 7 : 3) * (size_t)h->n, out, [&](double* d) {
-    hipLaunchKernelGGL(pnbd_customers_kernel<Src>, dim3(grid_for(h->nb)), dim3(256), 0, nullptr,
-                       h->x.as<const int32_t>(), h->tx.as<const double>(), h->T.as<const double>(), h->n, src, t_star, d);
+    with_integral(h, [&](auto mode) {
+      hipLaunchKernelGGL((pnbd_customers_kernel<Src, decltype(mode)::value>), dim3(grid_for(h->nb)), dim3(256), 0, nullptr,
+                         h->x.as<const int32_t>(), h->tx.as<const double>(), h->T.as<const double>(), h->n, src, t_star, d);
+    });
   });
 }
 
@@ -584,6 +695,14 @@ int clv_pnbd_set_covariates(clv_pnbd* h, int32_t k1, const double* z1, int32_t k
   return CLV_OK;
 }
 
+int clv_pnbd_set_integral(clv_pnbd* h, int32_t mode) {
+  if (mode != CLV_PNBD_INTEGRAL_SERIES && mode != CLV_PNBD_INTEGRAL_AUTO && mode != CLV_PNBD_INTEGRAL_QUADRATURE)
+    return fail(CLV_EINVAL, "pnbd: integral mode must be CLV_PNBD_INTEGRAL_SERIES, _AUTO or _QUADRATURE");
+  if (!h) return fail(CLV_EINVAL, "pnbd: null handle");
+  h->integral = mode;
+  return CLV_OK;
+}
+
 int clv_pnbd_eval_cov(clv_pnbd* h, const double* params, double* sums, int64_t* n_unconverged) {
   if (!h || !sums) return fail(CLV_EINVAL, "pnbd: null handle or sums");
   if (!h->has_cov) return fail(CLV_EINVAL, "pnbd: the handle has no covariates (clv_pnbd_set_covariates)");
@@ -613,8 +732,11 @@ int clv_pnbd_dert(clv_pnbd* h, const double* params, double delta, double horizo
     return fail(CLV_EINVAL, "pnbd: an infinite horizon needs a discount rate > 0");
   DeviceScope ds(h->device);
   return launch_rows(2 * (size_t)h->n, out, [&](double* d) {
-    hipLaunchKernelGGL(pnbd_dert_kernel, dim3(grid_for(h->nb)), dim3(256), 0, nullptr, h->x.as<const int32_t>(),
-                       h->tx.as<const double>(), h->T.as<const double>(), h->n, cov_source(h, c), delta, horizon, d);
+    with_integral(h, [&](auto mode) {
+      hipLaunchKernelGGL(pnbd_dert_kernel<decltype(mode)::value>, dim3(grid_for(h->nb)), dim3(256), 0, nullptr,
+                         h->x.as<const int32_t>(), h->tx.as<const double>(), h->T.as<const double>(), h->n,
+                         cov_source(h, c), delta, horizon, d);
+    });
   });
 }
 

@@ -379,6 +379,17 @@ class _WaldMixin:
 # Device handle
 # ---------------------------------------------------------------------------------------------
 MAX_COVARIATES = 8
+# How the likelihood's integral I is evaluated (clv_pnbd_set_integral): the series for every
+# customer (the default; NaN and a count past its 2,048-term cap), the series up to z(t_x) = 0.9 and the
+# quadrature of I itself past it, or the quadrature for every customer with t_x < T.
+INTEGRAL_MODES = {"series": 0, "auto": 1, "quadrature": 2}
+
+
+def integral_mode(integral) -> int:
+    """The C enum of ``integral``; ValueError for anything but "series", "auto" and "quadrature"."""
+    if not isinstance(integral, str) or integral not in INTEGRAL_MODES:
+        raise ValueError(f"integral must be one of {tuple(INTEGRAL_MODES)}; got {integral!r}")
+    return INTEGRAL_MODES[integral]
 
 
 class _Handle:
@@ -446,7 +457,9 @@ class PnbdData(_Handle):
     _DESTROY = "clv_pnbd_destroy"
 
     def __init__(self, frequency, recency, T, weights=None, *, device: int = -1, covariates=None,
-                 covariates_dropout=None):
+                 covariates_dropout=None, integral: str = "series"):
+        mode = integral_mode(integral)    # ValueError before the library is loaded
+        self.integral = "series"
         self.k1 = self.k2 = None          # None: no covariates in the handle
         cov = None
         if covariates is not None:
@@ -477,12 +490,20 @@ class PnbdData(_Handle):
         self._h = ctypes.c_void_p()
         check(L.clv_pnbd_create(int(device), self.n, self.x.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
                                 dptr(self.t_x), dptr(self.T), dptr(self.w), ctypes.byref(self._h)))
-        if cov is not None:
-            try:
+        try:
+            if mode != INTEGRAL_MODES["series"]:
+                self.set_integral(integral)
+            if cov is not None:
                 self.set_covariates(cov[0][0], cov[1][0])
-            except Exception:
-                self.close()
-                raise
+        except Exception:
+            self.close()
+            raise
+
+    def set_integral(self, integral: str):
+        """How every later evaluation of this handle forms I: "series", "auto" or "quadrature"
+        (clv_pnbd_set_integral)."""
+        check(self._L.clv_pnbd_set_integral(self._h, integral_mode(integral)))
+        self.integral = integral
 
     def set_covariates(self, z1, z2):
         """Covariates into the handle (clv_pnbd_set_covariates): z1 [K1][n] for the purchase process,
@@ -542,7 +563,8 @@ class PnbdData(_Handle):
 
     def eval(self, params):
         """(sums[6], n_unconverged): sum w log L, its derivatives with respect to
-        log(r, alpha, s, beta), sum w; customers whose series hit the term cap (sums[0] is NaN then)."""
+        log(r, alpha, s, beta), sum w; customers whose series hit the term cap (sums[0] is NaN then; in
+        the modes "auto" and "quadrature": customers with a result that is not finite)."""
         return self._evaluate(params, False)
 
     def customers(self, params, t_star: float = 0.0) -> np.ndarray:
@@ -568,11 +590,19 @@ class ParetoNBDFitter(_WaldMixin):
     beta_i = beta0 exp(-gamma2' z_i); ``params_`` then holds r, alpha (= alpha0), s, beta (= beta0),
     ``purchase:<name>`` per column of ``covariates`` and ``dropout:<name>`` per column of
     ``covariates_dropout`` (the same matrix unless given), and the penalty gains
-    penalizer_coef * sum(gamma^2)."""
+    penalizer_coef * sum(gamma^2).
+
+    ``integral`` is how every device evaluation of this fitter forms the likelihood's integral I
+    (DESIGN.md §4o): "series" (the default: a customer past the series' term cap, z of about 0.98, is
+    NaN and counted in ``n_unconverged_``), "auto" (the series with the same bits up to z(t_x) = 0.9, a
+    quadrature of I itself past it: what a covariate that moves alpha_i / beta_i by orders of magnitude
+    needs) or "quadrature" (the quadrature for every customer)."""
     _N_LOG = 4
     _NAMES = PARAM_NAMES
 
-    def __init__(self, penalizer_coef: float = 0.0):
+    def __init__(self, penalizer_coef: float = 0.0, *, integral: str = "series"):
+        integral_mode(integral)
+        self.integral = integral
         self.penalizer_coef = float(penalizer_coef)
         self.params_: Optional[pd.Series] = None
         self._device = -1
@@ -633,7 +663,7 @@ class ParetoNBDFitter(_WaldMixin):
             if p0.size != P or not (np.isfinite(p0).all() and (p0[:4] > 0.0).all()):
                 raise ValueError("initial_params must be four positive finite numbers" +
                                  (f", or those and the {P - 4} finite covariate coefficients" if cov else ""))
-        with PnbdData(frequency, recency, T, weights, device=device) as data:
+        with PnbdData(frequency, recency, T, weights, device=device, integral=self.integral) as data:
             if cov:
                 data.set_covariates(z1, z2)
             if p0 is None or not cov:
@@ -664,13 +694,13 @@ class ParetoNBDFitter(_WaldMixin):
         if self._k is None:
             if covariates is not None or covariates_dropout is not None:
                 raise ValueError("the model was fitted without covariates")
-            return PnbdData(frequency, recency, T, weights, device=self._device)
+            return PnbdData(frequency, recency, T, weights, device=self._device, integral=self.integral)
         if covariates is None:
             raise ValueError("the model was fitted with covariates: pass covariates=")
         if np.shape(covariates)[0] != int(np.asarray(frequency).reshape(-1).shape[0]):
             raise ValueError("covariates must have one row per customer")
         z1, z2 = self._customer_matrices(covariates, covariates_dropout)
-        data = PnbdData(frequency, recency, T, weights, device=self._device)
+        data = PnbdData(frequency, recency, T, weights, device=self._device, integral=self.integral)
         try:
             data.set_covariates(z1, z2)
         except Exception:
